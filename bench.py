@@ -2,6 +2,15 @@
 """Headline benchmark: gradient elements quantised per second, HSQ d=16 k=8 n=6.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload hsq|resnet50|qsgd] [--exchange MODE]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps (one window) and prints the headline line: `metric`, `value`,
+`unit`, `ms_per_step` (K steps' wall time / K), `higher_is_better`, `dtype`, the configuration and, with N > 1, the
+ranks the collectives joined.  `--full` adds everything else this script measures: the median of five windows of K
+steps, the roofline, the phase breakdown, the CPU baseline, the side variants, the `workloads` object and the
+per-transport exchange times (the extra objects below).  `--dump-outputs DIR` writes, after the timed steps, what
+the timed path computed in its last step as DIR/<name>.npy (float32 / float64, < 64 MB; a fixed, seeded sample of
+the larger outputs); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
 
 `--gpus N` with N > 1 from a bare shell launches its own N ranks (a child `python -m torch.distributed.run
 --nproc-per-node N ... bench.py ...`, started BEFORE anything touches the GPU); under torch.distributed.run
@@ -23,7 +32,7 @@ k_bit=8 n_bit=6 (quantizers/ps_quantizer.py:27-65): one multi-tensor encode, one
 Workload qsgd (BASELINE configs[4]): the same list with QSGDCompressor c_dim=128 n_bit=2 (packed 4-bit wire).
 Both hand every step fresh tensor objects of three input lists (apply() rebinds .grad.data like the reference).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline      dominant kernel: algorithmic bytes per launch / its average launch duration, measured with HIP
                 events attached to its dispatches inside the timed region; peak = 8 TB/s HBM3E.  `frac` is that kernel
                 alone, `frac_compress` SURVEY 8(d)'s own definition: 4.125 B x size / t(encode + levels).
@@ -109,6 +118,12 @@ def parse_args():
     ap.add_argument("--k-bit", type=int, default=0, help="--workload resnet50: codebook bits (default 8; 5 / 6: K = 32 / 64, the codebook files from tests/golden/codebooks)")
     ap.add_argument("--n-bit", type=int, default=0, help="--workload resnet50: level bits (default 6; main.py's own default is 8)")
     ap.add_argument("--no-variants", action="store_true", help="skip the untimed random=2 / 1e-3-scale side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: five timed windows (median reported), roofline, phase breakdown, CPU baseline, "
+                         "variants, the `workloads` object, per-transport exchange times.  The --no-* and --traffic options "
+                         "apply to this run only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -302,7 +317,7 @@ def live_traffic(workload, kernel_match):
         d = tempfile.mkdtemp(prefix="gq_pmc_", dir="/tmp")
         cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable,
                os.path.abspath(__file__), "--traffic-child", "--workload", workload, "--steps", "6", "--warmup", "2",
-               "--no-cpu-baseline", "--no-variants", "--traffic", "off"]
+               "--full", "--no-cpu-baseline", "--no-variants", "--traffic", "off"]
         try:
             # a child process (never an exec from this GPU-initialised process); the profiler's own program is python itself
             subprocess.run(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), timeout=150, stdout=subprocess.DEVNULL,
@@ -417,6 +432,43 @@ def issue_floor(clock_ghz, cus):
     if not clock_ghz:
         return None, isa
     return tiles * isa["issue_cycles_per_tile"] / (4.0 * cus) / (clock_ghz * 1e9) * 1e3, isa
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_BLOCKS = 250_000          # blocks of 16 consecutive elements kept of a larger output: 4,000,000 values, 16 MB
+
+
+def sample_index(np, nblk, count=DUMP_SAMPLE_BLOCKS, seed=0):
+    """The blocks sampled_blocks() keeps of `nblk`: `count` of them, seeded, ascending (all of them if there are no more)."""
+    if nblk <= count:
+        return np.arange(nblk)
+    return np.sort(np.random.RandomState(seed).choice(nblk, count, replace=False))
+
+
+def sampled_blocks(torch, np, flat, block=16):
+    """--dump-outputs: a fixed, seeded sample of the 1-D tensor `flat` -- whole blocks of `block` consecutive elements (one
+    HSQ subvector each, sample_index), as float32 on the host; the same blocks in every run.  A ragged tail of fewer than
+    `block` elements is never sampled."""
+    nblk = flat.numel() // block
+    idx = torch.from_numpy(sample_index(np, nblk)).to(flat.device)
+    return flat[:nblk * block].view(nblk, block)[idx].float().reshape(-1).cpu().numpy()
+
+
+def checksums(torch, tensors):
+    """float64 [len(tensors), 2]: sum and sum of squares of each tensor (covers what a sample leaves out)."""
+    return torch.stack([torch.stack([t.double().sum(), t.double().square().sum()]) for t in tensors]).cpu().numpy()
+
+
+def write_outputs(np, dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32, or float64 for the checksums); integer outputs such as codes
+    and levels are below 2**24 and convert exactly."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def event_ms(torch, fn, n=50, warm=10):
@@ -698,16 +750,18 @@ def run_hsq(args, torch, np, dist, native, exchange, dev, rank, world, backend, 
     # HIP events on the dominant kernel, live in the timed region: a start/stop pair ATTACHED to the encode's
     # dispatch (hipExtLaunchKernelGGL: gq_hsq_encode_ex's profile_slot) on up to 16 of the steps.  An event bracket
     # recorded around the call would also measure 5-8 us of queue bubbles and put them into the timed
-    # region (calibrated below for reference).
+    # region (calibrated below for reference).  --full only: a plain run arms nothing.
     stride = max(1, -(-args.steps // 16))          # at most 16 armed steps: an armed dispatch costs a few us of its own
-    armed = list(range(0, args.steps, stride))[:16]
+    armed = list(range(0, args.steps, stride))[:16] if args.full else []
     slot_of = {i: k for k, i in enumerate(armed)}
-    # TIMED_WINDOWS windows of exactly --steps steps each, every one bracketed by barrier + synchronize on both sides and
-    # reduced to the slowest rank; the line reports the MEDIAN window (ms_per_step, value) with the fastest and slowest next
-    # to it: one window of 20 steps is 1.2 ms of wall clock, and single windows differ by a few percent on one box.
+    # --full: TIMED_WINDOWS windows of exactly --steps steps each, every one bracketed by barrier + synchronize on both sides
+    # and reduced to the slowest rank; the line reports the MEDIAN window (ms_per_step, value) with the fastest and slowest
+    # next to it: one window of 20 steps is 1.2 ms of wall clock, and single windows differ by a few percent on one box.
+    # A plain run times one window: exactly --steps steps.
+    windows = TIMED_WINDOWS if args.full else 1
     window_dt = []
-    for w in range(TIMED_WINDOWS):
-        watch("timed window %d of %d" % (w + 1, TIMED_WINDOWS), transport=mode, steps=args.steps)
+    for w in range(windows):
+        watch("timed window %d of %d" % (w + 1, windows), transport=mode, steps=args.steps)
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -720,6 +774,38 @@ def run_hsq(args, torch, np, dist, native, exchange, dev, rank, world, backend, 
             dt = float(t.item())
         window_dt.append(dt)
     dt = float(np.median(window_dt))
+    ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as a caller receives them: this rank's wire and the decoded mean
+        if mode == "split":
+            wire_out = {"codes": s_codes, "levels_a": s_la, "levels_b": s_lb, "lb_ub": s_lbub}
+        else:
+            wire_out = {"codes": codes, "levels": levels, "lb_ub": lb_ub}
+        dumped = {k: v.float().cpu().numpy() for k, v in wire_out.items()}
+        dumped["decoded_sample"] = sampled_blocks(torch, np, out, C_DIM)
+        dumped["decoded_checksums"] = checksums(torch, [out])
+        write_outputs(np, args.dump_outputs, dumped)
+    line = None if rank != 0 else {
+        "metric": "gradient elements quantized/sec (HSQ d=16 k=8)", "value": world * SIZE * args.steps / dt, "unit": "elements/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "value_is": "end_to_end (encode + levels" + (" + exchange" if world > 1 else "") + " + decode-mean per step); "
+                    "compress_only holds the encode + levels rate (SURVEY 8d's definition)",
+        "prewarm_steps": prewarm,
+        "config": {"workload": "synthetic 25,000,000-float32 flat gradient per rank, HSQ c_dim=16 k_bit=8 "
+                               "n_bit=6 (BASELINE configs[%d]), step = encode+levels" % (1 if world == 1 else 3)
+                               + ("+exchange(%s)" % mode if world > 1 else "") + "+decode-mean",
+                   "elements_per_rank": SIZE, "random": args.random, "ranks": world,
+                   "wire_levels": "packed6" if packed6 else "bytes", "wire_bytes_per_rank": wire.nbytes,
+                   "inputs": "3 gradients of 100 MB used in turn (never Infinity-Cache resident)"},
+    }
+    if not args.full:
+        counted = ranks_counted(torch, dist, dev) if world > 1 else 1
+        if rank == 0 and world > 1:
+            line["exchange"] = exchange_report(torch, counted, sex if mode == "split" else ex, mode, args.exchange, backend, world,
+                                               None, None, (swire if mode == "split" else wire).nbytes)
+            line["exchange"]["autotune_ms"] = ex.timings_ms
+        return line
     enc_ms = float(np.mean([native.profile_read(k) for k in range(len(armed))]))
     identical = ranks_agree(torch, dist, world, [out])
 
@@ -791,30 +877,16 @@ def run_hsq(args, torch, np, dist, native, exchange, dev, rank, world, backend, 
 
     if rank != 0:
         return None
-    ms_per_step = dt / args.steps * 1e3
-    value = world * SIZE * args.steps / dt
     achieved = ALGO_BYTES_PER_ELEM * SIZE / (enc_ms * 1e-3) / 1e9
     achieved_compress = ALGO_BYTES_PER_ELEM * SIZE / (cmp_ms * 1e-3) / 1e9
     traffic, traffic_source = traffic_for(args, world, "hsq", "hsq_encode_pf_kernel", "hsq_encode_hbm_bytes_per_launch")
     clock, clock_source = (None, "not measured (N > 1 or a PMC child run)") if (world > 1 or args.traffic_child) else in_kernel_clock()
     clock_ghz = clock["in_kernel_clock_ghz"] if clock else None
     floor_ms, isa = issue_floor(clock_ghz, native.device_info(dev.index)[0])
-    line = {
-        "metric": "gradient elements quantized/sec (HSQ d=16 k=8)", "value": value, "unit": "elements/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+    line.update({
         "ms_per_step_min": min(window_dt) / args.steps * 1e3, "ms_per_step_max": max(window_dt) / args.steps * 1e3,
         "timed_windows": {"count": len(window_dt), "steps_each": args.steps, "ms_per_step": [d / args.steps * 1e3 for d in window_dt],
                           "reported": "median window (value and ms_per_step); kernel_ms: events on the first window's dispatches"},
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "value_is": "end_to_end (encode + levels" + (" + exchange" if world > 1 else "") + " + decode-mean per step); "
-                    "compress_only holds the encode + levels rate (SURVEY 8d's definition)",
-        "prewarm_steps": prewarm,
-        "config": {"workload": "synthetic 25,000,000-float32 flat gradient per rank, HSQ c_dim=16 k_bit=8 "
-                               "n_bit=6 (BASELINE configs[%d]), step = encode+levels" % (1 if world == 1 else 3)
-                               + ("+exchange(%s)" % mode if world > 1 else "") + "+decode-mean",
-                   "elements_per_rank": SIZE, "random": args.random, "ranks": world,
-                   "wire_levels": "packed6" if packed6 else "bytes", "wire_bytes_per_rank": wire.nbytes,
-                   "inputs": "3 gradients of 100 MB used in turn (never Infinity-Cache resident)"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                      "algorithmic_bytes": ALGO_BYTES_PER_ELEM * SIZE,
@@ -853,7 +925,7 @@ def run_hsq(args, torch, np, dist, native, exchange, dev, rank, world, backend, 
                               "can add up to ~1 us more than ms_per_step"},
         "compress_only": {"value": world * SIZE / (cmp_ms * 1e-3), "unit": "elements/s"},
         "ranks_bit_identical": identical,
-    }
+    })
     rep = exchange_report(torch, counted, sex if mode == "split" else ex, mode, args.exchange, backend, world, exch_ms, exch_by,
                           (swire if mode == "split" else wire).nbytes) if world > 1 else None
     if rep:
@@ -1100,9 +1172,9 @@ def run_list(args, torch, np, dist, native, exchange, dev, rank, world, backend,
     for i in range(prewarm + args.warmup):      # (--exchange auto: the first apply() times the transports)
         step(i)
     # HIP events attached to the dominant kernel's dispatch on up to 16 of the timed steps (HSQ: the multi-tensor
-    # prefilter encode takes them: gq_hsq_batch.profile_slot)
+    # prefilter encode takes them: gq_hsq_batch.profile_slot); --full only
     stride = max(1, -(-args.steps // 16))
-    armed = list(range(0, args.steps, stride))[:16] if (hsq and not args.graph) else []     # (a replayed graph has no armed dispatch)
+    armed = list(range(0, args.steps, stride))[:16] if (hsq and not args.graph and args.full) else []     # (a replayed graph has no armed dispatch)
     slot_of = {prewarm + args.warmup + i: k for k, i in enumerate(armed)}
     Grp = BatchedHSQ if hsq else BatchedQSGD
     grp = [g[2] for g in q._groups if isinstance(g[2], Grp) and not getattr(g[2], "wide", False)][0]
@@ -1119,6 +1191,45 @@ def run_list(args, torch, np, dist, native, exchange, dev, rank, world, backend,
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as a caller receives them: every parameter's .grad (the decoded mean)
+        outs = [p.grad.data.reshape(-1) for p in params]
+        write_outputs(np, args.dump_outputs, {"grads_sample": sampled_blocks(torch, np, torch.cat(outs)),
+                                              "grads_checksums": checksums(torch, outs)})
+    if hsq:
+        dd = qargs.c_dim
+        metric = "gradient elements quantized/sec (HSQ d=%d k=8, ResNet-50 list)" % dd
+        cfg = ("ResNet-50/CIFAR parameter list (161 tensors, %d elements) per rank through PSQuantizer.record + apply, HSQ c_dim=%d "
+               "k_bit=%d n_bit=%d random=1 on-device draws%s%s (%s), byte wire, multi-tensor kernels"
+               % (n, dd, qargs.k_bit, qargs.n_bit, ", error feedback" if args.ef else "", ", two-phase" if args.two_phase else "",
+                  "BASELINE configs[2]; the README's hsq command" if (dd == 16 and qargs.n_bit == 6 and qargs.k_bit == 8) else "main.py:90-92's own defaults" if (dd == 32 and qargs.n_bit == 8 and qargs.k_bit == 8) else "a variant"))
+    else:
+        metric = "gradient elements quantized/sec (QSGD c_dim=128 n_bit=2, ResNet-50 list)"
+        cfg = ("ResNet-50/CIFAR parameter list (161 tensors, %d elements) per rank, QSGD c_dim=128 n_bit=2 "
+               "random=1 (BASELINE configs[4]), packed 4-bit wire, multi-tensor kernels" % n)
+    line = None if rank != 0 else {
+        "metric": metric, "value": world * n * args.steps / dt,
+        "unit": "elements/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "value_is": "end_to_end: PSQuantizer.record + apply per step (compress, " + ("exchange, " if world > 1 else "")
+                    + "decode-mean, small tensors dense), host launch time included",
+        "prewarm_steps": prewarm,
+        "config": {"workload": cfg, "elements_per_rank": n, "ranks": world, "wire_bytes_per_rank": q.wire_bytes_per_user(),
+                   "inputs": "3 gradient lists used in turn, N(0,1)*1e-3: before every step the next list is put under the parameters' "
+                             "existing .grad objects (in place, as autograd writes gradients) by the library's C++ helper, inside the timed region",
+                   "launches": ("gq_graph: record() and apply() replay their device work from HIP graphs (one per set of gradient "
+                                "addresses / output buffer; %d + %d captured), stochastic rounding with draws keyed by each tensor's "
+                                "(lb, ub) / each bucket's norm (gq_rng = 'keyed')" % (
+                                    sum(1 for e in q._rec_graphs.values() if e[1] is not None),
+                                    sum(1 for e in q._apply_graphs.values() if e[1] is not None))) if args.graph
+                               else "eager: ten launches and copies per record + apply; per-call seeds for the on-device draws"},
+    }
+    if not args.full:
+        counted = ranks_counted(torch, dist, dev) if world > 1 else 1
+        if rank == 0 and world > 1 and q._ex is not None:
+            line["exchange"] = exchange_report(torch, counted, q._ex, q.exchange_mode, args.exchange, backend, world, None, None,
+                                               q.wire_bytes_per_user())
+        return line
     identical = ranks_agree(torch, dist, world, [p.grad.data for p in params if p.numel() > 1000][:8])
 
     # untimed: the kernels of the step alone, back to back between two HIP events on the stream they are launched on
@@ -1154,15 +1265,10 @@ def run_list(args, torch, np, dist, native, exchange, dev, rank, world, backend,
         return None
     if hsq:
         k_ms = float(np.mean([native.profile_read(k) for k in range(len(armed))]))
-        dd = qargs.c_dim
         algo = (4.0 + 2.0 / dd) * k_elems      # 4 B read + (code + level) per dd elements
         kernel = ("gq_hsq_encode_batched = hsq_encode_pf_kernel<uint8_t, BATCHED> (ONE launch for the 76 codebook-compressed "
                   "tensors: prefilter, exact rescoring, in-place fix-up, per-tensor lb/ub by atomics)")
-        match, metric = "hsq_encode_pf_kernel", "gradient elements quantized/sec (HSQ d=%d k=8, ResNet-50 list)" % dd
-        cfg = ("ResNet-50/CIFAR parameter list (161 tensors, %d elements) per rank through PSQuantizer.record + apply, HSQ c_dim=%d "
-               "k_bit=%d n_bit=%d random=1 on-device draws%s%s (%s), byte wire, multi-tensor kernels"
-               % (n, dd, qargs.k_bit, qargs.n_bit, ", error feedback" if args.ef else "", ", two-phase" if args.two_phase else "",
-                  "BASELINE configs[2]; the README's hsq command" if (dd == 16 and qargs.n_bit == 6 and qargs.k_bit == 8) else "main.py:90-92's own defaults" if (dd == 32 and qargs.n_bit == 8 and qargs.k_bit == 8) else "a variant"))
+        match = "hsq_encode_pf_kernel"
         note = ("kernel_ms: HIP start/stop events attached to the encode's dispatch on %d %s; compress_ms = encode + "
                 "levels launches back to back after the timed region; a replayed step is bound by its kernels (the host issues one in ~40 us), an eager one by the host"
                 % (len(armed), "eager steps run after the timed region (a replayed graph has no armed dispatch)" if args.graph
@@ -1171,30 +1277,13 @@ def run_list(args, torch, np, dist, native, exchange, dev, rank, world, backend,
         k_ms = cmp_ms
         algo = QSGD_ALGO_BYTES_PER_ELEM * k_elems
         kernel = "gq_qsgd_compress_batched = qsgd_compress_batched4_kernel"
-        match, metric = "qsgd_compress_batched4_kernel", "gradient elements quantized/sec (QSGD c_dim=128 n_bit=2, ResNet-50 list)"
-        cfg = ("ResNet-50/CIFAR parameter list (161 tensors, %d elements) per rank, QSGD c_dim=128 n_bit=2 "
-               "random=1 (BASELINE configs[4]), packed 4-bit wire, multi-tensor kernels" % n)
+        match = "qsgd_compress_batched4_kernel"
         note = ("HIP events around 50 back-to-back launches after the timed region (a replayed step is bound by its two kernels, "
                 "compress + decode-mean; an eager one by the host)")
     achieved = algo / (k_ms * 1e-3) / 1e9
     achieved_compress = algo / (cmp_ms * 1e-3) / 1e9
     traffic, traffic_source = traffic_for(args, world, args.workload, match, None)
-    line = {
-        "metric": metric, "value": world * n * args.steps / dt,
-        "unit": "elements/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "value_is": "end_to_end: PSQuantizer.record + apply per step (compress, " + ("exchange, " if world > 1 else "")
-                    + "decode-mean, small tensors dense), host launch time included",
-        "prewarm_steps": prewarm,
-        "config": {"workload": cfg, "elements_per_rank": n, "ranks": world, "wire_bytes_per_rank": q.wire_bytes_per_user(),
-                   "inputs": "3 gradient lists used in turn, N(0,1)*1e-3: before every step the next list is put under the parameters' "
-                             "existing .grad objects (in place, as autograd writes gradients) by the library's C++ helper, inside the timed region",
-                   "launches": ("gq_graph: record() and apply() replay their device work from HIP graphs (one per set of gradient "
-                                "addresses / output buffer; %d + %d captured), stochastic rounding with draws keyed by each tensor's "
-                                "(lb, ub) / each bucket's norm (gq_rng = 'keyed')" % (
-                                    sum(1 for e in q._rec_graphs.values() if e[1] is not None),
-                                    sum(1 for e in q._apply_graphs.values() if e[1] is not None))) if args.graph
-                               else "eager: ten launches and copies per record + apply; per-call seeds for the on-device draws"},
+    line.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes": algo,
                      "frac_compress": achieved_compress / HBM_PEAK_GBS, "compress_ms": cmp_ms,
@@ -1204,7 +1293,7 @@ def run_list(args, torch, np, dist, native, exchange, dev, rank, world, backend,
                               "transport alone; with N > 1 the decode-mean of the step runs over R = n_gpus payloads"},
         "compress_only": {"value": world * k_elems / (cmp_ms * 1e-3), "unit": "elements/s"},
         "ranks_bit_identical": identical,
-    }
+    })
     if world > 1 and q._ex is not None:
         line["exchange"] = exchange_report(torch, counted, q._ex, q.exchange_mode, args.exchange, backend, world, exch_ms, exch_by,
                                            q.wire_bytes_per_user())

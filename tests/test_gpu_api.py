@@ -1557,7 +1557,7 @@ def test_bench_two_rank_code_path_on_one_gpu():
     env = dict(os.environ, GQ_BENCH_BACKEND="gloo")
     port = 29650 + (os.getpid() % 300)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1566,6 +1566,56 @@ def test_bench_two_rank_code_path_on_one_gpu():
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["scaling"] == "weak" and d["value"] > 0
     assert d["config"]["ranks"] == 2 and "cpu_baseline" not in d and d["roofline"]["kernel_ms"] > 0
 
+
+
+@pytest.mark.parametrize("workload", ["hsq", "qsgd"])
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(workload, tmp_path, oracle):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one JSON line with the headline keys only
+    (none of --full's objects), `steps` == K, and DIR/<name>.npy in float32 / float64 under 64 MB -- bit-identical from one
+    run to the next.  hsq: the dumped wire decodes (CPU oracle) to the dumped sample of the decoded gradient."""
+    import json
+    import subprocess
+    root = os.path.dirname(HERE)
+    sys.path.insert(0, root)
+    import bench
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--workload", workload,
+               "--dump-outputs", d]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-1500:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["n_gpus"] == 1 and line["dtype"] == "f32"
+        assert line["higher_is_better"] is True and line["unit"] == "elements/s" and line["value"] > 0 and line["ms_per_step"] > 0
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 - line["config"]["elements_per_rank"]) < 1e-6 * line["value"]
+        for extra in ("roofline", "phases_ms", "cpu_baseline", "workloads", "variants", "timed_windows", "ranks_bit_identical"):
+            assert extra not in line, extra
+        files = sorted(os.listdir(d))
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert files and all(f.endswith(".npy") for f in files)
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        dumps.append(got)
+    assert set(dumps[0]) == set(dumps[1])
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name].view(np.uint8), dumps[1][name].view(np.uint8)), name
+    got = dumps[0]
+    if workload == "hsq":
+        from gq_amd.codebook import load_codebook
+        assert set(got) == {"codes", "levels", "lb_ub", "decoded_sample", "decoded_checksums"}
+        M = bench.SIZE // bench.C_DIM
+        assert got["codes"].shape == (M,) and got["levels"].shape == (M,) and got["lb_ub"].shape == (2,)
+        dec = oracle.hsq_decompress(got["codes"].astype(np.int32), got["levels"].astype(np.int32), got["lb_ub"][0], got["lb_ub"][1],
+                                    load_codebook(bench.C_DIM, 1 << bench.K_BIT), bench.N_BIT)
+        want = dec.reshape(M, bench.C_DIM)[bench.sample_index(np, M)].reshape(-1)
+        assert np.array_equal(got["decoded_sample"].view(np.uint32), want.view(np.uint32))
+        assert got["decoded_checksums"].shape == (1, 2)
+    else:
+        assert set(got) == {"grads_sample", "grads_checksums"} and got["grads_checksums"].shape == (161, 2)
+        assert np.isfinite(got["grads_sample"]).all() and got["grads_sample"].size == bench.DUMP_SAMPLE_BLOCKS * 16
 
 
 def test_integration_example_runs():
@@ -1612,7 +1662,7 @@ def test_bench_fails_when_the_collectives_joined_fewer_ranks_than_were_launched(
 @pytest.mark.parametrize("extra", [[], ["--exchange", "split"], ["--exchange", "auto"], ["--workload", "qsgd"], ["--workload", "resnet50"],
                                    ["--exchange", "pipelined"], ["--exchange", "pipelined", "--workload", "resnet50"]])
 def test_bench_launches_its_own_ranks(extra):
-    """`python bench.py --gpus 2` from a bare shell (no RANK / WORLD_SIZE): bench.py starts its own two ranks before
+    """`python bench.py --gpus 2 --full` from a bare shell (no RANK / WORLD_SIZE): bench.py starts its own two ranks before
     anything touches the GPU and rank 0 prints the one JSON line (GQ_BENCH_BACKEND=gloo: both ranks share this GPU)."""
     import json
     import subprocess
@@ -1620,7 +1670,7 @@ def test_bench_launches_its_own_ranks(extra):
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["GQ_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"] + extra
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

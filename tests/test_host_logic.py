@@ -620,23 +620,31 @@ def test_run_reference_launcher_shadows_the_reference_packages(tmp_path):
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/codebooks"), reason="reference checkout not present")
 def test_codebooks_are_found_in_a_reference_checkout_cwd(tmp_path):
-    """Run from the reference checkout (build container only): `./codebooks/learned_codebook/...`
-    relative to the cwd is what gets opened, as in nearest_neighbor_compressor.py:50-51."""
+    """Run from a reference-style checkout: `./codebooks/learned_codebook/...` relative to the cwd is what gets
+    opened, as in nearest_neighbor_compressor.py:50-51.  The checkout is a stand-in with one d=40 K=1024 codebook
+    (a shape neither the package nor tests/golden ships), written here in the .fvecs format."""
+    ref = tmp_path / "ref"
+    cbdir = ref / "codebooks" / "learned_codebook"
+    cbdir.mkdir(parents=True)
+    rows = np.random.RandomState(40).standard_normal((1024, 40)).astype(np.float32)
+    raw = np.empty((1024, 41), dtype="<i4")
+    raw[:, 0] = 40
+    raw[:, 1:] = rows.view("<i4")
+    raw.tofile(str(cbdir / "angular_dim_40_Ks_1024.fvecs"))
     script = tmp_path / "probe.py"
     script.write_text(
         "from compressors import *\n"
         "import torch, gq_amd.codebook as cbk\n"
         "from argparse import Namespace\n"
         "a = Namespace(c_dim=40, k_bit=10, n_bit=8, no_cuda=False, random=True)\n"
-        "c = NearestNeighborCompressor(40 * 50, torch.Size([50, 40]), a)\n"     # d=40, K=1024: only in the reference tree
+        "c = NearestNeighborCompressor(40 * 50, torch.Size([50, 40]), a)\n"     # d=40, K=1024: only in the checkout's tree
         "assert c.codewords.shape == (1024, 40) and cbk.codebook_path(40, 1024).startswith('./codebooks')\n"
         "print('ok')\n")
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
     env.pop("GQ_CODEBOOK_DIR", None)
     out = subprocess.run([sys.executable, "-B", os.path.join(PKG, "run_reference.py"), str(script)],
-                         cwd="/root/reference", env=env, capture_output=True, text=True, timeout=300)
+                         cwd=str(ref), env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 
@@ -868,6 +876,29 @@ def test_bench_watchdog_exits_with_its_code_and_says_what_was_in_flight():
             "w = bench.Watchdog(0, 1, 0.5); w.enter('x'); time.sleep(2.0); print('one rank: no watchdog')\n" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "no watchdog" in r.stdout
+
+
+def test_bench_dump_helpers_sample_fixed_blocks_and_keep_the_size_limit(tmp_path):
+    """bench.py --dump-outputs' helpers (no GPU): the sample of a large output is whole 16-element blocks at seeded,
+    ascending positions, the same on every call; a small output is kept whole; arrays are written as float32 .npy files
+    (float64 ones stay float64); more than 64 MB of outputs is refused before anything is written."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    flat = torch.arange(16 * 300_000 + 5, dtype=torch.float32)
+    a = bench.sampled_blocks(torch, np, flat)
+    idx = bench.sample_index(np, 300_000)
+    assert a.dtype == np.float32 and a.size == bench.DUMP_SAMPLE_BLOCKS * 16
+    assert np.array_equal(a, bench.sampled_blocks(torch, np, flat.clone())) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a.reshape(-1, 16), (idx[:, None] * 16 + np.arange(16)).astype(np.float32))
+    assert np.array_equal(bench.sampled_blocks(torch, np, torch.arange(64.0)), np.arange(64, dtype=np.float32))
+    d = str(tmp_path / "out")
+    bench.write_outputs(np, d, {"codes": np.arange(10, dtype=np.uint8), "sums": np.ones((3, 2))})
+    codes, sums = np.load(os.path.join(d, "codes.npy")), np.load(os.path.join(d, "sums.npy"))
+    assert codes.dtype == np.float32 and np.array_equal(codes, np.arange(10)) and sums.dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.write_outputs(np, str(tmp_path / "big"), {"x": np.zeros(17 << 20, np.float32)})
+    assert not os.path.exists(str(tmp_path / "big"))
 
 
 def test_qsgd_bucket_placement_rules(monkeypatch):
