@@ -5,7 +5,9 @@ device memory, through gq_amd.native).
     DenseCodec                 IdenticalCompressor tensors (<= 1000 elements, ps_quantizer.py:18-19): raw f32
     HSQCodec / QSGDCodec       one tensor per launch (the reference's per-tensor loop, nearest_neighbor_compressor.py:63-90,
                                qsgd_compressor.py:42-71)
-    BatchedHSQ / BatchedQSGD   every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
+    TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
+    BatchedHSQ / BatchedQSGD / BatchedTopK
+                               every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
 `codec_factory` arguments of the quantizers exist so that the host logic can be exercised without a GPU by the tests
@@ -17,8 +19,8 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (IdenticalCompressor, NearestNeighborCompressor, QSGDCompressor, _next_seed,
-                          _require_device)
+from .compressors import (IdenticalCompressor, NearestNeighborCompressor, QSGDCompressor, TopKSparsificationCompressor,
+                          _next_seed, _require_device)
 
 
 def _up(x, a=16):
@@ -361,6 +363,63 @@ class QSGDCodec(object):
         self._decode_rows(gathered, off, R, out, plain=plain)
         if R == 1 and not plain:
             out.add_(0.0)   # as HSQCodec.decode_mean: torch.stack(...).mean(0) of one payload turns -0 into +0
+        return out.view(self.shape)
+
+
+class TopKCodec(object):
+    """TopKSparsificationCompressor on the HIP kernels (libgq_topk.so).  Wire per tensor: k = numel // cr ascending uint32
+    indices, then the k f32 values -- 8k bytes.  Every call is a one-tensor BatchedTopK; roundtrip / encode_decode_into return the
+    compress launch's own dense decode (v * mask, the reference's signed zeros and NaNs included), not a decode of the wire."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.k = int(compressor.k)
+        if not 0 <= self.k <= numel:
+            raise ValueError("TopKCodec: k = %d for a tensor of %d elements" % (self.k, numel))
+        self.nbytes = 8 * self.k
+        self._single = None
+
+    def _batched1(self, dev):
+        if self._single is None or self._single.device != dev:
+            self._single = BatchedTopK([self], [0], [0], dev, 1, max(16, self.nbytes))
+        return self._single
+
+    @staticmethod
+    def _at(wire_user, off):
+        # (k = 0 writes nothing: any valid address will do when the section is empty and ends the buffer)
+        return wire_user[off:] if off < wire_user.numel() else wire_user
+
+    def encode_decode_into(self, grad, wire_user, off, salt, out):
+        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch sequence."""
+        _require_device(grad, "TopKCodec.encode_decode_into")
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt, out=out.view(-1))
+        assert ok, "TopKCodec: the gradient must be a float32 tensor on the current device"
+
+    def encode_into(self, grad, wire_user, off, salt):
+        _require_device(grad, "TopKCodec.encode_into")
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt)
+        assert ok, "TopKCodec: the gradient must be a float32 tensor on the current device"
+
+    def roundtrip(self, grad, salt):
+        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
+        tmp = torch.empty(max(16, self.nbytes), dtype=torch.uint8, device=grad.device)
+        self.encode_decode_into(grad, tmp, 0, salt, out)
+        return out.view(self.shape)
+
+    def decode_wire(self, wire_user, off, out):
+        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
+
+    def _decode_rows(self, gathered, off, R, out, plain=False):
+        if self.k == 0:
+            out.zero_()
+            return
+        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
+
+    def decode_mean(self, gathered, off, R, plain=False):
+        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        self._decode_rows(gathered, off, R, out, plain=plain)
         return out.view(self.shape)
 
 
@@ -912,6 +971,103 @@ class BatchedQSGD(_BatchedBase):
         return True
 
 
+class BatchedTopK(_BatchedBase):
+    """All TopKSparsificationCompressor tensors in ONE gq_topk_compress_batched sequence (eight launches: three radix passes with
+    a per-tensor pick behind each, counts, scan, write -- include/gq_topk.h) and ONE gq_topk_decode_sum_batched launch.  No
+    draws: every launch replays from a HIP graph.  The compress also writes the dense decoded tensors (v * mask) where a caller
+    asks for them: error feedback takes its residual from them, and the two-phase re-compress returns them, bit for bit the
+    reference's decompress(compress(g))."""
+
+    takes_tail = False
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is TopKCodec
+
+    @staticmethod
+    def group_key(codec):
+        return ()
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        self.idxs = list(idxs)
+        self.codecs = [codecs[i] for i in self.idxs]
+        nseg = len(self.idxs)
+        chunk = native.TOPK_CHUNK
+        table = torch.zeros((nseg, 8), dtype=torch.int64)
+        item_seg = []
+        item, out_off = 0, 0
+        self.out_off = []
+        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
+            items = max(1, -(-cd.numel // chunk))
+            table[s, 1], table[s, 2], table[s, 3], table[s, 4], table[s, 5] = cd.numel, item, offsets[i], cd.k, out_off
+            item_seg += [s] * items
+            item += items
+            self.out_off.append(out_off)
+            out_off += cd.numel
+        self.out_floats = out_off
+        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
+        self._item_seg, self._nitems = self.item_seg, item
+        self._setup(table, None, device, slots, user_bytes, dense)
+        self.align = 4
+        self.random = False
+        # the select's scratch (include/gq_topk.h): the histograms start zero and every compress leaves them zero
+        self._hist = torch.zeros(nseg * native.TOPK_HIST_BINS, dtype=torch.int32, device=device)
+        self._state = torch.zeros(nseg * 4, dtype=torch.int32, device=device)
+        self._counts = torch.zeros(item * 2, dtype=torch.int32, device=device)
+        self._ef_out = None         # the decoded tensors an error-feedback record needs and nobody asked for
+        self._batch = native.TopKBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self._hist, self._state, self._counts)
+
+    def graphable(self):
+        return True
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None):
+        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
+        feedback in the same launches (t += ef_scale*err before the select, err = t - decoded after it, both in place).
+        graph_header, dense, table_current: see BatchedHSQ.encode."""
+        if graph_header is not None:
+            self._graph_tables(graph_header, dense)
+        elif table_current:
+            self._batch.set_table(self._dev[:self._table_words])
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        elif not self._upload(tensors, slot, self.align, errs, dense):
+            return False
+        else:
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        ef = ef_scale if errs is not None else None
+        if ef is not None and out is None:
+            if self._ef_out is None or self._ef_out.device != wire_user.device:
+                self._ef_out = torch.empty(self.out_floats, dtype=torch.float32, device=wire_user.device)
+            out = self._ef_out
+        try:
+            self._batch.compress(wire_user, out, ef)
+        except BaseException:
+            if graph_header is not None:
+                self._graph_tables_abort()
+            raise
+        if graph_header is not None:
+            self._graph_tables_done(defer_reset)
+        return True
+
+    def decode_into(self, gathered, R, out, plain=False):
+        """The decode-mean launch into a caller's buffer (TopKCodec: a one-tensor group, its section at offset 0 of the rows)."""
+        if not self.ready:
+            self.upload_layout()
+        self._batch.decode(gathered, R, out, plain=plain)
+
+    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
+        """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode (the reference's signed
+        zeros and NaNs, which the wire does not carry).  See _BatchedBase.roundtrip."""
+        if self._tmp_wire is None:
+            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
+        out, views = self._out_buffer(self.device)
+        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
+        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, out=out, **kw):
+            self._out_turn ^= 1      # (the buffer was not used)
+            return None
+        return views
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, IdenticalCompressor):
         return DenseCodec(compressor, numel, shape)
@@ -919,4 +1075,6 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return HSQCodec(compressor, numel, shape, packed6)
     if isinstance(compressor, QSGDCompressor):
         return QSGDCodec(compressor, numel, shape)
+    if isinstance(compressor, TopKSparsificationCompressor):
+        return TopKCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)

@@ -438,8 +438,9 @@ class ResidualCompressor(object):
 
 
 # ---- exported for `from compressors import *` in the reference's main.py ----------------
-# Not on the accelerated path: plain tensor ops, kept only so
-# that main.py's `quantizer_choices` table resolves.
+# SignSGD is not on the accelerated path: plain tensor ops, kept only so that main.py's
+# `quantizer_choices` table resolves.  TopK runs on the HIP kernels for device tensors (libgq_topk.so; the quantizers ship it
+# on a sparse wire, gq_amd.codecs.TopKCodec) and keeps the reference's torch expression for CPU tensors.
 
 class SignSGDCompressor(object):
     """sign(v) (signsgd_compressor.py:4-12)."""
@@ -465,6 +466,9 @@ class TopKSparsificationCompressor(object):
         self.k = size // args.cr
 
     def compress(self, vec):
+        if vec.device.type == "cuda":
+            # the top-k kernels (libgq_topk.so, gq_amd.codecs.TopKCodec): the same dense tensor bit for bit
+            return self._device_roundtrip(vec).view(self.users, -1)
         vec = vec.view(self.users, -1)
         keep = torch.zeros_like(vec)
         idx = torch.topk(torch.abs(vec), k=self.k, dim=1)[1]
@@ -473,6 +477,19 @@ class TopKSparsificationCompressor(object):
 
     def decompress(self, signature):
         return signature.view(self.shape)
+
+    def _device_roundtrip(self, vec):
+        from .codecs import TopKCodec      # (codecs imports this module)
+        if vec.dtype != torch.float32:
+            raise TypeError("TopKSparsificationCompressor: the device kernels take float32 tensors, got %s" % (vec.dtype,))
+        n = vec.numel()
+        if self.k > n:
+            raise RuntimeError("TopKSparsificationCompressor: k = %d is larger than the tensor (%d elements)" % (self.k, n))
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = TopKCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0)
 
 
 class MaureySparsification(object):

@@ -596,3 +596,91 @@ def qsgd_decode_sum(norm, signs, levels, d, n_bit, out, R=1):
                                   ctypes.c_int(R), ctypes.c_int64(Mb), ctypes.c_int(d), ctypes.c_int(n_bit),
                                   _dev_ptr(out, torch.float32, "out"), _stream())
     _check(rc, "gq_qsgd_decode_sum")
+
+
+# ---- top-k sparsification: libgq_topk.so (include/gq_topk.h) ----------------------------------------------------------
+TOPK_LIB_PATH = os.environ.get("GQ_TOPK_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_topk.so")
+TOPK_ABI_VERSION = 1
+TOPK_EXPORTS = ["gq_topk_abi_version", "gq_topk_last_error", "gq_topk_compress_batched", "gq_topk_decode_sum_batched"]
+TOPK_CHUNK = 4096           # GQ_TOPK_CHUNK: elements per item
+TOPK_HIST_BINS = 2048       # GQ_TOPK_HIST_BINS: histogram words per tensor
+
+_topk_lib = None
+
+
+def topk_lib():
+    """Load libgq_topk.so; fail loudly if it was not built (as lib())."""
+    global _topk_lib
+    if _topk_lib is None:
+        if not os.path.exists(TOPK_LIB_PATH):
+            raise GQNativeError("libgq_topk.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                "(there is no CPU fallback)" % TOPK_LIB_PATH)
+        L = ctypes.CDLL(TOPK_LIB_PATH)
+        L.gq_topk_last_error.restype = ctypes.c_char_p
+        L.gq_topk_abi_version.restype = ctypes.c_int
+        for name in TOPK_EXPORTS:
+            getattr(L, name)
+        if L.gq_topk_abi_version() != TOPK_ABI_VERSION:
+            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
+                                % (TOPK_LIB_PATH, L.gq_topk_abi_version(), TOPK_ABI_VERSION))
+        _topk_lib = L
+    return _topk_lib
+
+
+def _check_topk(rc, what):
+    CALLS[0] += 1
+    if rc != 0:
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, topk_lib().gq_topk_last_error().decode()))
+
+
+class _TopKBatchStruct(ctypes.Structure):     # gq_topk_batch (include/gq_topk.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("hist", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TopKBatch(object):
+    """The multi-tensor top-k launches: gq_topk_compress_batched (select + compact, + the dense decoded tensors and the residual)
+    and gq_topk_decode_sum_batched.  hist (int32 [nseg * TOPK_HIST_BINS], zero), state (int32 [nseg * 4]) and counts
+    (int32 [nitems * 2]) are the caller's scratch; the compress leaves hist zero again."""
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, hist=None, state=None, counts=None):
+        self.L = topk_lib()
+        self.keep = (seg_table, item_seg, hist, state, counts)
+        ptr = lambda t, name: _dev_ptr(t, torch.int32, name).value if t is not None else None
+        self.s = _TopKBatchStruct(ctypes.sizeof(_TopKBatchStruct), int(nseg), int(nitems), _dev_ptr(seg_table, torch.int64, "seg_table").value,
+                                  _dev_ptr(item_seg, torch.int32, "item_seg").value, ptr(hist, "hist"), ptr(state, "state"),
+                                  ptr(counts, "counts"), None, 0, 0)
+        self.ref = ctypes.byref(self.s)
+
+    def set_table(self, seg_table):
+        """As HSQBatch.set_table."""
+        self.keep_table = seg_table
+        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
+
+    def set_dense(self, dense_table, ndense):
+        """As QSGDBatch.set_dense: the compress launch also copies the uncompressed tensors into the wire."""
+        self.keep_dense = dense_table
+        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
+        self.s.ndense = int(ndense) if dense_table is not None else 0
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
+        return TopKBatch(seg_table, item_seg, nseg, nitems)
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
+        launches (seg_table[:, 7] = error buffers; needs out)."""
+        rc = self.L.gq_topk_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
+                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check_topk(rc, "gq_topk_compress_batched")
+
+    def decode(self, gathered, R, out, plain=False):
+        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
+        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
+        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
+        rc = self.L.gq_topk_decode_sum_batched(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride),
+                                               ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
+                                               _stream())
+        _check_topk(rc, "gq_topk_decode_sum_batched")

@@ -30,7 +30,7 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import IdenticalCompressor, _next_seed, shared_seeds
+from .compressors import IdenticalCompressor, TopKSparsificationCompressor, _next_seed, shared_seeds
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
 # addresses as one bytes key and the "all plain f32" flag in one pass; `.data =` for all parameters in another.  A step
@@ -46,7 +46,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedHSQ, BatchedQSGD, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, _BatchedBase, _DATA_PTR,
+    BatchedHSQ, BatchedQSGD, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, TopKCodec, _BatchedBase, _DATA_PTR,
     _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     wire_levels_mode)
 
@@ -149,7 +149,7 @@ class PSQuantizer(object):
         self.use_graphs = bool(int(os.environ.get("GQ_GRAPH", "1"))) if g is None else bool(g)      # (see below: gq_graph)
         self._fuse_steps = type(self) is PSQuantizer and os.environ.get("GQ_FUSE_STEP", "1") != "0"   # (see below: _step_graphs)
         BatchedQSGD.place_lone_buckets(self.codecs)
-        for cls in (BatchedHSQ, BatchedQSGD):
+        for cls in (BatchedHSQ, BatchedQSGD, BatchedTopK):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -1098,6 +1098,15 @@ class PSQuantizer(object):
 # --------------------------------------------------------------------------------------
 # Ring quantizer (the reference's other --mode; sequential by construction)
 # --------------------------------------------------------------------------------------
+def _ring_codec_factory(compressor, numel, shape, packed6=False):
+    """The ring's hops carry decompress(compress(running sum)) as the reference computes it: a top-k tensor travels as its
+    DECODED dense f32 (GenericCodec, the compressor's own compress -- the top-k kernels on a device tensor), so the signed zeros
+    and NaNs of the unkept entries reach the next hop as they do in ring_quantizer.py.  Every other compressor: the PS codecs."""
+    if isinstance(compressor, TopKSparsificationCompressor):
+        return GenericCodec(compressor, numel, shape)
+    return default_codec_factory(compressor, numel, shape, packed6)
+
+
 class RingQuantizer(PSQuantizer):
     """quantizers/ring_quantizer.py:7-49: user k adds user k-1's decoded running sum to its own
     gradient and re-compresses; the result is the LAST user's decode (a sum, not a mean).
@@ -1114,7 +1123,7 @@ class RingQuantizer(PSQuantizer):
         two_phase = args.two_phase
         args.two_phase = False           # ring_quantizer.py has no second phase and no server residual
         try:
-            super().__init__(Compressor, parameters, args, process_group, codec_factory)
+            super().__init__(Compressor, parameters, args, process_group, codec_factory or _ring_codec_factory)
         finally:
             args.two_phase = two_phase
         self.two_phase = False

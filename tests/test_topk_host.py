@@ -1,0 +1,112 @@
+"""Top-k sparsification, host side (no GPU): codec routing, the sparse wire's size, the CPU torch path."""
+import json
+import os
+from argparse import Namespace
+
+import pytest
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden")
+
+
+def make_args(**kw):
+    base = dict(c_dim=16, k_bit=8, n_bit=6, no_cuda=False, random=0, ef=False, two_phase=False, scale="exp",
+                num_users=1, mode="ps", cr=256)
+    base.update(kw)
+    return Namespace(**base)
+
+
+def _resnet50_params():
+    with open(os.path.join(GOLDEN, "resnet50_cifar_shapes.json")) as f:
+        shapes = json.load(f)["parameter_shapes"]
+    return [torch.nn.Parameter(torch.zeros(s)) for s in shapes]
+
+
+def test_topk_routes_to_the_sparse_codec():
+    from gq_amd.codecs import BatchedTopK, DenseCodec, TopKCodec, default_codec_factory
+    from gq_amd.compressors import IdenticalCompressor, TopKSparsificationCompressor
+    c = TopKSparsificationCompressor(5000, torch.Size([5000]), make_args(cr=256))
+    cd = default_codec_factory(c, 5000, torch.Size([5000]))
+    assert type(cd) is TopKCodec and cd.k == 5000 // 256 and cd.nbytes == 8 * cd.k
+    assert BatchedTopK.eligible(cd)
+    assert type(default_codec_factory(IdenticalCompressor(), 10, torch.Size([10]))) is DenseCodec
+
+
+def test_quantizer_groups_every_topk_tensor():
+    from gq_amd.codecs import BatchedTopK, TopKCodec
+    from gq_amd.compressors import TopKSparsificationCompressor
+    from gq_amd.quantizers import PSQuantizer
+    params = _resnet50_params()
+    q = PSQuantizer(TopKSparsificationCompressor, params, make_args())
+    topk = [i for i, c in enumerate(q.codecs) if type(c) is TopKCodec]
+    assert len(topk) == 76
+    assert [g[0] for g in q._groups] == [BatchedTopK] and sorted(q._groups[0][1]) == topk
+
+
+def test_resnet50_wire_is_sparse():
+    """823,968 B per user at cr 256: 734,320 B of (index, value) sections + 89,640 B of dense tensors, rounded up to 16 B
+    (the decoded dense f32 of every tensor was 94,083,376 B)."""
+    from gq_amd.codecs import TopKCodec
+    from gq_amd.compressors import TopKSparsificationCompressor
+    from gq_amd.quantizers import PSQuantizer
+    q = PSQuantizer(TopKSparsificationCompressor, _resnet50_params(), make_args(cr=256))
+    sparse = sum(c.nbytes for c in q.codecs if type(c) is TopKCodec)
+    assert sparse == 734_320
+    assert q.dense_bytes == 89_640
+    assert q.wire_bytes_per_user() == 823_968
+    # every section starts 16-byte aligned and holds exactly k indices and k values
+    for c, off in zip(q.codecs, q.offsets):
+        if type(c) is TopKCodec:
+            assert off % 16 == 0 and c.nbytes == 8 * (c.numel // 256)
+
+
+def test_ring_keeps_the_reference_hop():
+    """The ring's hops carry the decoded dense tensor (the reference's signed zeros / NaNs reach the next user)."""
+    from gq_amd.codecs import GenericCodec
+    from gq_amd.compressors import TopKSparsificationCompressor
+    from gq_amd.quantizers import RingQuantizer
+    q = RingQuantizer(TopKSparsificationCompressor, _resnet50_params(), make_args(mode="ring"))
+    assert all(type(c) is GenericCodec for c in q.codecs if c.numel > 1000)
+
+
+def test_cpu_tensors_keep_the_torch_expression():
+    from gq_amd.compressors import TopKSparsificationCompressor
+    torch.manual_seed(0)
+    n, cr = 4096, 16
+    c = TopKSparsificationCompressor(n, torch.Size([n]), make_args(cr=cr))
+    v = torch.randn(n)
+    v[:7] = -0.0
+    got = c.decompress(c.compress(v))
+    keep = torch.zeros(1, n)
+    keep.scatter_(1, torch.topk(v.abs().view(1, -1), k=n // cr, dim=1)[1], 1)
+    want = (v.view(1, -1) * keep).view(n)
+    assert got.device.type == "cpu"
+    assert torch.equal(got.view(torch.int32), want.view(torch.int32))      # signed zeros included
+
+
+def test_topk_library_is_built_and_exports_its_abi():
+    import ctypes
+    import subprocess
+    from gq_amd import native
+    if not os.path.exists(native.TOPK_LIB_PATH):
+        pytest.fail("libgq_topk.so is not built (build() makes it)")
+    L = native.topk_lib()
+    assert L.gq_topk_abi_version() == native.TOPK_ABI_VERSION
+    out = subprocess.run(["nm", "-D", "--defined-only", native.TOPK_LIB_PATH], capture_output=True, text=True).stdout
+    exported = sorted(ln.split()[-1] for ln in out.splitlines() if " T " in ln and ln.split()[-1].startswith("gq"))
+    assert exported == sorted(native.TOPK_EXPORTS)
+    hdr = open(os.path.join(os.path.dirname(HERE), "include", "gq_topk.h")).read()
+    for name in native.TOPK_EXPORTS:
+        assert name + "(" in hdr
+    assert ctypes.sizeof(native._TopKBatchStruct) == 72      # (topk.hip static_asserts the same size)
+
+
+def test_topk_calls_fail_loudly_without_a_gpu_tensor():
+    from gq_amd import native
+    from gq_amd.codecs import TopKCodec
+    from gq_amd.compressors import TopKSparsificationCompressor
+    c = TopKSparsificationCompressor(2048, torch.Size([2048]), make_args(cr=8))
+    cd = TopKCodec(c, 2048, torch.Size([2048]))
+    with pytest.raises((native.GQNativeError, RuntimeError)):
+        cd.encode_into(torch.randn(2048), torch.zeros(cd.nbytes, dtype=torch.uint8), 0, 0)
