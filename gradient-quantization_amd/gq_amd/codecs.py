@@ -517,15 +517,30 @@ class _BatchedBase(object):
                 _kernel_copy(self._dev[self._table_words:self._dense_at], self._acc_init)
         self._batch.set_table(self._dev[:self._table_words])
 
-    def _graph_tables_abort(self):
+    def graph_tables_abort(self):
         """A launch failed between _graph_tables and _graph_tables_done (an invalidated capture, a launch error): the callers
         fall back to eager launches, which must not read their pointers from the graph's header.  The descriptor goes back to
         the shared device header and the next eager encode re-validates and re-sends it (no reset kernel: the stream may be
-        in a broken capture; `_acc_clean = False` makes the next replay clean the accumulators first)."""
+        in a broken capture; `_acc_clean = False` makes the next replay clean the accumulators first).  A level launch left
+        for the capture's decode (encode(..., skip_levels=True)) is dropped."""
         self._batch.set_table(self._dev[:self._table_words])
         self._batch.set_dense(self.dense_table_dev(), self.ndense)
         self._last_ptrs = self._last_eptrs = self._last_dptrs = None
         self._acc_clean = False
+        self._pending_levels = None
+
+    _pending_levels = None      # (BatchedHSQ.encode(..., skip_levels=True): the launch levels_decode still has to make)
+
+    def after_replay(self, decoded, table_replaced):
+        """What a replayed graph leaves behind.  decoded: it decoded into the next output buffer.  table_replaced: it read its
+        own table, not the last upload's pointers in the device header -- the next eager encode re-sends them."""
+        if decoded:
+            self._out_turn ^= 1
+        if table_replaced:
+            self._last_ptrs = None
+
+    def set_out_turn(self, turn):      # (a capture re-issues an eager call's launches, then puts the turn back)
+        self._out_turn = turn
 
     def ensure_clean(self):
         if self._resets and not self._acc_clean:
@@ -800,7 +815,7 @@ class BatchedHSQ(_BatchedBase):
                 self._batch.levels(wire_user, mode, seed, r_flat, write_error=errs is not None)
         except BaseException:
             if graph_header is not None:
-                self._graph_tables_abort()
+                self.graph_tables_abort()
             raise
         if graph_header is not None and not skip_levels:
             self._graph_tables_done(defer_reset)
@@ -826,7 +841,7 @@ class BatchedHSQ(_BatchedBase):
         try:
             self._batch.levels_decode(wire_user, mode, seed, r_flat, write_error, out, plain=plain, tail=tail)
         except BaseException:
-            self._graph_tables_abort()
+            self.graph_tables_abort()
             raise
         self._batch.set_table(self._dev[:self._table_words])      # (the reset itself rode in the launch: tail.reset)
         return views
@@ -964,7 +979,7 @@ class BatchedQSGD(_BatchedBase):
             self._batch.compress(wire_user, mode, seed, ef_scale if errs is not None else None)
         except BaseException:
             if graph_header is not None:
-                self._graph_tables_abort()
+                self.graph_tables_abort()
             raise
         if graph_header is not None:
             self._graph_tables_done(defer_reset)
@@ -1043,7 +1058,7 @@ class BatchedTopK(_BatchedBase):
             self._batch.compress(wire_user, out, ef)
         except BaseException:
             if graph_header is not None:
-                self._graph_tables_abort()
+                self.graph_tables_abort()
             raise
         if graph_header is not None:
             self._graph_tables_done(defer_reset)

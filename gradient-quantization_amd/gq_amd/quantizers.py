@@ -26,6 +26,7 @@ the only objects that touch device memory; the product codecs call the HIP libra
 import math
 import operator
 import os
+import warnings
 
 import torch
 
@@ -41,7 +42,6 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
     try:
         from . import _gq_host as _HOST
     except ImportError as _e:      # not built: the Python walks below do the same, slower; say so once
-        import warnings
         warnings.warn("gq_amd: the host helper _gq_host.so is not built (%s); run gradient-quantization_amd/build.py" % (_e,))
 
 
@@ -69,14 +69,15 @@ def _dist_world(process_group):
 
 
 class _capturing(object):
-    """`with _capturing(graph): ...` = torch.cuda.graph(graph, capture_error_mode="thread_local") with the cyclic garbage collector
-    held off for the duration.  torch.cuda.graph collects once BEFORE a capture begins because freeing device objects inside one is
-    not allowed; a collection that the interpreter starts by itself in the middle of the capture (an allocation count crossing its
-    threshold) can still finalize an older quantizer's graphs, plans and private memory pools there -- round 6 saw the process abort
-    in exactly that spot.  (thread_local: other threads -- RCCL's watchdog -- may call into HIP meanwhile.)"""
+    """`with _capturing(direct) as graph: ...` = torch.cuda.graph(_new_graph(direct), capture_error_mode="thread_local") with the
+    cyclic garbage collector held off for the duration.  torch.cuda.graph collects once BEFORE a capture begins because freeing device
+    objects inside one is not allowed; a collection that the interpreter starts by itself in the middle of the capture (an allocation
+    count crossing its threshold) can still finalize an older quantizer's graphs, plans and private memory pools there -- round 6 saw
+    the process abort in exactly that spot.  (thread_local: other threads -- RCCL's watchdog -- may call into HIP meanwhile.)"""
 
-    def __init__(self, graph):
-        self._ctx = torch.cuda.graph(graph, capture_error_mode="thread_local")
+    def __init__(self, direct):
+        self.graph = _new_graph(direct)
+        self._ctx = torch.cuda.graph(self.graph, capture_error_mode="thread_local")
         self._gc = False
 
     def __enter__(self):
@@ -84,11 +85,12 @@ class _capturing(object):
         self._gc = gc.isenabled()
         gc.disable()
         try:
-            return self._ctx.__enter__()
+            self._ctx.__enter__()
         except BaseException:
             if self._gc:
                 gc.enable()
             raise
+        return self.graph
 
     def __exit__(self, *exc):
         import gc
@@ -97,6 +99,69 @@ class _capturing(object):
         finally:
             if self._gc:
                 gc.enable()
+
+
+def _new_graph(direct):
+    """The graph object of a capture.  direct ($GQ_DIRECT_REPLAY, default 1): kept as a graph (keep_graph) so that _replayable
+    can read its kernel nodes back."""
+    if direct:
+        try:
+            return torch.cuda.CUDAGraph(keep_graph=True)
+        except TypeError:      # (a torch without keep_graph: the graph's own replay)
+            pass
+    return torch.cuda.CUDAGraph()
+
+
+def _replayable(graph, direct):
+    """What an entry's replay() runs: the captured kernel nodes as PLAIN launches on the current stream (native.LaunchPlan --
+    a replayed graph pays 4-5 us of boundary between two replays that launches on a stream do not: 62.4 against 57.6 us per
+    two-kernel ResNet-50 step, tools/direct_vs_graph.py), or the graph itself where it is not one chain of kernel launches
+    (a torch without raw graph access) or $GQ_DIRECT_REPLAY=0."""
+    if direct and hasattr(graph, "raw_cuda_graph"):
+        try:
+            return native.LaunchPlan(graph)
+        except Exception:
+            pass
+    try:
+        graph.instantiate()      # (keep_graph: not instantiated by capture_end)
+    except Exception:
+        pass
+    return graph
+
+
+class _GraphCache(dict):
+    """gq_graph's cache: key -> [sightings, replay or None, keep-alive, ...].  A few address sets recur (the allocator hands
+    the same blocks out again); captured graphs are never evicted -- once max_captured of them are tied to gradient addresses,
+    new address-tied keys keep their eager launches (sight() -> None) instead of displacing one another capture by capture --
+    and among the entries that only count sightings the oldest goes first.  Address-free keys (one graph serves every address
+    set) are neither refused nor counted."""
+
+    def __init__(self, max_captured=48, max_counting=64):
+        dict.__init__(self)
+        self.max_captured, self.max_counting = max_captured, max_counting
+        self.address_free = set()
+
+    def sight(self, key, address_free=False):
+        """The entry of `key` with this sighting counted, or None (a new address-tied key and the cap reached)."""
+        ent = self.get(key)
+        if ent is None:
+            if not address_free and self.captured()[0] >= self.max_captured:
+                return None
+            counting = [k for k, e in self.items() if e[1] is None]
+            if len(counting) >= self.max_counting:
+                del self[counting[0]]
+                self.address_free.discard(counting[0])
+            ent = self[key] = [0, None, None]
+            if address_free:
+                self.address_free.add(key)
+        ent[0] += 1
+        return ent
+
+    def captured(self):
+        """(address-tied, address-free) entries that hold a graph."""
+        keys = [k for k, e in self.items() if e[1] is not None]
+        free = sum(1 for k in keys if k in self.address_free)
+        return len(keys) - free, free
 
 
 class PSQuantizer(object):
@@ -148,6 +213,9 @@ class PSQuantizer(object):
         g = getattr(args, "gq_graph", None)
         self.use_graphs = bool(int(os.environ.get("GQ_GRAPH", "1"))) if g is None else bool(g)      # (see below: gq_graph)
         self._fuse_steps = type(self) is PSQuantizer and os.environ.get("GQ_FUSE_STEP", "1") != "0"   # (see below: _step_graphs)
+        self._direct = os.environ.get("GQ_DIRECT_REPLAY", "1") != "0"      # (see _replayable)
+        self._step_tail = os.environ.get("GQ_STEP_TAIL", "1") != "0"       # (see _decode_all)
+        self._fuse_levels = os.environ.get("GQ_FUSE_LEVELS", "1") != "0"   # (see _can_fuse_levels)
         BatchedQSGD.place_lone_buckets(self.codecs)
         for cls in (BatchedHSQ, BatchedQSGD, BatchedTopK):
             keyed = {}
@@ -157,8 +225,7 @@ class PSQuantizer(object):
             for key in sorted(keyed):
                 idx = keyed[key]
                 if len(idx) >= 2 and not getattr(args, "gq_no_batch", False):
-                    for part in self._overlap_chunks(idx, args):
-                        self._groups.append([cls, part, None])
+                    self._groups.append([cls, idx, None])
         self.batch_idx = [i for g in self._groups for i in g[1]]
         self._pick_dense = operator.itemgetter(*self.dense_idx) if len(self.dense_idx) >= 2 else None
         self._pick_group = {}
@@ -171,15 +238,14 @@ class PSQuantizer(object):
         # step whatever the gradients are (the reference draws per call: probabilistic_scalar_compressor.py:22-26).
         self._rng_state = None
         self._ticket = None          # gq_hsq_levels_decode_batched's last-workgroup counter (one device word, zero between launches)
-        self._rec_graphs = {}        # (slot, user, scale, gradient addresses) -> [sightings, graph or None, keep-alive]
-        self._apply_graphs = {}      # (users recorded, wire, output-buffer turns) -> [sightings, graph or None, decoded list]
+        self._rec_graphs = _GraphCache(self.MAX_ADDRESS_GRAPHS)    # (slot, user, wire, gradient addresses) -> [sightings, graph or None, headers]
+        self._apply_graphs = _GraphCache()   # (users recorded, wire, output-buffer turns) -> [sightings, graph or None, decoded list]
         # One rank, one user per step (args.num_users == 1, no process group): record() is always followed by the apply() of
         # exactly that payload, so the two replay as ONE graph from record() -- compress and decode-mean launches back to
         # back, one graph launch less per step (5 us of ~70, tools/graph_pieces.py) -- and apply() only rebinds the gradients.
         # $GQ_FUSE_STEP=0 keeps the two graphs.
-        self._step_graphs = {}       # (record key, apply key) -> [sightings, graph or None, decoded list]
+        self._step_graphs = _GraphCache()    # (record key, apply key) -> [sightings, graph or None, decoded list]
         self._fused = None           # the decoded list of a step whose record() has already replayed its apply()
-        self._side_stream = None     # the second branch of a chunked step's graph (_overlap_fractions)
         self._phase2_base = None     # the seed base all ranks share for the replicated second phase (_second_phase_base)
         self._fast_ok = None         # _replay_known_step applies to this quantizer (None: not decided yet)
         self._apply_key_memo, self._dense_gen = {}, 0
@@ -220,55 +286,6 @@ class PSQuantizer(object):
                 if c not in self.cuts:
                     self.cuts.append(c)
         self.cuts.sort()
-
-    # ---- overlap: the tensor list in chunks, a chunk's level / decode launch under the next chunk's encode ----------------
-    OVERLAP_MIN_ELEMENTS = 4 << 20      # below this a step is launch-bound: one group, as before
-
-    def _overlap_fractions(self, args):
-        """The shares of the compressed elements that the chunks of a tensor group take, or None (one group: the default).
-        args.gq_overlap / $GQ_OVERLAP: the shares, e.g. "0.58,0.42"; "0" (default): off.
-        EXPERIMENT, measured and not the default (profiles/r06_overlap_ab.txt): the compress of a tensor list is VALU-bound, its
-        level / decode launch HBM-bound, and a tensor's levels need only THAT tensor's (lb, ub) (ps_quantizer.py:33-44 treats
-        the tensors as independent), so with the list in chunks, chunk i's level + decode launch can run on a second stream -- a
-        parallel branch of the step's graph -- while chunk i + 1 is encoded.  The kernels do run side by side, but every extra
-        encode launch costs ~10 us of fixed time and every edge between two hardware queues 5-9 us: 94 against 68.5 us per
-        ResNet-50 step.  Only where a whole step replays as one graph (one rank, one user per step, no second phase)."""
-        spec = getattr(args, "gq_overlap", None)
-        spec = os.environ.get("GQ_OVERLAP", "0") if spec is None else str(spec)
-        if spec in ("0", "off", "") or not self._fuse_steps or not self.use_graphs or self.two_phase:
-            return None
-        if int(args.num_users) != 1 or _dist_world(self.process_group)[0] != 1:
-            return None
-        fr = [float(x) for x in spec.split(",")]
-        if len(fr) < 2 or min(fr) <= 0:
-            return None
-        return [f / sum(fr) for f in fr]
-
-    def _overlap_chunks(self, idx, args):
-        """`idx` (parameter indices of one tensor group, in wire order) cut at tensor boundaries into runs whose element counts
-        are nearest to the configured shares; every run keeps at least two tensors."""
-        fr = self._overlap_fractions(args)
-        sizes = [self.codecs[i].numel for i in idx]
-        total = sum(sizes)
-        if fr is None or total < self.OVERLAP_MIN_ELEMENTS or len(idx) < 2 * len(fr):
-            return [idx]
-        cum, acc = [], 0
-        for n in sizes:
-            acc += n
-            cum.append(acc)
-        cuts, target = [], 0.0
-        for f in fr[:-1]:
-            target += f * total
-            lo = (cuts[-1] if cuts else 0) + 2
-            cand = [k for k in range(lo, len(idx) - 1) if len(idx) - k >= 2]
-            if not cand:
-                return [idx]
-            cuts.append(min(cand, key=lambda k: abs(cum[k - 1] - target)))
-        parts, a = [], 0
-        for c in cuts + [len(idx)]:
-            parts.append(idx[a:c])
-            a = c
-        return parts if all(len(p) >= 2 for p in parts) else [idx]
 
     # ---- buffers -------------------------------------------------------------------------
     def _ensure_wire(self, device, slots):
@@ -368,7 +385,7 @@ class PSQuantizer(object):
         replay it without building the list of gradient objects (the C++ helper hands back the addresses as one bytes key).  One
         rank, one user per step, no error feedback (its key holds the residuals' addresses too); everything else takes record()'s
         long way, which ends in the same replays.  -> True when the step has been replayed."""
-        if (self._fast_ok is None or not self._fast_ok) and not self._fast_check():
+        if not self._fast_ok and not self._fast_check():
             return False
         if self._fast_misses >= 8:      # a caller whose gradients move every step (a training loop): look again every 32nd record only
             self._fast_misses += 1
@@ -389,34 +406,56 @@ class PSQuantizer(object):
             self._fast_misses += 1
             return False
         self._fast_misses = 0
-        for g in self._groups:
-            g[2].ensure_clean()
-        fent[1].replay()
-        for g in self._groups:
-            g[2]._last_ptrs = None
-            g[2]._out_turn ^= 1
-        if len(self.dense_idx) >= 2:
-            self._dense_turn ^= 1
-        self._fused = fent[2]
-        self.recorded = 1
-        self.record_paths["whole_step"] += 1
+        self._replayed(fent, "whole_step", True, True, True)
         return True
 
     def _fast_check(self):
         """Can _replay_known_step ever apply to this quantizer?  (False: decided for good; None: not yet -- the groups are built by
         the first record.)"""
-        if self._fast_ok is False:
-            return False
         if (_HOST is None or not hasattr(_HOST, "scan_key") or not self.use_graphs or not self._fuse_steps or self.error_feedback
                 or self.two_phase or self._draw_total or self.capacity != 1 or not self._groups):
             self._fast_ok = False
             return False
-        if self._wire is None or self._plan is None or self._plan[2] or _dist_world(self.process_group)[0] != 1:
+        if self._wire is None or not self._whole_step_ok(_dist_world(self.process_group)[0], 0) or not self._graphable():
             return False      # (not yet; a process group may still be initialised later: checked again by the long way's own conditions)
-        if not all(g[2] is not None and g[2].ready and g[2].graphable() for g in self._groups):
-            return False
         self._fast_ok = True
         return True
+
+    def _graphable(self):
+        return all(g[2] is not None and g[2].ready and g[2].graphable() for g in self._groups)
+
+    def _whole_step_ok(self, world, slot):
+        """The record of user slot `slot` is followed by the apply() of exactly its payload (one rank, one user per step, no
+        second phase) and everything decodes through multi-tensor launches (the plan): the two can replay as ONE graph."""
+        return (self._fuse_steps and world == 1 and slot == 0 and self.capacity == 1 and not self.two_phase
+                and self._plan is not None and not self._plan[2])
+
+    def _replayed(self, ent, path, clean, table_replaced, decoded):
+        """Replay a cache entry and leave behind what its launches did.  path: the record_paths key (None: an apply).  clean: reset
+        the accumulators an eager call left used first.  table_replaced: the graph read its own copy of the header, not the shared
+        one that an address-free graph's upload has just written.  decoded: it ends in the aggregate's decode-mean (output turns).
+
+            route (record_paths key)                    clean   table_replaced  decoded     (_fused set)
+            known step, short way (whole_step)          yes     yes             yes         yes
+            address-tied whole step (whole_step)        yes     yes             yes         yes
+            address-tied record (graph)                 yes     yes             no          no
+            address-free whole step (..._any_address)   no      no              yes         yes
+            address-free record (graph_any_address)     no      no              no          no
+            apply                                       two-phase only  yes     yes (groups: without two-phase only)"""
+        if clean:
+            for g in self._groups:
+                g[2].ensure_clean()
+        ent[1].replay()
+        turn = decoded and not self.two_phase
+        for g in self._groups:
+            g[2].after_replay(turn, table_replaced)
+        if decoded and len(self.dense_idx) >= 2:
+            self._dense_turn ^= 1
+        if path is not None:
+            if decoded:
+                self._fused = ent[2]
+            self.recorded += 1
+            self.record_paths[path] += 1
 
     def record(self, user, epoch):
         if self._fast_ok is not False and self._replay_known_step(user):
@@ -429,87 +468,46 @@ class PSQuantizer(object):
         wire = self._ensure_wire(dev, slot + 1)[slot]
         world, rank = _dist_world(self.process_group)
         salt = ((rank * 1000003 + user) * 0x9E3779B1) & (2 ** 62 - 1)
-        skip = set()
         draws = self._draws(dev)
         # gq_graph: a record whose gradient addresses were seen before replays its device work as ONE graph launch
         graph_key = None
-        if (self.use_graphs and dev.type == "cuda" and not self._draw_total and slot < self.TWO_PHASE_RNG_SLOT
-                and all(g[2] is not None and g[2].ready and g[2].graphable() for g in self._groups)
+        if (self.use_graphs and dev.type == "cuda" and not self._draw_total and slot < self.TWO_PHASE_RNG_SLOT and self._graphable()
                 and not torch.cuda.is_current_stream_capturing()):      # (inside a caller's own capture the launches are simply recorded)
             graph_key = (slot, user, self._wire.data_ptr(), scan[1] if scan is not None else tuple(map(_DATA_PTR, all_grads)))
-            if self.error_feedback:     # the residual buffers' addresses are in the header too (a per-tensor step replaces them)
-                graph_key += (scale, tuple(p.error[user].data_ptr() for p in self.parameters))
-            ent = self._rec_graphs.get(graph_key)
-            plain_f32 = ent is not None and ent[1] is not None and (
-                scan[2] if scan is not None else (all(map(_IS_CONTIGUOUS, all_grads)) and set(map(_DTYPE_OF, all_grads)) == _F32_ONLY))
-            step_key = None
-            if (plain_f32 and self._fuse_steps and world == 1 and slot == 0 and self.capacity == 1 and not self.two_phase
-                    and self._plan is not None and not self._plan[2]):      # (the plan: everything decodes through multi-tensor launches)
-                step_key = (graph_key, self._apply_key(self._wire[:1]))
-                fent = self._step_graphs.get(step_key)
-                if fent is not None and fent[1] is not None:      # compress + decode-mean of this step in one launch
-                    for g in self._groups:
-                        g[2].ensure_clean()
-                    fent[1].replay()
-                    for g in self._groups:
-                        g[2]._last_ptrs = None
-                        g[2]._out_turn ^= 1
-                    if len(self.dense_idx) >= 2:
-                        self._dense_turn ^= 1
-                    self._fused = fent[2]
-                    self.recorded += 1
-                    self.record_paths["whole_step"] += 1
-                    return
-            if plain_f32:
-                for g in self._groups:
-                    g[2].ensure_clean()
-                ent[1].replay()
-                self.record_paths["graph"] += 1
-                for g in self._groups:
-                    g[2]._last_ptrs = None      # the device header now holds this graph's table: the next eager call re-sends its own
-                self.recorded += 1
-                if step_key is not None:
-                    fent = self._graph_entry(self._step_graphs, step_key)
-                    if fent is not None and fent[0] >= 2 and fent[1] is None:
-                        self._capture_step(fent, ent[2], all_grads, wire, slot, user, salt, scale, dev)
-                return
             # No graph for THESE gradient addresses (a training loop whose backward allocates the gradients anew sees a new set
             # nearly every step: round 6 measured 98 sets in 150 iterations of driver.one_iter, 48 captures that were hardly
             # ever replayed and eager launches from then on).  The ADDRESS-FREE graph: the same launches reading the shared
             # device header, which is refreshed -- pointers, accumulator resets -- by one pinned copy in front of the replay,
             # exactly what an eager step sends.  One graph per (slot, user) serves every address set.
-            generic_key = ("any", slot, user, self._wire.data_ptr()) + ((scale,) if self.error_feedback else ())
-            gent = self._rec_graphs.get(generic_key)
-            if (gent is not None and gent[1] is not None
-                    and (scan[2] if scan is not None else (all(map(_IS_CONTIGUOUS, all_grads)) and set(map(_DTYPE_OF, all_grads)) == _F32_ONLY))
-                    and self._upload_headers(all_grads, slot, user)):
-                # an address set that has come back gets a graph of its own (no header copy in front of its replays); the capture
-                # executes nothing, this step still replays the address-free graph
-                ent = self._graph_entry(self._rec_graphs, graph_key, max_captured=self.MAX_ADDRESS_GRAPHS)
-                if ent is not None and ent[0] >= 2 and ent[1] is None:
-                    self._capture_record(ent, all_grads, wire, slot, user, salt, scale, dev)
-                gstep = None
-                if (self._fuse_steps and world == 1 and slot == 0 and self.capacity == 1 and not self.two_phase
-                        and self._plan is not None and not self._plan[2]):
-                    gstep = (generic_key, self._apply_key(self._wire[:1]))
-                    fent = self._step_graphs.get(gstep)
-                    if fent is not None and fent[1] is not None:
-                        fent[1].replay()
-                        for g in self._groups:
-                            g[2]._out_turn ^= 1
-                        if len(self.dense_idx) >= 2:
-                            self._dense_turn ^= 1
-                        self._fused = fent[2]
-                        self.recorded += 1
-                        self.record_paths["whole_step_any_address"] += 1
-                        return
-                gent[1].replay()
-                self.recorded += 1
-                self.record_paths["graph_any_address"] += 1
-                if gstep is not None:
-                    fent = self._graph_entry(self._step_graphs, gstep)
+            generic_key = ("any", slot, user, self._wire.data_ptr())
+            if self.error_feedback:     # the residual buffers' addresses are in the header too (a per-tensor step replaces them)
+                graph_key += (scale, tuple(p.error[user].data_ptr() for p in self.parameters))
+                generic_key += (scale,)
+            plain_f32 = scan[2] if scan is not None else (all(map(_IS_CONTIGUOUS, all_grads)) and set(map(_DTYPE_OF, all_grads)) == _F32_ONLY)
+            ent = self._rec_graphs.get(graph_key) if plain_f32 else None
+            tied = ent is not None and ent[1] is not None
+            if plain_f32 and not tied:
+                ent = self._rec_graphs.get(generic_key)
+                if ent is None or ent[1] is None or not self._upload_headers(all_grads, slot, user):
+                    ent = None
+                else:
+                    # an address set that has come back gets a graph of its own (no header copy in front of its replays); the
+                    # capture executes nothing, this step still replays the address-free graph
+                    own = self._rec_graphs.sight(graph_key)
+                    if own is not None and own[0] >= 2 and own[1] is None:
+                        self._capture_record(own, all_grads, wire, slot, user, salt, scale, dev)
+            if ent is not None:
+                key = graph_key if tied else generic_key
+                step_key = (key, self._apply_key_for(1, self._wire.data_ptr())) if self._whole_step_ok(world, slot) else None
+                fent = self._step_graphs.get(step_key)      # (step_key None: never a key)
+                if fent is not None and fent[1] is not None:      # compress + decode-mean of this step in one launch
+                    self._replayed(fent, "whole_step" if tied else "whole_step_any_address", tied, tied, True)
+                    return
+                self._replayed(ent, "graph" if tied else "graph_any_address", tied, tied, False)
+                if step_key is not None:
+                    fent = self._step_graphs.sight(step_key, address_free=not tied)
                     if fent is not None and fent[0] >= 2 and fent[1] is None:
-                        self._capture_step(fent, None, all_grads, wire, slot, user, salt, scale, dev)
+                        self._capture_step(fent, ent[2], all_grads, wire, slot, user, salt, scale, dev)
                 return
         self.record_paths["eager"] += 1
         skip = self._record_launches(all_grads, wire, slot, user, salt, scale, draws, dev)
@@ -518,11 +516,10 @@ class PSQuantizer(object):
             if graph_key is not None:
                 # the address-free graph first (it serves every later step); a graph of its own for an address set only when
                 # the set has come back (callers whose gradients keep their storage: one copy node less per step)
-                generic_key = ("any", slot, user, self._wire.data_ptr()) + ((scale,) if self.error_feedback else ())
-                gent = self._graph_entry(self._rec_graphs, generic_key, max_captured=1 << 30)
-                if gent is not None and gent[1] is None and gent[0] >= 2 and self._generic_ok():
+                gent = self._rec_graphs.sight(generic_key, address_free=True)
+                if gent[1] is None and gent[0] >= 2 and self._generic_ok():
                     self._capture_record(gent, all_grads, wire, slot, user, salt, scale, dev, generic=True)
-                ent = self._graph_entry(self._rec_graphs, graph_key, max_captured=self.MAX_ADDRESS_GRAPHS)
+                ent = self._rec_graphs.sight(graph_key)
                 if ent is not None and ent[0] >= 2 and ent[1] is None:      # the second sighting: worth a capture
                     self._capture_record(ent, all_grads, wire, slot, user, salt, scale, dev)
             return
@@ -563,13 +560,9 @@ class PSQuantizer(object):
 
     def graph_counts(self):
         """Captured graphs by kind: record / whole step tied to a set of gradient addresses, their address-free forms, apply."""
-        def split(cache, pick):
-            keys = [k for k, e in cache.items() if e[1] is not None]
-            free = sum(1 for k in keys if pick(k)[0] == "any")
-            return len(keys) - free, free
-        rec, rec_any = split(self._rec_graphs, lambda k: k)
-        step, step_any = split(self._step_graphs, lambda k: k[0])
-        return {"record": rec, "record_any_address": rec_any, "apply": sum(1 for e in self._apply_graphs.values() if e[1] is not None),
+        rec, rec_any = self._rec_graphs.captured()
+        step, step_any = self._step_graphs.captured()
+        return {"record": rec, "record_any_address": rec_any, "apply": sum(self._apply_graphs.captured()),
                 "whole_step": step, "whole_step_any_address": step_any}
 
     def _generic_ok(self):
@@ -598,30 +591,26 @@ class PSQuantizer(object):
         obj = grp[2] = cls(self.codecs, self.offsets, idxs, dev, self.capacity, self.user_bytes, dense=dense)
         obj.fma = bool(self.aggregate_fma and cls is BatchedHSQ)
         if dev.type == "cuda":
-            self._ticket_for(dev, 0)      # (allocated and zeroed HERE, eagerly: a first use under stream capture would put it in a graph's pool)
+            self._ticket_for(dev)      # (allocated and zeroed HERE, eagerly: a first use under stream capture would put it in a graph's pool)
         if getattr(obj, "counter", False) and len(self._groups) * self.RNG_SLOTS <= 256:
             obj.rng_pairs = self._rng_pairs_for(dev, self._groups.index(grp))
         return obj
 
-    def _ticket_for(self, dev, gi):
-        """Group gi's last-workgroup counters (gq_step_tail.ticket: zero between launches; one set per group -- the groups of a
-        chunked step run their launches side by side)."""
+    def _ticket_for(self, dev):
+        """The last-workgroup counters of gq_step_tail.ticket (zero between launches)."""
         if self._ticket is None or self._ticket.device != dev:
-            assert not torch.cuda.is_current_stream_capturing(), "the ticket words are made by the first eager record (_make_group)"
-            self._ticket = torch.zeros((max(1, len(self._groups)), native.TICKET_WORDS), dtype=torch.int32, device=dev)
-        return self._ticket[gi]
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the ticket words are made by the first eager record (_make_group), not under stream capture")
+            self._ticket = torch.zeros(native.TICKET_WORDS, dtype=torch.int32, device=dev)
+        return self._ticket
 
     def _record_launches(self, all_grads, wire, slot, user, salt, scale, draws, dev, headers=None, defer_resets=None, fuse_levels=False,
-                         overlap=None, table_current=False):
+                         table_current=False):
         """The multi-tensor launches of a record (+ the dense tensors' copy into the wire) -> the set of parameters served.
         headers (stream capture): one device-resident header per group, see BatchedHSQ.encode.
-        fuse_levels (whole-step capture, _can_fuse_levels): the group's level launch is left to the aggregate's decode.
-        overlap (whole-step capture of a chunked list, a dict): an event is recorded behind every group's compress
-        (overlap["events"][group]) and its accumulators' reset is kept per group (overlap["resets"][group]): _decode_all puts
-        the group's level / decode launch on the side stream behind that event."""
+        fuse_levels (whole-step capture, _can_fuse_levels): the group's level launch is left to the aggregate's decode."""
         skip = set()
-        skip_groups = []
-        for grp in (self._groups if dev.type == "cuda" else []):
+        for gi, grp in enumerate(self._groups if dev.type == "cuda" else []):
             cls, idxs, obj = grp
             if obj is None:
                 obj = self._make_group(grp, dev)
@@ -632,22 +621,14 @@ class PSQuantizer(object):
             # error feedback (ps_quantizer.py:35,39) rides in the same launches: grad += scale*error
             # before the encode, error = grad - decoded after it, both in place
             errs = [self.parameters[i].error[user] for i in idxs] if self.error_feedback else None
-            hdr = headers[len(skip_groups)] if headers is not None else None
-            skip_groups.append(obj)
+            hdr = headers[gi] if headers is not None else None
             dense = list(self._pick_dense(all_grads)) if obj.ndense else None
             kw = {"skip_levels": True} if fuse_levels else {}
-            if table_current:      # (capture of an address-free graph: launches only, the shared device header is current)
-                kw["table_current"] = True
-            mine = [] if overlap is not None else defer_resets
-            if obj.encode(grads, wire, slot, salt, errs, scale, draws=draws, graph_header=hdr, dense=dense, defer_reset=mine, **kw):
+            if obj.encode(grads, wire, slot, salt, errs, scale, draws=draws, graph_header=hdr, dense=dense, defer_reset=defer_resets,
+                          table_current=table_current, **kw):      # (table_current: an address-free graph's launches, shared header)
                 skip.update(idxs)
                 if dense is not None:
                     skip.update(self.dense_idx)      # (copied by that launch)
-                if overlap is not None:
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    overlap["events"][id(obj)] = ev
-                    overlap["resets"][id(obj)] = mine
         if len(self.dense_idx) >= 2 and self.dense_idx[0] not in skip:
             # all small tensors with one concatenation straight into the packed wire region.  Under
             # error feedback their residual is identically zero (decoded == grad), so nothing else to do.
@@ -667,51 +648,6 @@ class PSQuantizer(object):
             skip.update(self.dense_idx)
         return skip
 
-    @staticmethod
-    def _new_graph():
-        """The graph object of a capture.  $GQ_DIRECT_REPLAY (default 1): kept as a graph (keep_graph) so that _replayable can read its
-        kernel nodes back."""
-        if os.environ.get("GQ_DIRECT_REPLAY", "1") != "0":
-            try:
-                return torch.cuda.CUDAGraph(keep_graph=True)
-            except TypeError:      # (a torch without keep_graph: the graph's own replay)
-                pass
-        return torch.cuda.CUDAGraph()
-
-    @staticmethod
-    def _replayable(graph):
-        """What an entry's replay() runs: the captured kernel nodes as PLAIN launches on the current stream (native.LaunchPlan --
-        a replayed graph pays 4-5 us of boundary between two replays that launches on a stream do not: 62.4 against 57.6 us per
-        two-kernel ResNet-50 step, tools/direct_vs_graph.py), or the graph itself where it is not one chain of kernel launches
-        (two branches, a torch without raw graph access) or $GQ_DIRECT_REPLAY=0."""
-        if os.environ.get("GQ_DIRECT_REPLAY", "1") != "0" and hasattr(graph, "raw_cuda_graph"):
-            try:
-                return native.LaunchPlan(graph)
-            except Exception:
-                pass
-        try:
-            graph.instantiate()      # (keep_graph: not instantiated by capture_end)
-        except Exception:
-            pass
-        return graph
-
-    @staticmethod
-    def _graph_entry(cache, key, max_captured=48, max_counting=64):
-        """[sightings, graph or None, keep-alive] of `key`, its sighting counted.  A few address sets recur (the allocator
-        hands the same blocks out again); captured graphs are never evicted -- once max_captured of them exist, new sets keep
-        their eager launches (None) instead of displacing one another capture by capture -- and among the entries that
-        only count sightings the oldest goes first."""
-        ent = cache.get(key)
-        if ent is None:
-            counting = [k for k, e in cache.items() if e[1] is None]
-            if sum(1 for k, e in cache.items() if e[1] is not None and not (type(k) is tuple and k and k[0] == "any")) >= max_captured:
-                return None      # (address-free graphs, keys ("any", ...), are not counted)
-            if len(counting) >= max_counting:
-                cache.pop(counting[0])
-            ent = cache[key] = [0, None, None]
-        ent[0] += 1
-        return ent
-
     def _capture_record(self, ent, all_grads, wire, slot, user, salt, scale, dev, generic=False):
         """Stream-capture the launches the record just made eagerly, with copies of the headers it has just sent
         (the shared pinned buffers are rewritten by later records, a graph's memcpy node reads its source at every replay).
@@ -721,16 +657,12 @@ class PSQuantizer(object):
             # (device-resident: the graph's copy node is device-to-device.  A host-to-device node -- pinned memory over PCIe --
             # cost 15 us of every replayed step, tools/graph_pieces.py; the 5 KB header per captured graph is nothing)
             headers = None if generic else [g[2]._host[g[2]._last_slot].to(dev) for g in self._groups]
-            graph = self._new_graph()
-            with _capturing(graph):
+            with _capturing(self._direct) as graph:
                 self._record_launches(all_grads, wire, slot, user, salt, scale, None, dev, headers=headers, table_current=generic)
-            graph = self._replayable(graph)
+            ent[1], ent[2] = _replayable(graph, self._direct), headers
         except Exception as e:      # a capture that fails leaves the eager path as it was (this record has already run eagerly)
             self.use_graphs = False
-            import warnings
             warnings.warn("gq_graph: capturing a record failed (%s); continuing with eager launches" % (e,))
-            return
-        ent[1], ent[2] = graph, headers
 
     def _capture_step(self, fent, headers, all_grads, wire, slot, user, salt, scale, dev):
         """One graph for a whole step: the record's launches (headers: the device copies its own graph keeps) and the
@@ -738,55 +670,66 @@ class PSQuantizer(object):
         executes here; the output-buffer turns the capture advances are put back for the apply() that is still to come."""
         after = ([g[2]._out_turn for g in self._groups], self._dense_turn)
         try:
-            graph = self._new_graph()
-            with _capturing(graph):
+            with _capturing(self._direct) as graph:
                 resets = []      # the groups' accumulator resets ride in the step's last launch
                 fuse = self._can_fuse_levels()      # one rank, one user: level launch + decode of that payload as ONE launch
-                overlap = None
-                if len(self._groups) >= 2 and all(g[2].takes_tail for g in self._groups) and os.environ.get("GQ_STEP_TAIL", "1") != "0":
-                    # a chunked list (_overlap_fractions): every group's level / decode launch (with the group's OWN tail) on the
-                    # side stream behind its compress -- a parallel branch of this graph
-                    if self._side_stream is None:
-                        self._side_stream = torch.cuda.Stream(device=dev)
-                    overlap = {"events": {}, "resets": {}, "side": self._side_stream if os.environ.get("GQ_OVERLAP_STREAMS", "1") != "0" else None}
                 self._record_launches(all_grads, wire, slot, user, salt, scale, None, dev, headers=headers, defer_resets=resets,
-                                      fuse_levels=fuse, overlap=overlap, table_current=headers is None)
-                decoded = self._decode_all(self._wire[:1], False, (), resets=resets, fused_levels=fuse, overlap=overlap)
-            fent[1], fent[2] = self._replayable(graph), decoded
+                                      fuse_levels=fuse, table_current=headers is None)
+                decoded = self._decode_all(self._wire[:1], False, (), resets=resets, fused_levels=fuse)
+            fent[1], fent[2] = _replayable(graph, self._direct), decoded
         except Exception as e:      # the two-graph replay keeps working
             self._fuse_steps = False
             for g in self._groups:      # a launch that failed between a group's encode and its level launch: back to the shared header
-                if g[2] is not None:
-                    g[2]._graph_tables_abort()
-                    if getattr(g[2], "_pending_levels", None) is not None:
-                        g[2]._pending_levels = None
-            import warnings
+                g[2].graph_tables_abort()
             warnings.warn("gq_graph: capturing a whole step failed (%s); record and apply keep their own graphs" % (e,))
         finally:
-            for g, t in zip(self._groups, after[0]):
-                g[2]._out_turn = t
-            self._dense_turn = after[1]
+            self._set_turns(after)
+
+    def _capture_apply(self, ent, graph_key, gathered, decoded):
+        """Stream-capture the launches the apply has just made eagerly, from the output-buffer turns it started with (in
+        graph_key); nothing executes here, and the turns are put back as the eager apply left them."""
+        after = ([g[2]._out_turn for g in self._groups], self._dense_turn)
+        try:
+            self._set_turns((graph_key[2], graph_key[3]))
+            # two-phase (ps_quantizer.py:52-61): the second phase's encode reads a device copy of the table its eager run
+            # has just sent (the decode-mean's output buffers, the server residuals), which belongs to this graph
+            hdrs2 = [g[2]._host[g[2]._last_slot].to(gathered.device) for g in self._groups] if self.two_phase else None
+            calls = self._phase2_calls
+            with _capturing(self._direct) as graph:
+                again = self._decode_all(gathered, self.two_phase, (), phase2_headers=hdrs2)
+            if self._phase2_calls != calls:      # (a seed baked into the graph would replay the same draws every step)
+                raise RuntimeError("a captured second phase must not take per-call seeds")
+            if len(again) == len(decoded) and all(a is b for a, b in zip(again, decoded)):
+                ent[1], ent[2] = _replayable(graph, self._direct), decoded
+                ent.append(hdrs2)      # (kept alive with the graph)
+        except Exception as e:      # this apply has already run eagerly
+            self.use_graphs = False
+            for g in self._groups:
+                g[2].graph_tables_abort()
+            warnings.warn("gq_graph: capturing an apply failed (%s); continuing with eager launches" % (e,))
+        finally:
+            self._set_turns(after)
+
+    def _set_turns(self, turns):      # (the groups' output turns, the dense tensors' turn): the buffers the next decode takes
+        for g, t in zip(self._groups, turns[0]):
+            g[2].set_out_turn(t)
+        self._dense_turn = turns[1]
 
     def _can_fuse_levels(self):
         """A whole step of one rank and one user whose tensors all go through ONE HSQ group (+ the dense tensors riding in
         its launches): encode, then gq_hsq_levels_decode_batched.  $GQ_FUSE_LEVELS=0 keeps the three launches."""
-        if os.environ.get("GQ_FUSE_LEVELS", "1") == "0" or not self._groups:
+        if not self._fuse_levels or not self._groups:
             return False
         if self.error_feedback:
             # measured twice (profiles/r05_experiments.txt, 2 and 8): with error feedback the one launch moves three streams (updated
             # gradient in, residual and decoded tensor out) and is SLOWER than the level launch + the decode (0.1203 against
             # 0.1175 ms per step); the opt-in that forced it ($GQ_FUSE_LEVELS=ef) went in round 6
             return False
-        obj = self._groups[0][2]      # (several groups: the chunks of ONE tensor group, _overlap_chunks; the first carries the dense tensors)
         return (all(isinstance(g[2], BatchedHSQ) and g[2].fusable_levels() for g in self._groups)
-                and (not self.dense_idx or (len(self.dense_idx) >= 2 and obj.ndense))
-                and os.environ.get("GQ_STEP_TAIL", "1") != "0")
-
-    def _apply_key(self, gathered):
-        """What an apply()'s captured launches depend on: payload count, the wire, and which output buffers are next."""
-        return self._apply_key_for(gathered.shape[0], gathered.data_ptr())
+                and (not self.dense_idx or (len(self.dense_idx) >= 2 and self._groups[0][2].ndense)) and self._step_tail)
 
     def _apply_key_for(self, R, ptr):
+        """What an apply()'s captured launches depend on: payload count, the wire, and which output buffers are next."""
         # (the two tuples of buffer addresses change only when a buffer is allocated: remembered per (turns, allocation count))
         turns = tuple([g[2]._out_turn for g in self._groups])
         gen = (turns, self._dense_turn, self._dense_gen, tuple([g[2]._out_gen for g in self._groups]))
@@ -805,7 +748,7 @@ class PSQuantizer(object):
         o = self._draw_off[i]
         return {"r": draws[0][o:o + self.codecs[i].M]}
 
-    def _decode_all(self, gathered, two_phase, pending=(), plain=False, resets=None, fused_levels=False, overlap=None, phase2_headers=None):
+    def _decode_all(self, gathered, two_phase, pending=(), plain=False, resets=None, fused_levels=False, phase2_headers=None):
         """Mean of the R = gathered.shape[0] user payloads for every parameter (ps_quantizer.py:47-61),
         as a list of tensors in parameter order.  `pending`: the transfers that fill `gathered`
         (exchange.WireExchange.start) -- one, or one per byte range for a split / pipelined exchange, in which case the
@@ -851,30 +794,7 @@ class PSQuantizer(object):
                 self._dense_gen += 1
             dense_job = (rows, k)
         tail, tail_group = None, -1
-        tails = None
-        if overlap is not None:
-            # whole-step capture of a chunked list: every group's launch carries its OWN tail -- the step of its own draws' words,
-            # the reset of its own accumulators (both behind the group's last reader, whatever the other branch is doing), and the
-            # first group's also the mean of the dense tensors its compress launch copied into the wire
-            assert on_gpu and not chunked and not two_phase and [g[2] for g in groups] == [g[2] for g in self._groups]
-            mean_in_tail = dense_job is not None and not (plain and R == 1)
-            tails = {}
-            for gi, g in enumerate(groups):
-                obj = g[2]
-                rs = overlap["resets"].get(id(obj)) or []
-                pairs = (self._rng_state[gi * self.RNG_SLOTS:(gi + 1) * self.RNG_SLOTS]
-                         if (step_rng and obj.rng_pairs is not None) else None)
-                first = gi == 0 and mean_in_tail
-                if first or pairs is not None or rs:
-                    tails[gi] = native.StepTail(rows=dense_job[0] if first else None, out=self._dense_mean[dense_job[1]] if first else None,
-                                                rng_state=pairs, reset=rs[0] if rs else None, ticket=self._ticket_for(gathered.device, gi))
-                for extra in rs[1:]:
-                    resets.append(extra)
-            if step_rng and all(g[2].rng_pairs is not None for g in groups):
-                step_rng = False
-            if mean_in_tail:
-                dense_job = (None, dense_job[1])
-        elif on_gpu and not chunked and not two_phase and os.environ.get("GQ_STEP_TAIL", "1") != "0":
+        if on_gpu and not chunked and not two_phase and self._step_tail:
             takers = [gi for gi, g in enumerate(groups) if g[2].takes_tail]
             mean_in_tail = dense_job is not None and not (plain and R == 1)
             if takers and (mean_in_tail or step_rng or resets):
@@ -882,12 +802,10 @@ class PSQuantizer(object):
                 tail = native.StepTail(rows=dense_job[0] if mean_in_tail else None,
                                        out=self._dense_mean[dense_job[1]] if mean_in_tail else None,
                                        rng_state=self._rng_state if step_rng else None, reset=resets.pop(0) if resets else None,
-                                       ticket=self._ticket_for(gathered.device, 0))
+                                       ticket=self._ticket_for(gathered.device))
                 step_rng = False
                 if mean_in_tail:
                     dense_job = (None, dense_job[1])      # (done by the decode launch)
-
-        main_stream = torch.cuda.current_stream() if overlap is not None else None
 
         def decode_range(lo, hi, first):
             """The tensors whose wire section starts in [lo, hi) (None: all of them)."""
@@ -899,21 +817,11 @@ class PSQuantizer(object):
                         part = seg_ranges[(gi, lo, hi)] = (sum(1 for i in idxs if self.offsets[i] < lo),
                                                           sum(1 for i in idxs if self.offsets[i] < hi))
                     part = part + (first,)
-                t = tails.get(gi) if tails is not None else (tail if gi == tail_group else None)
-                side = overlap["side"] if overlap is not None else None
-                if side is not None:      # this group's branch: behind its compress, next to the following groups' compresses
-                    side.wait_event(overlap["events"][id(obj)])
-                    torch.cuda.set_stream(side)
-                try:
-                    if fused_levels and lo is None and getattr(obj, "_pending_levels", None) is not None:
-                        group_views[gi] = obj.levels_decode(plain, t)      # levels + decode (+ tail): one launch
-                    else:
-                        group_views[gi] = obj.decode_mean(gathered, R, part, plain=plain, tail=t)
-                finally:
-                    if side is not None:
-                        torch.cuda.set_stream(main_stream)
-            if overlap is not None and overlap["side"] is not None:
-                main_stream.wait_stream(overlap["side"])      # the branches join: the step's graph ends behind all of them
+                t = tail if gi == tail_group else None
+                if fused_levels and lo is None and obj._pending_levels is not None:
+                    group_views[gi] = obj.levels_decode(plain, t)      # levels + decode (+ tail): one launch
+                else:
+                    group_views[gi] = obj.decode_mean(gathered, R, part, plain=plain, tail=t)
             for i in single:
                 if lo is None or lo <= self.offsets[i] < hi:
                     done[i] = self.codecs[i].decode_mean(gathered, self.offsets[i], R, plain=plain)
@@ -1034,53 +942,20 @@ class PSQuantizer(object):
             for pnd in pending:
                 pnd.wait()
             pending = ()
-            graph_key = self._apply_key(gathered)
+            graph_key = self._apply_key_for(gathered.shape[0], gathered.data_ptr())
             if self.two_phase and self.error_feedback:      # (the server residuals' addresses are in the second phase's table)
                 graph_key += (tuple(p.server_error.data_ptr() for p in self.parameters),)
             ent = self._apply_graphs.get(graph_key)
             if ent is not None and ent[1] is not None:
-                if self.two_phase:      # the re-compress folds into the accumulators an eager record() may have left used
-                    for g in self._groups:
-                        g[2].ensure_clean()
-                ent[1].replay()
-                for g in self._groups:
-                    if not self.two_phase:      # (two-phase: decode-mean and the re-decode took one output buffer each -- back to the first)
-                        g[2]._out_turn ^= 1
-                    g[2]._last_ptrs = None      # (two-phase: the last eager upload is not what the device header was last used with)
-                if len(self.dense_idx) >= 2:
-                    self._dense_turn ^= 1
+                # (two-phase: the re-compress folds into accumulators an eager record() may have left used; the re-decode turns back)
+                self._replayed(ent, None, self.two_phase, True, True)
                 decoded = ent[2]
         if decoded is None:
             decoded = self._decode_all(gathered, self.two_phase, pending)
             if graph_key is not None and self._plan is not None and not self._plan[2]:     # (no per-tensor decodes in the plan)
-                ent = self._graph_entry(self._apply_graphs, graph_key)
+                ent = self._apply_graphs.sight(graph_key)
                 if ent is not None and ent[0] >= 2 and ent[1] is None:
-                    after = ([g[2]._out_turn for g in self._groups], self._dense_turn)
-                    try:
-                        for g, t in zip(self._groups, graph_key[2]):      # the capture re-issues the launches of THIS apply
-                            g[2]._out_turn = t
-                        self._dense_turn = graph_key[3]
-                        # two-phase (ps_quantizer.py:52-61): the second phase's encode reads a device copy of the table its eager run
-                        # has just sent (the decode-mean's output buffers, the server residuals), which belongs to this graph
-                        hdrs2 = [g[2]._host[g[2]._last_slot].to(gathered.device) for g in self._groups] if self.two_phase else None
-                        calls = self._phase2_calls
-                        graph = self._new_graph()
-                        with _capturing(graph):
-                            again = self._decode_all(gathered, self.two_phase, (), phase2_headers=hdrs2)
-                        assert self._phase2_calls == calls, "a captured second phase must not take per-call seeds"
-                        if len(again) == len(decoded) and all(a is b for a, b in zip(again, decoded)):
-                            ent[1], ent[2] = self._replayable(graph), decoded
-                            ent.append(hdrs2)      # (kept alive with the graph)
-                    except Exception as e:      # this apply has already run eagerly
-                        self.use_graphs = False
-                        for g in self._groups:
-                            g[2]._graph_tables_abort()
-                        import warnings
-                        warnings.warn("gq_graph: capturing an apply failed (%s); continuing with eager launches" % (e,))
-                    finally:
-                        for g, t in zip(self._groups, after[0]):
-                            g[2]._out_turn = t
-                        self._dense_turn = after[1]
+                    self._capture_apply(ent, graph_key, gathered, decoded)
         # ps_quantizer.py:63 `param.grad.data = g`: `param.grad` is evaluated HERE, at apply time -- a caller that replaced a
         # parameter's .grad object after the last record() gets the mean in the object it holds now.  The C++ helper reads
         # p.grad() without building Python objects (the 161 attribute look-ups were the step's largest host cost, which is

@@ -50,7 +50,7 @@ L = native.lib()
 wire = q._wire[0]
 out = grp._outs[0]
 dense_rows = q._wire[:1][:, q.dense_off:q.dense_off + q.dense_bytes].view(torch.float32)
-tail = native.StepTail(rows=dense_rows, out=q._dense_mean[0], rng_state=q._rng_state, reset=(grp._dev[grp._table_words:grp._dense_at], grp._acc_init), ticket=q._ticket_for(dev, 0))
+tail = native.StepTail(rows=dense_rows, out=q._dense_mean[0], rng_state=q._rng_state, reset=(grp._dev[grp._table_words:grp._dense_at], grp._acc_init), ticket=q._ticket_for(dev))
 seed = grp._counter_seed(0)
 st = native._stream()
 wp, op = ctypes.c_void_p(wire.data_ptr()), ctypes.c_void_p(out.data_ptr())
