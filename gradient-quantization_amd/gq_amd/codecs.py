@@ -6,7 +6,8 @@ device memory, through gq_amd.native).
     HSQCodec / QSGDCodec       one tensor per launch (the reference's per-tensor loop, nearest_neighbor_compressor.py:63-90,
                                qsgd_compressor.py:42-71)
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
-    BatchedHSQ / BatchedQSGD / BatchedTopK
+    SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
+    BatchedHSQ / BatchedQSGD / BatchedTopK / BatchedSign
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -19,8 +20,8 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (IdenticalCompressor, NearestNeighborCompressor, QSGDCompressor, TopKSparsificationCompressor,
-                          _next_seed, _require_device)
+from .compressors import (IdenticalCompressor, NearestNeighborCompressor, QSGDCompressor, SignSGDCompressor,
+                          TopKSparsificationCompressor, _next_seed, _require_device)
 
 
 def _up(x, a=16):
@@ -415,6 +416,58 @@ class TopKCodec(object):
         if self.k == 0:
             out.zero_()
             return
+        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
+
+    def decode_mean(self, gathered, off, R, plain=False):
+        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        self._decode_rows(gathered, off, R, out, plain=plain)
+        return out.view(self.shape)
+
+
+def sign_section_bytes(numel):
+    """Bytes of one tensor's section of the 2-bit sign wire (include/gq_sign.h): ceil(numel / 16) words, 16-byte aligned."""
+    return _up(-(-numel // 16) * 4)
+
+
+class SignCodec(object):
+    """SignSGDCompressor on the HIP kernels (libgq_sign.so).  Wire per tensor: one 2-bit code per element, 00 = +0, 01 = +1,
+    11 = -1, sixteen to a little-endian uint32 word (element i in bits 2*(i%16) of word i/16) -- _up(ceil(numel/16) * 4) bytes.
+    torch.sign never returns -0 or NaN on the device, so the wire holds the decoded tensor exactly.  Every call is a one-tensor
+    BatchedSign; roundtrip / encode_decode_into return the compress launch's own dense sign(grad)."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.nbytes = sign_section_bytes(numel)
+        self._single = None
+
+    def _batched1(self, dev):
+        if self._single is None or self._single.device != dev:
+            self._single = BatchedSign([self], [0], [0], dev, 1, max(16, self.nbytes))
+        return self._single
+
+    def encode_decode_into(self, grad, wire_user, off, salt, out):
+        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch."""
+        _require_device(grad, "SignCodec.encode_decode_into")
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt, out=out.view(-1))
+        assert ok, "SignCodec: the gradient must be a float32 tensor on the current device"
+
+    def encode_into(self, grad, wire_user, off, salt):
+        _require_device(grad, "SignCodec.encode_into")
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt)
+        assert ok, "SignCodec: the gradient must be a float32 tensor on the current device"
+
+    def roundtrip(self, grad, salt):
+        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
+        tmp = torch.empty(max(16, self.nbytes), dtype=torch.uint8, device=grad.device)
+        self.encode_decode_into(grad, tmp, 0, salt, out)
+        return out.view(self.shape)
+
+    def decode_wire(self, wire_user, off, out):
+        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
+
+    def _decode_rows(self, gathered, off, R, out, plain=False):
         self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
 
     def decode_mean(self, gathered, off, R, plain=False):
@@ -1083,6 +1136,92 @@ class BatchedTopK(_BatchedBase):
         return views
 
 
+class BatchedSign(_BatchedBase):
+    """All SignSGDCompressor tensors in ONE gq_sign_compress_batched launch and ONE gq_sign_decode_sum_batched launch
+    (include/gq_sign.h).  No draws and no scratch: both replay from a HIP graph.  The compress also writes the dense sign(w)
+    where a caller asks for it (the two-phase re-compress returns it); with error feedback it updates the gradient and the
+    residual in the same launch.  The decode-mean sums the codes as integers and divides by R: gq_mean_rows' result over the
+    dense signs, bit for bit."""
+
+    takes_tail = False
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is SignCodec
+
+    @staticmethod
+    def group_key(codec):
+        return ()
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        self.idxs = list(idxs)
+        self.codecs = [codecs[i] for i in self.idxs]
+        nseg = len(self.idxs)
+        table = torch.zeros((nseg, 8), dtype=torch.int64)
+        item_seg = []
+        item, out_off = 0, 0
+        self.out_off = []
+        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
+            items = max(1, -(-cd.nbytes // native.SIGN_ITEM_BYTES))
+            table[s, 1], table[s, 2], table[s, 3], table[s, 5] = cd.numel, item, offsets[i], out_off
+            item_seg += [s] * items
+            item += items
+            self.out_off.append(out_off)
+            out_off += -(-cd.numel // 4) * 4      # (16-byte aligned views: the launches store float4 there)
+        self.out_floats = out_off
+        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
+        self._item_seg, self._nitems = self.item_seg, item
+        self._setup(table, None, device, slots, user_bytes, dense)
+        self.align = 4
+        self.random = False
+        self._batch = native.SignBatch(self._dev[:self._table_words], self.item_seg, nseg, item)
+
+    def graphable(self):
+        return True
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None):
+        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense sign.  With `errs`: error feedback
+        in the same launch (t += ef_scale*err before the sign, err = t - sign(t) after it, both in place).
+        graph_header, dense, table_current: see BatchedHSQ.encode."""
+        if graph_header is not None:
+            self._graph_tables(graph_header, dense)
+        elif table_current:
+            self._batch.set_table(self._dev[:self._table_words])
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        elif not self._upload(tensors, slot, self.align, errs, dense):
+            return False
+        else:
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        try:
+            self._batch.compress(wire_user, out, ef_scale if errs is not None else None)
+        except BaseException:
+            if graph_header is not None:
+                self.graph_tables_abort()
+            raise
+        if graph_header is not None:
+            self._graph_tables_done(defer_reset)
+        return True
+
+    def decode_into(self, gathered, R, out, plain=False):
+        """The decode-mean launch into a caller's buffer (SignCodec: a one-tensor group, its section at offset 0 of the rows)."""
+        if not self.ready:
+            self.upload_layout()
+        self._batch.decode(gathered, R, out, plain=plain)
+
+    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
+        """decompress(compress(t)) for every tensor of the group: the compress launch's own dense sign, no decode launch.
+        See _BatchedBase.roundtrip."""
+        if self._tmp_wire is None:
+            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
+        out, views = self._out_buffer(self.device)
+        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
+        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, out=out, **kw):
+            self._out_turn ^= 1      # (the buffer was not used)
+            return None
+        return views
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, IdenticalCompressor):
         return DenseCodec(compressor, numel, shape)
@@ -1092,4 +1231,6 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return QSGDCodec(compressor, numel, shape)
     if isinstance(compressor, TopKSparsificationCompressor):
         return TopKCodec(compressor, numel, shape)
+    if isinstance(compressor, SignSGDCompressor):
+        return SignCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)

@@ -438,9 +438,8 @@ class ResidualCompressor(object):
 
 
 # ---- exported for `from compressors import *` in the reference's main.py ----------------
-# SignSGD is not on the accelerated path: plain tensor ops, kept only so that main.py's
-# `quantizer_choices` table resolves.  TopK runs on the HIP kernels for device tensors (libgq_topk.so; the quantizers ship it
-# on a sparse wire, gq_amd.codecs.TopKCodec) and keeps the reference's torch expression for CPU tensors.
+# SignSGD and TopK run on HIP kernels for device float32 tensors (libgq_sign.so, libgq_topk.so; the quantizers ship them on a
+# 2-bit and a sparse wire, gq_amd.codecs.SignCodec / TopKCodec) and keep the reference's torch expressions for CPU tensors.
 
 class SignSGDCompressor(object):
     """sign(v) (signsgd_compressor.py:4-12)."""
@@ -449,10 +448,24 @@ class SignSGDCompressor(object):
         pass
 
     def compress(self, vec):
+        if vec.device.type == "cuda" and vec.dtype == torch.float32:
+            # the sign kernels (libgq_sign.so, gq_amd.codecs.SignCodec): torch.sign's tensor bit for bit
+            return self._device_roundtrip(vec)
         return torch.sign(vec)
 
     def decompress(self, signature):
         return signature
+
+    def _device_roundtrip(self, vec):
+        from .codecs import SignCodec      # (codecs imports this module)
+        n = vec.numel()
+        if n == 0:
+            return torch.sign(vec)
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = SignCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
 
 
 class TopKSparsificationCompressor(object):

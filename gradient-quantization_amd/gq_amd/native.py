@@ -684,3 +684,87 @@ class TopKBatch(object):
                                                ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
                                                _stream())
         _check_topk(rc, "gq_topk_decode_sum_batched")
+
+
+# ---- signSGD on a 2-bit wire: libgq_sign.so (include/gq_sign.h) -----------------------------------------------------------
+SIGN_LIB_PATH = os.environ.get("GQ_SIGN_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_sign.so")
+SIGN_ABI_VERSION = 1
+SIGN_EXPORTS = ["gq_sign_abi_version", "gq_sign_last_error", "gq_sign_compress_batched", "gq_sign_decode_sum_batched"]
+SIGN_ITEM_BYTES = 4096      # GQ_SIGN_ITEM_BYTES: wire bytes (16384 elements) per item
+
+_sign_lib = None
+
+
+def sign_lib():
+    """Load libgq_sign.so; fail loudly if it was not built (as lib())."""
+    global _sign_lib
+    if _sign_lib is None:
+        if not os.path.exists(SIGN_LIB_PATH):
+            raise GQNativeError("libgq_sign.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                "(there is no CPU fallback)" % SIGN_LIB_PATH)
+        L = ctypes.CDLL(SIGN_LIB_PATH)
+        L.gq_sign_last_error.restype = ctypes.c_char_p
+        L.gq_sign_abi_version.restype = ctypes.c_int
+        for name in SIGN_EXPORTS:
+            getattr(L, name)
+        if L.gq_sign_abi_version() != SIGN_ABI_VERSION:
+            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
+                                % (SIGN_LIB_PATH, L.gq_sign_abi_version(), SIGN_ABI_VERSION))
+        _sign_lib = L
+    return _sign_lib
+
+
+def _check_sign(rc, what):
+    CALLS[0] += 1
+    if rc != 0:
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, sign_lib().gq_sign_last_error().decode()))
+
+
+class _SignBatchStruct(ctypes.Structure):     # gq_sign_batch (include/gq_sign.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
+                ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class SignBatch(object):
+    """The multi-tensor sign launches: gq_sign_compress_batched (2-bit codes, + the dense signs and the residual) and
+    gq_sign_decode_sum_batched.  No scratch: both are one launch over the segment table."""
+
+    def __init__(self, seg_table, item_seg, nseg, nitems):
+        self.L = sign_lib()
+        self.keep = (seg_table, item_seg)
+        self.s = _SignBatchStruct(ctypes.sizeof(_SignBatchStruct), int(nseg), int(nitems), _dev_ptr(seg_table, torch.int64, "seg_table").value,
+                                  _dev_ptr(item_seg, torch.int32, "item_seg").value, None, 0, 0)
+        self.ref = ctypes.byref(self.s)
+
+    def set_table(self, seg_table):
+        """As HSQBatch.set_table."""
+        self.keep_table = seg_table
+        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
+
+    def set_dense(self, dense_table, ndense):
+        """As QSGDBatch.set_dense: the compress launch also copies the uncompressed tensors into the wire."""
+        self.keep_dense = dense_table
+        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
+        self.s.ndense = int(ndense) if dense_table is not None else 0
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
+        return SignBatch(seg_table, item_seg, nseg, nitems)
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense sign(w) (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
+        (seg_table[:, 7] = error buffers)."""
+        rc = self.L.gq_sign_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
+                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check_sign(rc, "gq_sign_compress_batched")
+
+    def decode(self, gathered, R, out, plain=False):
+        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
+        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
+        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
+        rc = self.L.gq_sign_decode_sum_batched(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride),
+                                               ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
+                                               _stream())
+        _check_sign(rc, "gq_sign_decode_sum_batched")

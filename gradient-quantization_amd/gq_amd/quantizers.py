@@ -46,8 +46,8 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedHSQ, BatchedQSGD, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, TopKCodec, _BatchedBase, _DATA_PTR,
-    _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
+    BatchedHSQ, BatchedQSGD, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, SignCodec, TopKCodec,
+    _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     wire_levels_mode)
 
 
@@ -217,7 +217,7 @@ class PSQuantizer(object):
         self._step_tail = os.environ.get("GQ_STEP_TAIL", "1") != "0"       # (see _decode_all)
         self._fuse_levels = os.environ.get("GQ_FUSE_LEVELS", "1") != "0"   # (see _can_fuse_levels)
         BatchedQSGD.place_lone_buckets(self.codecs)
-        for cls in (BatchedHSQ, BatchedQSGD, BatchedTopK):
+        for cls in (BatchedHSQ, BatchedQSGD, BatchedTopK, BatchedSign):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -976,7 +976,8 @@ class PSQuantizer(object):
 def _ring_codec_factory(compressor, numel, shape, packed6=False):
     """The ring's hops carry decompress(compress(running sum)) as the reference computes it: a top-k tensor travels as its
     DECODED dense f32 (GenericCodec, the compressor's own compress -- the top-k kernels on a device tensor), so the signed zeros
-    and NaNs of the unkept entries reach the next hop as they do in ring_quantizer.py.  Every other compressor: the PS codecs."""
+    and NaNs of the unkept entries reach the next hop as they do in ring_quantizer.py.  Every other compressor: the PS codecs --
+    SignSGD's 2-bit wire among them, which carries the decoded tensor exactly (torch.sign yields no -0 and no NaN)."""
     if isinstance(compressor, TopKSparsificationCompressor):
         return GenericCodec(compressor, numel, shape)
     return default_codec_factory(compressor, numel, shape, packed6)
