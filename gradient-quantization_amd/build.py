@@ -21,6 +21,9 @@ TOPK_SOURCES = ["topk.hip"]
 # signSGD on a 2-bit wire (include/gq_sign.h): a library of its own too
 SIGN_LIB = os.path.join(HERE, "libgq_sign.so")
 SIGN_SOURCES = ["sign.hip"]
+# the multi-tensor ProbabilisticVectorCompressor encode (include/gq_pvq.h): likewise; it shares the walk with pvq.hip (csrc/pvq_walk.hpp)
+PVQ_LIB = os.path.join(HERE, "libgq_pvq.so")
+PVQ_SOURCES = ["pvq_batched.hip"]
 SOURCES = ["gq_common.hip", "gq_api.hip", "hsq_encode.hip", "hsq_encode_pf.hip", "hsq_encode_pfd.hip", "hsq_levels.hip", "hsq_batched.hip", "hsq_decode.hip", "qsgd.hip", "qsgd_batched.hip", "qsgd_wide.hip", "pvq.hip"]
 # -ffp-contract=off: the reference's elementwise ops are separately rounded; hipcc's
 # default ("fast") would fuse the decode's mul/add and the level quantiser's sub/div.
@@ -46,10 +49,10 @@ HOST_EXT = os.path.join(HERE, "gq_amd", "_gq_host.so")
 
 def needs_build():
     if (not os.path.exists(LIB) or not os.path.exists(os.path.join(HERE, "libgq_hsq_clock.so")) or not os.path.exists(HOST_EXT)
-            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB)):
+            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB) or not os.path.exists(PVQ_LIB)):
         return True
-    t = min(os.path.getmtime(LIB), os.path.getmtime(HOST_EXT), os.path.getmtime(TOPK_LIB), os.path.getmtime(SIGN_LIB))
-    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h")]
+    t = min(os.path.getmtime(LIB), os.path.getmtime(HOST_EXT), os.path.getmtime(TOPK_LIB), os.path.getmtime(SIGN_LIB), os.path.getmtime(PVQ_LIB))
+    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h", "gq_pvq.h")]
             + [__file__])
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -63,6 +66,7 @@ EXTRA = {
     "hsq_encode_pfd.hip": ["-fno-honor-nans", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     # every score of the f32 MFMA is read by the VALU (two sequential sums per subvector): keep them out of the AGPRs
     "pvq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "pvq_batched.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 
 
@@ -79,11 +83,11 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd), obj))
-    topk_objs, sign_objs = [], []
-    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs)):
+    topk_objs, sign_objs, pvq_objs = [], [], []
+    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs), (PVQ_SOURCES, pvq_objs)):
         for src in srcs:
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
-            cmd = [hipcc()] + compile_flags + ["-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = [hipcc()] + compile_flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             procs.append((cmd, subprocess.Popen(cmd), obj))
@@ -92,7 +96,7 @@ def build(force=False, verbose=False):
     for cmd, p, obj in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
-        if obj not in topk_objs and obj not in sign_objs:
+        if obj not in topk_objs and obj not in sign_objs and obj not in pvq_objs:
             objs.append(obj)
     link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
@@ -106,6 +110,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(link)
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", TOPK_LIB] + topk_objs)
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SIGN_LIB] + sign_objs)
+        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PVQ_LIB] + pvq_objs)
         build_clock_lib(objs, verbose)
     finally:
         if host is not None and host[1].wait() != 0:     # (always reaped, also when the link above raised)

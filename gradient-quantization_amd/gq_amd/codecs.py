@@ -5,9 +5,10 @@ device memory, through gq_amd.native).
     DenseCodec                 IdenticalCompressor tensors (<= 1000 elements, ps_quantizer.py:18-19): raw f32
     HSQCodec / QSGDCodec       one tensor per launch (the reference's per-tensor loop, nearest_neighbor_compressor.py:63-90,
                                qsgd_compressor.py:42-71)
+    PVQCodec                   ProbabilisticVectorCompressor: HSQCodec's wire, the sampled encode (gq_pvq_encode)
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
-    BatchedHSQ / BatchedQSGD / BatchedTopK / BatchedSign
+    BatchedHSQ / BatchedPVQ / BatchedQSGD / BatchedTopK / BatchedSign
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -20,8 +21,8 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (IdenticalCompressor, NearestNeighborCompressor, QSGDCompressor, SignSGDCompressor,
-                          TopKSparsificationCompressor, _next_seed, _require_device)
+from .compressors import (IdenticalCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor, QSGDCompressor,
+                          SignSGDCompressor, TopKSparsificationCompressor, _next_seed, _require_device)
 
 
 def _up(x, a=16):
@@ -185,6 +186,11 @@ class HSQCodec(object):
         nc = getattr(self.c, "norm_compressor", None)
         return bool(self.c.compressed_norm and nc is not None and nc.random and nc._rng == "reference")
 
+    def draw_count(self):
+        """Reference draws per compress (uses_reference_draws): the quantizer's one torch.rand per record gives the codec a
+        slice of this length."""
+        return self.M
+
     def _levels(self, u, partials, levels, lb_ub, salt, r=None):
         nc = self.c.norm_compressor
         if not nc.random:
@@ -272,6 +278,51 @@ class HSQCodec(object):
         if R == 1 and not plain:
             out.add_(0.0)   # one payload is the plain decompress (-0 kept); the aggregate is a sum that starts from +0
         return out.view(self.shape)
+
+
+class PVQCodec(HSQCodec):
+    """ProbabilisticVectorCompressor on the HIP kernels: HSQCodec's wire layout, packed6 rule and decode (the compressor's
+    decode IS HSQ's: codewords[codes] * norms, probabilistic_vector_compressor.py:67-77); the encode samples the codeword
+    (gq_pvq_encode).  Reference draws: torch.rand(M) for the codewords (:52, always), then torch.rand(M) for the levels
+    (probabilistic_scalar_compressor.py:23, with args.random and n_bit != 32) -- `r` is the two slices back to back.
+    gq_rng = "keyed" draws like "device" here (a fresh seed per call, as HSQCodec): only the multi-tensor launches key their
+    streams, so keyed runs with and without gq_no_batch give different bits."""
+
+    def _level_draws_wanted(self):
+        nc = getattr(self.c, "norm_compressor", None)
+        return bool(self.c.compressed_norm and nc is not None and nc.random)
+
+    def uses_reference_draws(self):
+        return self.c._rng == "reference"      # the sampler always draws
+
+    def draw_count(self):
+        return self.M * (2 if self._level_draws_wanted() else 1)
+
+    def encode_into(self, grad, wire_user, off, salt, r=None):
+        _require_device(grad, "PVQCodec.encode_into")
+        dev = grad.device
+        flat = grad.contiguous().view(-1)
+        codes, levels, lb_ub = self._views(wire_user, off)
+        _, cdag = self.c._on(dev)
+        u, partials = self._scratch(dev)
+        if not self.c.compressed_norm:
+            u = levels      # the `levels` section holds f32 u
+        r_levels = None
+        if self.c._rng == "reference":
+            if r is None:       # the compressor's own order: the codeword draws, then the level draws (HSQCodec._levels)
+                r_code = torch.rand(self.M).to(dev)
+            else:
+                r_code, r_levels = r[:self.M], (r[self.M:2 * self.M] if self._level_draws_wanted() else None)
+            native.pvq_encode(flat, cdag, codes, u, partials, native.RANDOM_GIVEN, r_code, 0)
+        else:
+            native.pvq_encode(flat, cdag, codes, u, partials, native.RANDOM_DEVICE, None, _next_seed() ^ salt)
+        if self.c.compressed_norm:
+            self._levels(u, partials, levels, lb_ub, salt, r_levels)
+
+    def encode_decode_into(self, grad, wire_user, off, salt, out, r=None):
+        """ONE compress: what travels is what the residual is taken against (ps_quantizer.py:37)."""
+        self.encode_into(grad, wire_user, off, salt, r)
+        self.decode_wire(wire_user, off, out)
 
 
 class QSGDCodec(object):
@@ -760,7 +811,10 @@ class BatchedHSQ(_BatchedBase):
         self.keyed = bool(self.random and c0.norm_compressor._rng == "keyed")   # draws keyed by (lb, ub): a launch that never changes
         self.counter = bool(self.random and c0.norm_compressor._rng == "device")  # draws keyed by a device step word: likewise, and fresh every step
         self.reference_draws = self.codecs[0].uses_reference_draws()     # the reference's CPU draws, handed in per record
-        self._r_index = self._r_flat = None
+        # ... for the level quantiser.  Here the two are one fact; BatchedPVQ's sampler draws also when the levels are
+        # deterministic or travel as f32, so there `reference_draws` (the record needs draws) can hold without this one
+        self.level_reference = bool(self.random and c0.norm_compressor._rng == "reference")
+        self._r_gather = {}
         self.codebook = c0._codebook_on(device)
         nseg = len(self.idxs)
         table = torch.zeros((nseg, 8), dtype=torch.int64)
@@ -791,25 +845,47 @@ class BatchedHSQ(_BatchedBase):
         self.ws = native.new_workspace(device, self.ntiles * 64)
         # ONE launch descriptor for the group (gq_hsq_batch): the library picks the kernels -- prefilter (K <= 256,
         # d = 8 / 12 / 16 / 24 / 32), the same with the pages of a larger codebook resident, or exact scoring for every other shape
-        self._batch = native.HSQBatch(self._dev[:self._table_words], self.tile_seg, self.nseg, self.ntiles, self.codebook,
-                                      self.code_dtype, cd0.wire_level_kind(), self.n_bit, self.u_flat,
-                                      self._dev[self._table_words:self._dense_at].view(torch.int32), self.ws)
+        self._batch = self._new_batch(cd0)
         self.profile_slot = -1      # measurement hook (bench.py): the NEXT encode's dispatch is timed into this slot
 
-    def _given_draws(self, draws):
-        """draws = (r_all on the device, {parameter index: offset of its M draws}): the reference's
+    def _new_batch(self, cd0):
+        return native.HSQBatch(self._dev[:self._table_words], self.tile_seg, self.nseg, self.ntiles, self.codebook,
+                               self.code_dtype, cd0.wire_level_kind(), self.n_bit, self.u_flat,
+                               self._dev[self._table_words:self._dense_at].view(torch.int32), self.ws)
+
+    def _given_draws(self, draws, which=0):
+        """draws = (r_all on the device, {parameter index: offset of its draws}): the reference's
         torch.rand(M) per tensor, drawn by the quantizer in ONE call per record.  Laid out like u_flat for
-        the level kernels (one gather through an index built once)."""
+        the kernels (one gather through an index built once).  which: the tensor's first (0) or second (1) run of M draws
+        (BatchedPVQ: the codeword draws, then the level draws)."""
         r_all, offsets = draws
-        if self._r_index is None:
+        ent = self._r_gather.get(which)
+        if ent is None:
             idx = torch.zeros(self.ntiles * 64, dtype=torch.int64)
             for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
                 first = int(self._layout[s, 2]) * 64
-                idx[first:first + cd.M] = torch.arange(offsets[i], offsets[i] + cd.M)
-            self._r_index = idx.to(self.device)
-            self._r_flat = torch.empty(self.ntiles * 64, dtype=torch.float32, device=self.device)
-        torch.index_select(r_all, 0, self._r_index, out=self._r_flat)
-        return self._r_flat
+                idx[first:first + cd.M] = torch.arange(offsets[i] + which * cd.M, offsets[i] + (which + 1) * cd.M)
+            ent = self._r_gather[which] = (idx.to(self.device), torch.empty(self.ntiles * 64, dtype=torch.float32, device=self.device))
+        torch.index_select(r_all, 0, ent[0], out=ent[1])
+        return ent[1]
+
+    _level_draw_run = 0      # which run of a tensor's reference draws the level quantiser takes
+
+    def _launch_encode(self, wire_user, ef, salt, counter_seed, draws):
+        self._batch.encode(wire_user, ef, self.profile_slot)
+        self.profile_slot = -1
+
+    def _level_draws(self, salt, counter_seed, draws):
+        """(random_mode, seed, r_flat) of the level launch."""
+        if self.n_bit == 32 or not self.random:
+            return native.RANDOM_OFF, 0, None
+        if self.level_reference:
+            return native.RANDOM_GIVEN, 0, self._given_draws(draws, self._level_draw_run)
+        if self.keyed:
+            return native.RANDOM_DEVICE_KEYED, (salt * 0x2545F4914F6CDD1D + 0x5851F42D4C957F2D) & (2 ** 63 - 1), None
+        if self.counter and counter_seed is not None:
+            return native.RANDOM_DEVICE_COUNTER, counter_seed, None
+        return native.RANDOM_DEVICE, _next_seed() ^ salt, None
 
     def graphable(self):
         """True when nothing in this group's launches changes from record to record for fixed gradient addresses (no
@@ -848,20 +924,8 @@ class BatchedHSQ(_BatchedBase):
         ef = ef_scale if errs is not None else None
         counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
         try:
-            self._batch.encode(wire_user, ef, self.profile_slot)
-            self.profile_slot = -1
-            if self.n_bit == 32:
-                mode, seed, r_flat = native.RANDOM_OFF, 0, None
-            elif self.reference_draws:
-                mode, seed, r_flat = native.RANDOM_GIVEN, 0, self._given_draws(draws)
-            elif self.keyed:
-                mode, seed, r_flat = native.RANDOM_DEVICE_KEYED, (salt * 0x2545F4914F6CDD1D + 0x5851F42D4C957F2D) & (2 ** 63 - 1), None
-            elif self.counter and counter_seed is not None:
-                mode, seed, r_flat = native.RANDOM_DEVICE_COUNTER, counter_seed, None
-            elif self.random:
-                mode, seed, r_flat = native.RANDOM_DEVICE, _next_seed() ^ salt, None
-            else:
-                mode, seed, r_flat = native.RANDOM_OFF, 0, None
+            self._launch_encode(wire_user, ef, salt, counter_seed, draws)
+            mode, seed, r_flat = self._level_draws(salt, counter_seed, draws)
             if skip_levels:
                 self._pending_levels = (wire_user, mode, seed, r_flat, errs is not None)
             else:
@@ -898,6 +962,55 @@ class BatchedHSQ(_BatchedBase):
             raise
         self._batch.set_table(self._dev[:self._table_words])      # (the reset itself rode in the launch: tail.reset)
         return views
+
+
+class BatchedPVQ(BatchedHSQ):
+    """BatchedHSQ for ProbabilisticVectorCompressor tensors: the same wire, tables, level launch, decode-mean (with its step
+    tail), fused error-feedback residual and graph machinery; the encode launch is gq_pvq_encode_batched (libgq_pvq.so), which
+    projects on c_dagger and SAMPLES the codeword, and the descriptor's codebook -- what the level launch's residual and the
+    decode read -- is the compressor's codewords.  The sampler always draws: one uniform per subvector from the compressor's
+    gq_rng ("reference": the quantizer's draw plan gives a tensor its codeword draws and then its level draws; "device": the
+    group's { seed, step } words, the level launch on another stream of the same words; "keyed": keyed by the subvector's l1).
+    Shapes: d in {8, 16, 32}, K = 32 ... 256 in whole blocks of 32, byte codes; every other tensor keeps PVQCodec."""
+
+    _level_draw_run = 1
+
+    @staticmethod
+    def eligible(codec):
+        c = getattr(codec, "c", None)
+        if type(codec) is not PVQCodec or c.K == c.dim:   # K == d: a random codebook per tensor
+            return False
+        return native.pvq_batched_serves(c.dim, c.K, codec.code_dtype)
+
+    @staticmethod
+    def group_key(codec):
+        return ("pvq",) + BatchedHSQ.group_key(codec)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        BatchedHSQ.__init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense)
+        rng = self.codecs[0].c._rng
+        self.keyed = rng == "keyed"
+        self.counter = rng == "device"       # (also without stochastic levels: the sampler's draws)
+
+    def _new_batch(self, cd0):
+        self.c_dagger = cd0.c._on(self.device)[1]
+        return native.PVQBatch(self._dev[:self._table_words], self.tile_seg, self.nseg, self.ntiles, self.codebook, self.c_dagger,
+                               self.code_dtype, cd0.wire_level_kind(), self.n_bit, self.u_flat,
+                               self._dev[self._table_words:self._dense_at].view(torch.int32), self.ws)
+
+    def graphable(self):
+        return (self.keyed or (self.counter and self.rng_pairs is not None)) and not self.reference_draws and self._batch.path != 0
+
+    def _launch_encode(self, wire_user, ef, salt, counter_seed, draws):
+        if self.reference_draws:
+            mode, seed, r_flat = native.RANDOM_GIVEN, 0, self._given_draws(draws, 0)
+        elif self.keyed:
+            mode, seed, r_flat = native.RANDOM_DEVICE_KEYED, (salt * 0x2545F4914F6CDD1D + 0x5851F42D4C957F2D) & (2 ** 63 - 1), None
+        elif self.counter and counter_seed is not None:
+            mode, seed, r_flat = native.RANDOM_DEVICE_COUNTER, counter_seed, None
+        else:
+            mode, seed, r_flat = native.RANDOM_DEVICE, _next_seed() ^ salt, None
+        self._batch.encode(wire_user, ef, mode, seed, r_flat)
 
 
 class BatchedQSGD(_BatchedBase):
@@ -1223,6 +1336,8 @@ class BatchedSign(_BatchedBase):
 
 
 def default_codec_factory(compressor, numel, shape, packed6=False):
+    if isinstance(compressor, ProbabilisticVectorCompressor):
+        return PVQCodec(compressor, numel, shape, packed6)
     if isinstance(compressor, IdenticalCompressor):
         return DenseCodec(compressor, numel, shape)
     if isinstance(compressor, NearestNeighborCompressor):

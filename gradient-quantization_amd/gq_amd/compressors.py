@@ -358,6 +358,12 @@ class ProbabilisticVectorCompressor(object):
             self.c_dagger = self.c_dagger.to(device)
         return self.codewords, self.c_dagger
 
+    def _codebook_on(self, device):
+        """The DECODE codebook, as NearestNeighborCompressor names it (the wire codecs decode both classes the same way)."""
+        return self._on(device)[0]
+
+    wire_level_dtype = NearestNeighborCompressor.wire_level_dtype
+
     def compress(self, vec, minus=None):
         """minus = (codes1, norm1, codebook1): compress  vec - codebook1[codes1] * norm1  -- the residual of a first
         stage (ResidualCompressor) -- computed inside the kernel's tile staging instead of as a tensor."""

@@ -32,8 +32,8 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (IdenticalCompressor, NearestNeighborCompressor, QSGDCompressor, SignSGDCompressor,
-                          TopKSparsificationCompressor)
+from .compressors import (IdenticalCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor, QSGDCompressor,
+                          SignSGDCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
 quantizer_choices = {          # main.py:20-26
@@ -42,6 +42,7 @@ quantizer_choices = {          # main.py:20-26
     'hsq': NearestNeighborCompressor,
     'sign': SignSGDCompressor,
     'topk': TopKSparsificationCompressor,
+    'pvq': ProbabilisticVectorCompressor,      # the unbiased vector quantiser (not in main.py's table: INTEGRATION.md)
 }
 
 

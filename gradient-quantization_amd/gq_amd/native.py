@@ -768,3 +768,72 @@ class SignBatch(object):
                                                ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
                                                _stream())
         _check_sign(rc, "gq_sign_decode_sum_batched")
+
+
+# ---- the ProbabilisticVectorCompressor's multi-tensor encode: libgq_pvq.so (include/gq_pvq.h) ------------------------------
+PVQ_LIB_PATH = os.environ.get("GQ_PVQ_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_pvq.so")
+PVQ_ABI_VERSION = 1
+PVQ_EXPORTS = ["gq_pvq_abi_version", "gq_pvq_last_error", "gq_pvq_batched_serves", "gq_pvq_encode_batched"]
+
+_pvq_lib = None
+
+
+def pvq_lib():
+    """Load libgq_pvq.so; fail loudly if it was not built (as lib())."""
+    global _pvq_lib
+    if _pvq_lib is None:
+        if not os.path.exists(PVQ_LIB_PATH):
+            raise GQNativeError("libgq_pvq.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                "(there is no CPU fallback)" % PVQ_LIB_PATH)
+        L = ctypes.CDLL(PVQ_LIB_PATH)
+        L.gq_pvq_last_error.restype = ctypes.c_char_p
+        L.gq_pvq_abi_version.restype = ctypes.c_int
+        for name in PVQ_EXPORTS:
+            getattr(L, name)
+        if L.gq_pvq_abi_version() != PVQ_ABI_VERSION:
+            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
+                                % (PVQ_LIB_PATH, L.gq_pvq_abi_version(), PVQ_ABI_VERSION))
+        _pvq_lib = L
+    return _pvq_lib
+
+
+def _check_pvq(rc, what):
+    CALLS[0] += 1
+    if rc != 0:
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, pvq_lib().gq_pvq_last_error().decode()))
+
+
+def pvq_batched_serves(d, K, code_dtype):
+    """True when the multi-tensor PVQ encode serves the shape: d in {8, 16, 32}, K = 32 ... 256 in whole blocks of 32, byte
+    codes (the host-side rule of gq_pvq_batched_serves; no library needed to ask)."""
+    return d in (8, 16, 32) and 32 <= K <= 256 and K % 32 == 0 and code_dtype == torch.uint8
+
+
+class _PVQBatchStruct(ctypes.Structure):      # gq_pvq_batch (include/gq_pvq.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("hsq", ctypes.c_void_p), ("c_dagger", ctypes.c_void_p)]
+
+
+class PVQBatch(HSQBatch):
+    """HSQBatch whose encode launch is gq_pvq_encode_batched: the descriptor's codebook is the compressor's codewords (levels
+    with error feedback, decode), the encode projects on c_dagger.  Levels / decode / levels_decode are HSQBatch's."""
+
+    def __init__(self, seg_table, tile_seg, nseg, ntiles, codebook, c_dagger, code_dtype, level_dtype, n_bit, u_flat=None,
+                 seg_minmax=None, workspace=None):
+        HSQBatch.__init__(self, seg_table, tile_seg, nseg, ntiles, codebook, code_dtype, level_dtype, n_bit, u_flat, seg_minmax, workspace)
+        self.PL = pvq_lib()
+        assert c_dagger.shape == codebook.shape
+        self.c_dagger = c_dagger
+        self.ps = _PVQBatchStruct(ctypes.sizeof(_PVQBatchStruct), 0, ctypes.addressof(self.s), _dev_ptr(c_dagger, torch.float32, "c_dagger").value)
+        self.pref = ctypes.byref(self.ps)
+        if not self.PL.gq_pvq_batched_serves(ctypes.c_int(self.s.d), ctypes.c_int(self.s.K), ctypes.c_int(self.s.code_bytes)):
+            self.path = 0
+
+    def encode(self, wire, ef_scale, random_mode, seed, r_flat=None):
+        """(Not HSQBatch.encode's arguments: the sampler needs draws, and there is no profile slot -- the timed dispatch is the
+        d16/K256 prefilter's.)  Every tensor's codes into `wire`, u into u_flat, (min, max) into seg_minmax.  One draw per subvector: r_flat
+        (RANDOM_GIVEN, laid out like u_flat) or in-kernel from `seed` (the level launch may be given the same seed: the encode
+        salts it)."""
+        rp = _dev_ptr(r_flat, torch.float32, "r_flat") if r_flat is not None else ctypes.c_void_p(0)
+        rc = self.PL.gq_pvq_encode_batched(self.pref, self._wire(wire), ctypes.c_int(random_mode), ctypes.c_uint64(seed & (2 ** 64 - 1)), rp,
+                                           ctypes.c_float(_NAN if ef_scale is None else ef_scale), _stream())
+        _check_pvq(rc, "gq_pvq_encode_batched")

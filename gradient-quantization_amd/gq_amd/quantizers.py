@@ -46,7 +46,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedHSQ, BatchedQSGD, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, SignCodec, TopKCodec,
+    BatchedHSQ, BatchedPVQ, BatchedQSGD, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, SignCodec, TopKCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     wire_levels_mode)
 
@@ -217,7 +217,7 @@ class PSQuantizer(object):
         self._step_tail = os.environ.get("GQ_STEP_TAIL", "1") != "0"       # (see _decode_all)
         self._fuse_levels = os.environ.get("GQ_FUSE_LEVELS", "1") != "0"   # (see _can_fuse_levels)
         BatchedQSGD.place_lone_buckets(self.codecs)
-        for cls in (BatchedHSQ, BatchedQSGD, BatchedTopK, BatchedSign):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedQSGD, BatchedTopK, BatchedSign):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -255,12 +255,14 @@ class PSQuantizer(object):
         # gq_rng = "reference": the reference draws r = torch.rand(M) per compressed tensor, in parameter order, from
         # the CPU generator (probabilistic_scalar_compressor.py:23).  torch.rand is one sequential stream, so ONE
         # torch.rand(sum of M) per record (and one per two-phase apply) gives every tensor the same numbers; the
-        # multi-tensor kernels and the per-tensor path both take their slices from it.
+        # multi-tensor kernels and the per-tensor path both take their slices from it.  A ProbabilisticVectorCompressor tensor
+        # draws twice (probabilistic_vector_compressor.py:52 for the codewords, then the level quantiser's): it owns two
+        # consecutive slices in that order (PVQCodec.draw_count).
         self._draw_off, n = {}, 0
         for i, c in enumerate(self.codecs):
             if isinstance(c, HSQCodec) and c.uses_reference_draws():
                 self._draw_off[i] = n
-                n += c.M
+                n += c.draw_count()
         self._draw_total = n
         self._draw_host = None
         self._assembled = {}
@@ -746,7 +748,7 @@ class PSQuantizer(object):
         if draws is None or i not in self._draw_off:
             return {}
         o = self._draw_off[i]
-        return {"r": draws[0][o:o + self.codecs[i].M]}
+        return {"r": draws[0][o:o + self.codecs[i].draw_count()]}
 
     def _decode_all(self, gathered, two_phase, pending=(), plain=False, resets=None, fused_levels=False, phase2_headers=None):
         """Mean of the R = gathered.shape[0] user payloads for every parameter (ps_quantizer.py:47-61),
