@@ -24,6 +24,9 @@ SIGN_SOURCES = ["sign.hip"]
 # the multi-tensor ProbabilisticVectorCompressor encode (include/gq_pvq.h): likewise; it shares the walk with pvq.hip (csrc/pvq_walk.hpp)
 PVQ_LIB = os.path.join(HERE, "libgq_pvq.so")
 PVQ_SOURCES = ["pvq_batched.hip"]
+# the ResidualCompressor's own two launches (include/gq_rq.h): stage 2's multi-tensor encode (the same walk) and the two-stage decode-mean
+RQ_LIB = os.path.join(HERE, "libgq_rq.so")
+RQ_SOURCES = ["rq_batched.hip"]
 SOURCES = ["gq_common.hip", "gq_api.hip", "hsq_encode.hip", "hsq_encode_pf.hip", "hsq_encode_pfd.hip", "hsq_levels.hip", "hsq_batched.hip", "hsq_decode.hip", "qsgd.hip", "qsgd_batched.hip", "qsgd_wide.hip", "pvq.hip"]
 # -ffp-contract=off: the reference's elementwise ops are separately rounded; hipcc's
 # default ("fast") would fuse the decode's mul/add and the level quantiser's sub/div.
@@ -49,10 +52,11 @@ HOST_EXT = os.path.join(HERE, "gq_amd", "_gq_host.so")
 
 def needs_build():
     if (not os.path.exists(LIB) or not os.path.exists(os.path.join(HERE, "libgq_hsq_clock.so")) or not os.path.exists(HOST_EXT)
-            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB) or not os.path.exists(PVQ_LIB)):
+            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB) or not os.path.exists(PVQ_LIB) or not os.path.exists(RQ_LIB)):
         return True
-    t = min(os.path.getmtime(LIB), os.path.getmtime(HOST_EXT), os.path.getmtime(TOPK_LIB), os.path.getmtime(SIGN_LIB), os.path.getmtime(PVQ_LIB))
-    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h", "gq_pvq.h")]
+    t = min(os.path.getmtime(LIB), os.path.getmtime(HOST_EXT), os.path.getmtime(TOPK_LIB), os.path.getmtime(SIGN_LIB), os.path.getmtime(PVQ_LIB),
+            os.path.getmtime(RQ_LIB))
+    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h", "gq_pvq.h", "gq_rq.h")]
             + [__file__])
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -67,6 +71,7 @@ EXTRA = {
     # every score of the f32 MFMA is read by the VALU (two sequential sums per subvector): keep them out of the AGPRs
     "pvq.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "pvq_batched.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    "rq_batched.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 
 
@@ -83,8 +88,8 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd), obj))
-    topk_objs, sign_objs, pvq_objs = [], [], []
-    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs), (PVQ_SOURCES, pvq_objs)):
+    topk_objs, sign_objs, pvq_objs, rq_objs = [], [], [], []
+    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs), (PVQ_SOURCES, pvq_objs), (RQ_SOURCES, rq_objs)):
         for src in srcs:
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
             cmd = [hipcc()] + compile_flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
@@ -96,7 +101,7 @@ def build(force=False, verbose=False):
     for cmd, p, obj in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
-        if obj not in topk_objs and obj not in sign_objs and obj not in pvq_objs:
+        if obj not in topk_objs and obj not in sign_objs and obj not in pvq_objs and obj not in rq_objs:
             objs.append(obj)
     link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
@@ -111,6 +116,7 @@ def build(force=False, verbose=False):
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", TOPK_LIB] + topk_objs)
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SIGN_LIB] + sign_objs)
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PVQ_LIB] + pvq_objs)
+        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", RQ_LIB] + rq_objs)
         build_clock_lib(objs, verbose)
     finally:
         if host is not None and host[1].wait() != 0:     # (always reaped, also when the link above raised)

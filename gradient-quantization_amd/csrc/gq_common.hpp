@@ -89,6 +89,21 @@ __device__ __forceinline__ V mean_div(V x, const MeanDiv &m) {
     return m.pow2 ? x * m.inv : x / m.fR;
 }
 
+// The level quantiser's decode, probabilistic_scalar_compressor.py:31-32: float(l) * (ub - lb) / s + lb, every step rounded on
+// its own.  s = 2^n_bit, so the reference's division by s is an exact scaling: multiplying by inv_s = 2^-n_bit
+// gives the same bits for every input and saves the IEEE division sequence per payload.  (One definition for the decode
+// kernels of libgq_hsq.so and for the residual compressor's second stage, libgq_rq.so, which de-quantises stage 1's norms.)
+template <typename LevelT>
+__device__ __forceinline__ float level_to_norm(LevelT l, float lb, float range, float inv_s) {
+    float t = (float)l * range;
+    t = t * inv_s;
+    return t + lb;
+}
+template <>
+__device__ __forceinline__ float level_to_norm<float>(float l, float, float, float) {
+    return l;  // n_bit == 32: the payload already carries the f32 projection
+}
+
 // a / b for many a and ONE b, correctly rounded, in three operations: y = RN(1/b) is computed once (a true division);
 // q0 = RN(a y) is within an ulp of the quotient, r = a - q0 b is exact in one fma, RN(q0 + r y) is the correctly
 // rounded quotient (Markstein's correction step).  Valid while nothing on the way is subnormal: the caller checks

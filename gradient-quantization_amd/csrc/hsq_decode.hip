@@ -22,18 +22,7 @@ constexpr int DEC_THREADS = 256;
 // of an R = 8 decode).  An odd number of 16-byte units per row spreads the row starts over all positions.
 __host__ __device__ inline int cb_row_stride(int d) { return ((d >> 2) & 1) ? d : d + 4; }
 
-// s = 2^n_bit, so the reference's division by s is an exact scaling: multiplying by inv_s = 2^-n_bit
-// gives the same bits for every input and saves the IEEE division sequence per payload.
-template <typename LevelT>
-__device__ __forceinline__ float level_to_norm(LevelT l, float lb, float range, float inv_s) {
-    float t = (float)l * range;
-    t = t * inv_s;
-    return t + lb;
-}
-template <>
-__device__ __forceinline__ float level_to_norm<float>(float l, float, float, float) {
-    return l;  // n_bit == 32: the payload already carries the f32 projection
-}
+// (level_to_norm -- probabilistic_scalar_compressor.py:31-32 -- is in gq_common.hpp: libgq_rq.so evaluates it too)
 
 // d % 4 == 0: one thread produces 4 consecutive floats (one dwordx4 store).
 template <typename CodeT, typename LevelT, bool LDS_CB>

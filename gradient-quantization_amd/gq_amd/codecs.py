@@ -6,9 +6,10 @@ device memory, through gq_amd.native).
     HSQCodec / QSGDCodec       one tensor per launch (the reference's per-tensor loop, nearest_neighbor_compressor.py:63-90,
                                qsgd_compressor.py:42-71)
     PVQCodec                   ProbabilisticVectorCompressor: HSQCodec's wire, the sampled encode (gq_pvq_encode)
+    ResidualCodec              ResidualCompressor: two HSQ sections back to back, stage 1's and stage 2's
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
-    BatchedHSQ / BatchedPVQ / BatchedQSGD / BatchedTopK / BatchedSign
+    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedSign
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -22,7 +23,7 @@ import torch
 
 from . import exchange, native
 from .compressors import (IdenticalCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor, QSGDCompressor,
-                          SignSGDCompressor, TopKSparsificationCompressor, _next_seed, _require_device)
+                          ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed, _require_device)
 
 
 def _up(x, a=16):
@@ -323,6 +324,123 @@ class PVQCodec(HSQCodec):
         """ONE compress: what travels is what the residual is taken against (ps_quantizer.py:37)."""
         self.encode_into(grad, wire_user, off, salt, r)
         self.decode_wire(wire_user, off, out)
+
+
+class ResidualCodec(object):
+    """ResidualCompressor on the HIP kernels.  Wire per user: stage 1's HSQ section (NearestNeighbor on the gradient), then --
+    16-byte aligned -- stage 2's (the probabilistic vector compressor on what stage 1 leaves), each laid out as HSQCodec lays
+    out codes | levels (or f32 u when n_bit == 32) | lb, ub.  The encode is the launches ResidualCompressor.compress makes,
+    writing into wire views: gq_hsq_encode + levels, stage 1's norms de-quantised, gq_pvq_encode's stage1 form + levels.  The
+    decode is the two-stage decode-mean of libgq_rq.so over a one-row table: per payload (0 + d1) + d2, rounded before it
+    enters the sum over the payloads -- torch.stack([d1, d2]).sum(0) per user, then stack(users).mean(0).
+    Reference draws per compress, in the reference's call order: stage 1's level draws (with args.random and n_bit != 32),
+    stage 2's codeword draws (always), stage 2's level draws (as the first) -- `r` is the runs back to back.
+    Levels travel as bytes or wider, never as packed6 (the stage-2 kernel reads stage 1's levels as they are on the wire).
+    Shapes: the ones libgq_rq.so serves (serves()); every other ResidualCompressor keeps GenericCodec."""
+
+    @staticmethod
+    def serves(compressor):
+        first, second = compressor.compressors
+        return bool(first.dim == second.dim and first.K == second.K and first.code_dtype == second.code_dtype
+                    and native.rq_batched_serves(first.dim, first.K, first.code_dtype))
+
+    def __init__(self, compressor, numel, shape, packed6=False):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        first, second = compressor.compressors
+        self.s1 = HSQCodec(first, numel, shape)
+        self.s2 = PVQCodec(second, numel, shape)
+        assert self.s1.M == self.s2.M and self.s1.level_dtype == self.s2.level_dtype
+        self.M = self.s1.M
+        self.code_dtype, self.level_dtype = self.s1.code_dtype, self.s1.level_dtype
+        self.stage2_off = _up(self.s1.nbytes)
+        self.nbytes = self.stage2_off + self.s2.nbytes
+        self._single = None
+
+    def _level_draws_wanted(self):
+        return self.s2._level_draws_wanted()
+
+    def uses_reference_draws(self):
+        return self.s2.uses_reference_draws()      # stage 2's sampler always draws
+
+    def draw_runs(self):
+        """Which run of M reference draws each consumer takes: (stage 1's levels, stage 2's codewords, stage 2's levels);
+        None: that consumer does not draw."""
+        return (0, 1, 2) if self._level_draws_wanted() else (None, 0, None)
+
+    def draw_count(self):
+        return self.M * (3 if self._level_draws_wanted() else 1)
+
+    def wire_level_kind(self):
+        return self.level_dtype
+
+    def _batched1(self, dev, off):
+        """The launch descriptor of this one tensor at byte `off` of a payload (a one-row table)."""
+        if self._single is None or self._single[0] != (dev, off):
+            first, second = self.c.compressors
+            ntiles = (self.M + 63) // 64
+            tabs = []
+            for cd, o in ((self.s1, off), (self.s2, off + self.stage2_off)):
+                t = torch.zeros((1, 8), dtype=torch.int64)
+                t[0, 1], t[0, 3], t[0, 4], t[0, 5] = self.M, o + cd.codes_off, o + cd.levels_off, o + cd.lbub_off
+                tabs.append(t.view(-1).to(dev))
+            cb1, (cb2, cdag) = first._codebook_on(dev), second._on(dev)
+            n_bit = first.n_bit if first.compressed_norm else 32
+            batch = native.RQBatch(tabs[0], tabs[1], torch.zeros(ntiles, dtype=torch.int32, device=dev), 1, ntiles, cb1, cb2, cdag,
+                                   self.code_dtype, self.level_dtype, n_bit)
+            self._single = ((dev, off), batch)
+        return self._single[1]
+
+    def encode_into(self, grad, wire_user, off, salt, r=None):
+        _require_device(grad, "ResidualCodec.encode_into")
+        dev = grad.device
+        first, second = self.c.compressors
+        flat = grad.contiguous().view(-1)
+        M = self.M
+        runs = self.draw_runs()
+        take = lambda k: None if (r is None or runs[k] is None) else r[runs[k] * M:(runs[k] + 1) * M]
+        self.s1.encode_into(flat, wire_user, off, salt, take(0))
+        codes1, levels1, lb_ub1 = self.s1._views(wire_user, off)
+        # stage 1's norms as the compressor de-quantises them (probabilistic_scalar_compressor.py:31-32); n_bit == 32: f32 u as it travels
+        norm1 = first.norm_compressor.decompress((lb_ub1[0], lb_ub1[1], levels1)) if first.compressed_norm else levels1
+        codes2, levels2, lb_ub2 = self.s2._views(wire_user, off + self.stage2_off)
+        _, cdag = second._on(dev)
+        u, partials = self.s2._scratch(dev)
+        if not second.compressed_norm:
+            u = levels2      # the `levels` section holds f32 u
+        if second._rng == "reference":
+            r_code = take(1)
+            if r_code is None:       # the compressor's own order: its codeword draws here, its level draws in _levels
+                r_code = torch.rand(M).to(dev)
+            native.pvq_encode_residual(flat, codes1, norm1, first._codebook_on(dev), cdag, codes2, u, partials, native.RANDOM_GIVEN, r_code, 0)
+        else:
+            native.pvq_encode_residual(flat, codes1, norm1, first._codebook_on(dev), cdag, codes2, u, partials, native.RANDOM_DEVICE, None,
+                                       _next_seed() ^ salt)
+        if second.compressed_norm:
+            self.s2._levels(u, partials, levels2, lb_ub2, salt, take(2))
+
+    def decode_wire(self, wire_user, off, out):
+        """Decode this user's own payload (error feedback residual): the plain decompress, (0 + d1) + d2."""
+        self._decode(wire_user.view(1, -1), off, 1, out, plain=True)
+
+    def encode_decode_into(self, grad, wire_user, off, salt, out, r=None):
+        """ONE compress: what travels is what the residual is taken against (ps_quantizer.py:37)."""
+        self.encode_into(grad, wire_user, off, salt, r)
+        self.decode_wire(wire_user, off, out)
+
+    def _decode(self, gathered, off, R, out, plain=False):
+        self._batched1(gathered.device, off).decode(gathered, R, out.view(-1), plain=plain)
+
+    def roundtrip(self, grad, salt, r=None):
+        dev = grad.device
+        tmp = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(self.numel, dtype=torch.float32, device=dev)
+        self.encode_decode_into(grad, tmp, 0, salt, out, r)
+        return out.view(self.shape)
+
+    def decode_mean(self, gathered, off, R, plain=False):
+        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        self._decode(gathered, off, R, out, plain=plain)
+        return out.view(self.shape)
 
 
 class QSGDCodec(object):
@@ -1013,6 +1131,167 @@ class BatchedPVQ(BatchedHSQ):
         self._batch.encode(wire_user, ef, mode, seed, r_flat)
 
 
+class BatchedResidual(BatchedHSQ):
+    """Every ResidualCompressor tensor of a model in four launches per record and one per apply, on BatchedHSQ's tables, header,
+    draws and graph machinery.  Two descriptors over one tile space (native.RQBatch): stage 1's, whose table carries the
+    pointers, and stage 2's, whose table holds layout only and never changes.  Per record: gq_hsq_encode_batched (with error
+    feedback: v = grad + scale * error over grad), gq_hsq_levels_batched (+ the dense tensors' copy), gq_rq_encode2_batched --
+    the PVQ walk over v - decode(stage 1), stage 1 read from the wire --, gq_hsq_levels_batched over stage 2; with error feedback
+    a fifth launch leaves error = v - ((0 + d1) + d2), the reference's rounding (stage 1's fused residual would be v - d1).  Per
+    apply: gq_rq_decode_sum_batched.  The header carries both stages' (min, max) accumulators behind the table.
+    Draws: "reference" -- the quantizer's one torch.rand per record gives a tensor up to three runs (ResidualCodec.draw_runs);
+    "device" -- the three consumers draw from three streams of the group's { seed, step } words (stage 2's level launch reads
+    the words stage 2's encode derives for it); "keyed" as BatchedPVQ."""
+
+    takes_tail = False
+
+    @staticmethod
+    def eligible(codec):
+        if type(codec) is not ResidualCodec:
+            return False
+        first = codec.c.compressors[0]
+        return first.K != first.dim      # K == d: a random codebook per tensor
+
+    @staticmethod
+    def group_key(codec):
+        first = codec.c.compressors[0]
+        return ("rq", first.dim, first.K, _esize(codec.code_dtype), _esize(codec.level_dtype), int(first.n_bit))
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        self.idxs = list(idxs)
+        self.codecs = [codecs[i] for i in self.idxs]
+        cd0 = self.codecs[0]
+        first, second = cd0.c.compressors
+        self.n_bit = first.n_bit
+        self.random = bool(first.compressed_norm and first.norm_compressor.random)
+        self.keyed = second._rng == "keyed"
+        self.counter = second._rng == "device"       # (also without stochastic levels: the sampler's draws)
+        self.reference_draws = cd0.uses_reference_draws()
+        self.level_reference = bool(self.random and second._rng == "reference")
+        self.draw_runs = cd0.draw_runs()
+        self._r_gather = {}
+        self.codebook = first._codebook_on(device)
+        self.codebook2, self.c_dagger = second._on(device)
+        if self.codebook2.shape == self.codebook.shape and torch.equal(self.codebook2, self.codebook):
+            self.codebook2 = self.codebook      # one file behind both classes: the decode stages ONE image
+        nseg = len(self.idxs)
+        table = torch.zeros((nseg, 8), dtype=torch.int64)
+        table2 = torch.zeros((nseg, 8), dtype=torch.int64)
+        tile_seg = []
+        tile, out_off = 0, 0
+        self.out_off = []
+        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
+            ntile = (cd.M + 63) // 64
+            for tab, st, o in ((table, cd.s1, offsets[i]), (table2, cd.s2, offsets[i] + cd.stage2_off)):
+                tab[s, 1], tab[s, 2] = cd.M, tile
+                tab[s, 3], tab[s, 4], tab[s, 5] = o + st.codes_off, o + st.levels_off, o + st.lbub_off
+                tab[s, 6] = out_off
+            tile_seg += [s] * ntile
+            tile += ntile
+            self.out_off.append(out_off)
+            out_off += cd.numel
+        self.ntiles, self.out_floats = tile, out_off
+        self.tile_seg = torch.tensor(tile_seg, dtype=torch.int32, device=device)
+        self._item_seg, self._nitems = self.tile_seg, tile
+        init = torch.empty((2 * nseg, 2), dtype=torch.int32)      # stage 1's accumulators, then stage 2's
+        init[:, 0], init[:, 1] = -1, 0            # 0xFFFFFFFF / 0: identities of the mapped min / max
+        self._setup(table, init.view(torch.int64), device, slots, user_bytes, dense)
+        self._layout2 = table2.clone()
+        self._table2 = table2.view(-1).to(device)
+        self.u_flat = torch.empty(self.ntiles * 64, dtype=torch.float32, device=device)
+        self.u_flat2 = torch.empty(self.ntiles * 64, dtype=torch.float32, device=device)
+        self.level2_words = torch.zeros(2, dtype=torch.int64, device=device)
+        self.code_dtype, self.level_dtype = cd0.code_dtype, cd0.level_dtype
+        self.align = 16
+        self.ws = native.new_workspace(device, self.ntiles * 64)
+        acc = self._dev[self._table_words:self._dense_at].view(torch.int32)
+        self._batch = native.RQBatch(self._dev[:self._table_words], self._table2, self.tile_seg, self.nseg, self.ntiles, self.codebook,
+                                     self.codebook2, self.c_dagger, self.code_dtype, cd0.wire_level_kind(), self.n_bit,
+                                     self.u_flat, acc[:2 * nseg], self.ws, self.u_flat2, acc[2 * nseg:], self.level2_words)
+        self.profile_slot = -1
+
+    LEVEL2_SALT = 0x9FB21C651E98DF25      # stage 2's level launch where the host picks the seed (keyed draws)
+
+    def graphable(self):
+        return (self.keyed or (self.counter and self.rng_pairs is not None)) and not self.reference_draws and self._batch.path != 0
+
+    def fusable_levels(self):
+        return False
+
+    def _draws_for(self, consumer, salt, counter_seed, draws):
+        """(random_mode, seed, r_flat) of consumer 0 (stage 1's levels), 1 (stage 2's codewords) or 2 (stage 2's levels)."""
+        if consumer != 1 and (self.n_bit == 32 or not self.random):
+            return native.RANDOM_OFF, 0, None
+        if self.reference_draws:
+            return native.RANDOM_GIVEN, 0, self._given_draws(draws, self.draw_runs[consumer])
+        if self.keyed:
+            seed = (salt * 0x2545F4914F6CDD1D + 0x5851F42D4C957F2D) & (2 ** 63 - 1)
+            return native.RANDOM_DEVICE_KEYED, (seed ^ self.LEVEL2_SALT) if consumer == 2 else seed, None
+        if self.counter and counter_seed is not None:
+            # (the encode salts the words' seed itself and leaves stage 2's level launch a seed of its own in level2_words)
+            return native.RANDOM_DEVICE_COUNTER, self._batch.level2_seed if consumer == 2 else counter_seed, None
+        return native.RANDOM_DEVICE, _next_seed() ^ salt, None
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, skip_levels=False, table_current=False):
+        """BatchedHSQ.encode's contract (header, capture, error feedback) over the residual compressor's launches."""
+        assert not skip_levels, "the fused level + decode launch is BatchedHSQ's (fusable_levels)"
+        if self.reference_draws and draws is None:
+            return False
+        if self._batch.path == 0:
+            return False
+        if graph_header is not None:
+            self._graph_tables(graph_header, dense)
+        elif table_current:
+            self._batch.set_table(self._dev[:self._table_words])
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        elif not self._upload(tensors, slot, self.align, errs, dense):
+            return False
+        else:
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+            self._acc_clean = False
+        ef = ef_scale if errs is not None else None
+        counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
+        b = self._batch
+        try:
+            b.b1.encode(wire_user, ef)
+            mode, seed, r_flat = self._draws_for(0, salt, counter_seed, draws)
+            b.b1.levels(wire_user, mode, seed, r_flat)
+            mode, seed, r_flat = self._draws_for(1, salt, counter_seed, draws)
+            b.encode2(wire_user, mode, seed, r_flat)
+            mode, seed, r_flat = self._draws_for(2, salt, counter_seed, draws)
+            b.b2.levels(wire_user, mode, seed, r_flat)
+            if errs is not None:      # error = v - ((0 + d1) + d2)  (ps_quantizer.py:37-39)
+                b.decode(wire_user.view(1, -1), 1, None, mode=native.RQ_ERROR)
+        except BaseException:
+            if graph_header is not None:
+                self.graph_tables_abort()
+            raise
+        if graph_header is not None:
+            self._graph_tables_done(defer_reset)
+        return True
+
+    def _range(self, lo, hi):
+        if lo >= hi:
+            return None
+        ent = self._parts.get((lo, hi))
+        if ent is None:
+            i_lo = int(self._layout[lo, 2])
+            i_hi = int(self._layout[hi, 2]) if hi < self.nseg else self._nitems
+            if lo == 0:
+                ent = self._batch.part(self._dev[:self._table_words], self._table2, self._item_seg, hi, i_hi)
+            else:
+                tabs = []
+                for lay in (self._layout, self._layout2):
+                    tab = lay[lo:hi].clone()
+                    tab[:, 2] -= i_lo
+                    tabs.append(tab.view(-1).to(self.device))
+                items = (self._item_seg[i_lo:i_hi] - lo).contiguous()
+                ent = self._batch.part(tabs[0], tabs[1], items, hi - lo, i_hi - i_lo)
+            self._parts[(lo, hi)] = ent
+        return ent
+
+
 class BatchedQSGD(_BatchedBase):
     """All packed-form QSGD tensors in ONE gq_qsgd_compress_batched / gq_qsgd_decode_sum_batched launch.
     Tensors with WIDE buckets (TernGrad's `--c-dim 0`: the tensor is one bucket; any bucket of WIDE_MIN elements
@@ -1349,3 +1628,12 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, SignSGDCompressor):
         return SignCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
+
+
+def quantizer_codec_factory(compressor, numel, shape, packed6=False):
+    """What PSQuantizer / RingQuantizer use when the caller names no factory: default_codec_factory, and the two-section wire
+    for a ResidualCompressor of a shape libgq_rq.so serves.  (default_codec_factory itself still answers GenericCodec for that
+    class -- tests/test_pvq_host.py pins it --, so the choice is made here, where the quantizers ask.)"""
+    if isinstance(compressor, ResidualCompressor) and ResidualCodec.serves(compressor):
+        return ResidualCodec(compressor, numel, shape, packed6)
+    return default_codec_factory(compressor, numel, shape, packed6)

@@ -33,7 +33,7 @@ import torch.optim as optim
 
 from .datasets import OnDiskClassification
 from .compressors import (IdenticalCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor, QSGDCompressor,
-                          SignSGDCompressor, TopKSparsificationCompressor)
+                          ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
 quantizer_choices = {          # main.py:20-26
@@ -43,6 +43,7 @@ quantizer_choices = {          # main.py:20-26
     'sign': SignSGDCompressor,
     'topk': TopKSparsificationCompressor,
     'pvq': ProbabilisticVectorCompressor,      # the unbiased vector quantiser (not in main.py's table: INTEGRATION.md)
+    'rq': ResidualCompressor,                  # two stages: hsq, then pvq on what it leaves (not in main.py's table either)
 }
 
 

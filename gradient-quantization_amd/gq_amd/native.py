@@ -837,3 +837,105 @@ class PVQBatch(HSQBatch):
         rc = self.PL.gq_pvq_encode_batched(self.pref, self._wire(wire), ctypes.c_int(random_mode), ctypes.c_uint64(seed & (2 ** 64 - 1)), rp,
                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale), _stream())
         _check_pvq(rc, "gq_pvq_encode_batched")
+
+
+# ---- the ResidualCompressor's own launches: libgq_rq.so (include/gq_rq.h) ---------------------------------------------------
+RQ_LIB_PATH = os.environ.get("GQ_RQ_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_rq.so")
+RQ_ABI_VERSION = 1
+RQ_EXPORTS = ["gq_rq_abi_version", "gq_rq_last_error", "gq_rq_batched_serves", "gq_rq_encode2_batched", "gq_rq_decode_sum_batched"]
+RQ_MEAN, RQ_PLAIN, RQ_ERROR = 0, 1, 2      # GQ_RQ_* of include/gq_rq.h
+
+_rq_lib = None
+
+
+def rq_lib():
+    """Load libgq_rq.so; fail loudly if it was not built (as lib())."""
+    global _rq_lib
+    if _rq_lib is None:
+        if not os.path.exists(RQ_LIB_PATH):
+            raise GQNativeError("libgq_rq.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                "(there is no CPU fallback)" % RQ_LIB_PATH)
+        L = ctypes.CDLL(RQ_LIB_PATH)
+        L.gq_rq_last_error.restype = ctypes.c_char_p
+        L.gq_rq_abi_version.restype = ctypes.c_int
+        for name in RQ_EXPORTS:
+            getattr(L, name)
+        if L.gq_rq_abi_version() != RQ_ABI_VERSION:
+            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
+                                % (RQ_LIB_PATH, L.gq_rq_abi_version(), RQ_ABI_VERSION))
+        _rq_lib = L
+    return _rq_lib
+
+
+def _check_rq(rc, what):
+    CALLS[0] += 1
+    if rc != 0:
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, rq_lib().gq_rq_last_error().decode()))
+
+
+def rq_batched_serves(d, K, code_dtype):
+    """True when libgq_rq.so serves the shape: d in {8, 16, 32}, K = 32 ... 256 in whole blocks of 32, byte codes (the host-side
+    rule of gq_rq_batched_serves, which is gq_pvq_batched_serves'; no library needed to ask)."""
+    return pvq_batched_serves(d, K, code_dtype)
+
+
+class _RQBatchStruct(ctypes.Structure):      # gq_rq_batch (include/gq_rq.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("stage1", ctypes.c_void_p), ("stage2", ctypes.c_void_p),
+                ("c_dagger", ctypes.c_void_p), ("level2_words", ctypes.c_void_p)]
+
+
+class RQBatch(object):
+    """The multi-tensor launches of one group of ResidualCompressor tensors: two HSQBatch descriptors over one tile space --
+    `b1` over stage 1's sections (its table carries the gradient and error pointers, the dense copies ride in its level launch),
+    `b2` over stage 2's -- and the gq_rq_batch that names both.  Stage 1's encode and the two level launches are libgq_hsq.so's;
+    encode2 and decode are libgq_rq.so's."""
+
+    def __init__(self, seg_table, seg_table2, tile_seg, nseg, ntiles, codebook1, codebook2, c_dagger, code_dtype, level_dtype, n_bit,
+                 u_flat1=None, seg_minmax1=None, workspace1=None, u_flat2=None, seg_minmax2=None, level2_words=None):
+        self.RL = rq_lib()
+        self.b1 = HSQBatch(seg_table, tile_seg, nseg, ntiles, codebook1, code_dtype, level_dtype, n_bit, u_flat1, seg_minmax1, workspace1)
+        self.b2 = HSQBatch(seg_table2, tile_seg, nseg, ntiles, codebook2, code_dtype, level_dtype, n_bit, u_flat2, seg_minmax2, None)
+        assert c_dagger.shape == codebook2.shape == codebook1.shape
+        self.keep = (c_dagger, level2_words, code_dtype, level_dtype, n_bit)
+        self.device = self.b1.device
+        self.s = _RQBatchStruct(ctypes.sizeof(_RQBatchStruct), 0, ctypes.addressof(self.b1.s), ctypes.addressof(self.b2.s),
+                                _dev_ptr(c_dagger, torch.float32, "c_dagger").value,
+                                _dev_ptr(level2_words, torch.int64, "level2_words").value if level2_words is not None else None)
+        self.ref = ctypes.byref(self.s)
+        self.level2_seed = level2_words.data_ptr() if level2_words is not None else None
+        serves = self.RL.gq_rq_batched_serves(ctypes.c_int(self.b1.s.d), ctypes.c_int(self.b1.s.K), ctypes.c_int(self.b1.s.code_bytes))
+        self.path = self.b1.path if (serves and self.b2.path) else 0
+
+    def set_table(self, seg_table):
+        """Stage 1's table (the one with the pointers) for the launches that follow; stage 2's holds layout only and stays."""
+        self.b1.set_table(seg_table)
+
+    def set_dense(self, dense_table, ndense):
+        self.b1.set_dense(dense_table, ndense)
+
+    def part(self, seg_table, seg_table2, tile_seg, nseg, ntiles):
+        """The same configuration over other tables (the head / tail of a split decode)."""
+        c_dagger, _, code_dtype, level_dtype, n_bit = self.keep
+        return RQBatch(seg_table, seg_table2, tile_seg, nseg, ntiles, self.b1.keep[2], self.b2.keep[2], c_dagger, code_dtype, level_dtype, n_bit)
+
+    def encode2(self, wire, random_mode, seed, r_flat=None):
+        """Stage 2's codes into `wire`, u into stage 2's u_flat, (min, max) into its seg_minmax -- behind stage 1's encode and
+        levels for the same wire.  One draw per subvector: r_flat (RANDOM_GIVEN, laid out like u_flat) or in-kernel from `seed`
+        (salted: a level launch may be given the same seed).  RANDOM_DEVICE_COUNTER: the launch also leaves the seed of stage
+        2's level launch in level2_words (`level2_seed` is their address)."""
+        rp = _dev_ptr(r_flat, torch.float32, "r_flat") if r_flat is not None else ctypes.c_void_p(0)
+        rc = self.RL.gq_rq_encode2_batched(self.ref, self.b1._wire(wire), ctypes.c_int(random_mode), ctypes.c_uint64(seed & (2 ** 64 - 1)), rp,
+                                           _stream())
+        _check_rq(rc, "gq_rq_encode2_batched")
+
+    def decode(self, gathered, R, out, plain=False, mode=None):
+        """Mean of the R payloads, each (0 + d1) + d2 (plain: the decompress of ONE payload).  mode = RQ_ERROR (one payload):
+        error = v - decoded into the error buffers of stage 1's table instead; `out` may be None."""
+        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
+        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
+        if mode is None:
+            mode = RQ_PLAIN if (plain and R == 1) else RQ_MEAN
+        op = _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0)
+        rc = self.RL.gq_rq_decode_sum_batched(self.ref, self.b1._wire(gathered), ctypes.c_int64(stride), ctypes.c_int(R), op,
+                                              ctypes.c_int(mode), _stream())
+        _check_rq(rc, "gq_rq_decode_sum_batched")

@@ -46,8 +46,10 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedHSQ, BatchedPVQ, BatchedQSGD, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec, SignCodec, TopKCodec,
+    BatchedHSQ, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec,
+    ResidualCodec, SignCodec, TopKCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
+    quantizer_codec_factory,
     wire_levels_mode)
 
 
@@ -172,7 +174,7 @@ class PSQuantizer(object):
         self.error_feedback = args.ef
         self.two_phase = args.two_phase
         self.process_group = process_group
-        factory = codec_factory or default_codec_factory
+        factory = codec_factory or quantizer_codec_factory
         self.aggregate_fma = aggregate_fma(args)     # opt-in fused accumulation of the decode-mean (R >= 2 only)
         self.wire_levels = wire_levels_mode(args, _dist_world(process_group)[0])      # "bytes" | "packed6" (6-bit levels where the configuration allows)
         if self.wire_levels == "packed6":
@@ -217,7 +219,7 @@ class PSQuantizer(object):
         self._step_tail = os.environ.get("GQ_STEP_TAIL", "1") != "0"       # (see _decode_all)
         self._fuse_levels = os.environ.get("GQ_FUSE_LEVELS", "1") != "0"   # (see _can_fuse_levels)
         BatchedQSGD.place_lone_buckets(self.codecs)
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedQSGD, BatchedTopK, BatchedSign):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, BatchedTopK, BatchedSign):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -257,10 +259,11 @@ class PSQuantizer(object):
         # torch.rand(sum of M) per record (and one per two-phase apply) gives every tensor the same numbers; the
         # multi-tensor kernels and the per-tensor path both take their slices from it.  A ProbabilisticVectorCompressor tensor
         # draws twice (probabilistic_vector_compressor.py:52 for the codewords, then the level quantiser's): it owns two
-        # consecutive slices in that order (PVQCodec.draw_count).
+        # consecutive slices in that order (PVQCodec.draw_count); a ResidualCompressor tensor up to three: stage 1's level draws,
+        # stage 2's codeword draws, stage 2's level draws (residual_compressor.py:17-24; ResidualCodec.draw_runs).
         self._draw_off, n = {}, 0
         for i, c in enumerate(self.codecs):
-            if isinstance(c, HSQCodec) and c.uses_reference_draws():
+            if isinstance(c, (HSQCodec, ResidualCodec)) and c.uses_reference_draws():
                 self._draw_off[i] = n
                 n += c.draw_count()
         self._draw_total = n
@@ -982,7 +985,7 @@ def _ring_codec_factory(compressor, numel, shape, packed6=False):
     SignSGD's 2-bit wire among them, which carries the decoded tensor exactly (torch.sign yields no -0 and no NaN)."""
     if isinstance(compressor, TopKSparsificationCompressor):
         return GenericCodec(compressor, numel, shape)
-    return default_codec_factory(compressor, numel, shape, packed6)
+    return quantizer_codec_factory(compressor, numel, shape, packed6)
 
 
 class RingQuantizer(PSQuantizer):
