@@ -27,6 +27,9 @@ PVQ_SOURCES = ["pvq_batched.hip"]
 # the ResidualCompressor's own two launches (include/gq_rq.h): stage 2's multi-tensor encode (the same walk) and the two-stage decode-mean
 RQ_LIB = os.path.join(HERE, "libgq_rq.so")
 RQ_SOURCES = ["rq_batched.hip"]
+# Maurey sparsification on a sparse wire (include/gq_maurey.h): the sampler's six launches and the decode-mean
+MAUREY_LIB = os.path.join(HERE, "libgq_maurey.so")
+MAUREY_SOURCES = ["maurey.hip"]
 SOURCES = ["gq_common.hip", "gq_api.hip", "hsq_encode.hip", "hsq_encode_pf.hip", "hsq_encode_pfd.hip", "hsq_levels.hip", "hsq_batched.hip", "hsq_decode.hip", "qsgd.hip", "qsgd_batched.hip", "qsgd_wide.hip", "pvq.hip"]
 # -ffp-contract=off: the reference's elementwise ops are separately rounded; hipcc's
 # default ("fast") would fuse the decode's mul/add and the level quantiser's sub/div.
@@ -52,11 +55,12 @@ HOST_EXT = os.path.join(HERE, "gq_amd", "_gq_host.so")
 
 def needs_build():
     if (not os.path.exists(LIB) or not os.path.exists(os.path.join(HERE, "libgq_hsq_clock.so")) or not os.path.exists(HOST_EXT)
-            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB) or not os.path.exists(PVQ_LIB) or not os.path.exists(RQ_LIB)):
+            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB) or not os.path.exists(PVQ_LIB) or not os.path.exists(RQ_LIB)
+            or not os.path.exists(MAUREY_LIB)):
         return True
     t = min(os.path.getmtime(LIB), os.path.getmtime(HOST_EXT), os.path.getmtime(TOPK_LIB), os.path.getmtime(SIGN_LIB), os.path.getmtime(PVQ_LIB),
-            os.path.getmtime(RQ_LIB))
-    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h", "gq_pvq.h", "gq_rq.h")]
+            os.path.getmtime(RQ_LIB), os.path.getmtime(MAUREY_LIB))
+    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h", "gq_pvq.h", "gq_rq.h", "gq_maurey.h")]
             + [__file__])
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -88,8 +92,9 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd), obj))
-    topk_objs, sign_objs, pvq_objs, rq_objs = [], [], [], []
-    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs), (PVQ_SOURCES, pvq_objs), (RQ_SOURCES, rq_objs)):
+    topk_objs, sign_objs, pvq_objs, rq_objs, maurey_objs = [], [], [], [], []
+    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs), (PVQ_SOURCES, pvq_objs), (RQ_SOURCES, rq_objs),
+                      (MAUREY_SOURCES, maurey_objs)):
         for src in srcs:
             obj = os.path.join(objdir, src.replace(".hip", ".o"))
             cmd = [hipcc()] + compile_flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
@@ -101,7 +106,7 @@ def build(force=False, verbose=False):
     for cmd, p, obj in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
-        if obj not in topk_objs and obj not in sign_objs and obj not in pvq_objs and obj not in rq_objs:
+        if obj not in topk_objs and obj not in sign_objs and obj not in pvq_objs and obj not in rq_objs and obj not in maurey_objs:
             objs.append(obj)
     link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
     if verbose:
@@ -117,6 +122,7 @@ def build(force=False, verbose=False):
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SIGN_LIB] + sign_objs)
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PVQ_LIB] + pvq_objs)
         subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", RQ_LIB] + rq_objs)
+        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", MAUREY_LIB] + maurey_objs)
         build_clock_lib(objs, verbose)
     finally:
         if host is not None and host[1].wait() != 0:     # (always reaped, also when the link above raised)

@@ -9,7 +9,8 @@ device memory, through gq_amd.native).
     ResidualCodec              ResidualCompressor: two HSQ sections back to back, stage 1's and stage 2's
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
-    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedSign
+    MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
+    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedSign / BatchedMaurey
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -22,8 +23,9 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (IdenticalCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor, QSGDCompressor,
-                          ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed, _require_device)
+from .compressors import (IdenticalCompressor, MaureySparsification, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed,
+                          _require_device)
 
 
 def _up(x, a=16):
@@ -631,6 +633,74 @@ class SignCodec(object):
         out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
         tmp = torch.empty(max(16, self.nbytes), dtype=torch.uint8, device=grad.device)
         self.encode_decode_into(grad, tmp, 0, salt, out)
+        return out.view(self.shape)
+
+    def decode_wire(self, wire_user, off, out):
+        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
+
+    def _decode_rows(self, gathered, off, R, out, plain=False):
+        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
+
+    def decode_mean(self, gathered, off, R, plain=False):
+        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        self._decode_rows(gathered, off, R, out, plain=plain)
+        return out.view(self.shape)
+
+
+class MaureyCodec(object):
+    """MaureySparsification on the HIP kernels (libgq_maurey.so).  Wire per tensor: a 16-byte header (scale = ||w||_1 / k as
+    f32, 12 zero bytes), then k little-endian uint32 words  index | (w_index < 0) << 31, ascending by index (an index drawn m
+    times appears m times), zero padding to 16 bytes -- 16 + _up(4k) bytes.  Every call is a one-tensor BatchedMaurey; roundtrip /
+    encode_decode_into return the compress launches' own dense decode.
+    The draws, by the compressor's gq_rng: "device" -- the library's counter-based generator, a fresh seed per call (the
+    multi-tensor launches key theirs by the quantizer's { seed, step } words); "reference" -- torch.rand(k) per tensor from the
+    CPU generator, in parameter order, handed to the kernels as given draws.  That is ONE uniform per draw, not the reference's
+    k x n matrix (maurey_sparsification.py:28), so the draws are not the reference's; "keyed" draws like "device".
+    `r` (float32 [k] on the device) hands a call its uniforms whatever the mode; `seed` pins the device generator's."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.k = int(compressor.k)
+        if self.k < 1 or not 1 <= numel < 2 ** 31:
+            raise ValueError("MaureyCodec: k = %d draws for a tensor of %d elements" % (self.k, numel))
+        self.nbytes = native.MAUREY_HEADER_BYTES + _up(4 * self.k)
+        self._rng = getattr(compressor, "_rng", "device")
+        self._single = None
+
+    def uses_reference_draws(self):
+        return self._rng == "reference"
+
+    def draw_count(self):
+        return self.k
+
+    def _batched1(self, dev):
+        if self._single is None or self._single.device != dev:
+            self._single = BatchedMaurey([self], [0], [0], dev, 1, self.nbytes)
+        return self._single
+
+    def _draws(self, r, dev):
+        if r is None and self.uses_reference_draws():
+            r = torch.rand(self.k).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
+        return (r, {0: 0}) if r is not None else None
+
+    def encode_decode_into(self, grad, wire_user, off, salt, out, r=None, seed=None):
+        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch sequence."""
+        _require_device(grad, "MaureyCodec.encode_decode_into")
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt, draws=self._draws(r, flat.device), out=out.view(-1),
+                                                seed=seed)
+        assert ok, "MaureyCodec: the gradient must be a float32 tensor on the current device"
+
+    def encode_into(self, grad, wire_user, off, salt, r=None, seed=None):
+        _require_device(grad, "MaureyCodec.encode_into")
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt, draws=self._draws(r, flat.device), seed=seed)
+        assert ok, "MaureyCodec: the gradient must be a float32 tensor on the current device"
+
+    def roundtrip(self, grad, salt, r=None, seed=None):
+        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
+        tmp = torch.empty(self.nbytes, dtype=torch.uint8, device=grad.device)
+        self.encode_decode_into(grad, tmp, 0, salt, out, r=r, seed=seed)
         return out.view(self.shape)
 
     def decode_wire(self, wire_user, off, out):
@@ -1614,6 +1684,137 @@ class BatchedSign(_BatchedBase):
         return views
 
 
+class BatchedMaurey(_BatchedBase):
+    """All MaureySparsification tensors in ONE gq_maurey_compress_batched sequence (six launches: item sums, their scan, the
+    draws counted, the counts' scan, the draws bucketed, the per-item placement -- include/gq_maurey.h) and ONE
+    gq_maurey_decode_sum_batched launch.  Tensor s owns the draws [first draw, first draw + k) of the group's stream.  The compress
+    also writes the dense decoded tensors where a caller asks for them: error feedback takes its residual from them and the
+    two-phase re-compress returns them.  gq_rng "device" with the quantizer's { seed, step } pairs: nothing in the launches changes
+    from record to record, they replay from a HIP graph and draw afresh every step; "reference": the quantizer's draw plan
+    (torch.rand(k) per tensor, in parameter order) as given draws; "keyed" / a group without pairs: a fresh seed per call."""
+
+    takes_tail = False
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is MaureyCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec._rng,)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        self.idxs = list(idxs)
+        self.codecs = [codecs[i] for i in self.idxs]
+        nseg = len(self.idxs)
+        chunk = native.MAUREY_CHUNK
+        table = torch.zeros((nseg, 8), dtype=torch.int64)
+        item_seg = []
+        item, out_off, draw = 0, 0, 0
+        self.out_off = []
+        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
+            items = -(-cd.numel // chunk)
+            table[s, 1], table[s, 2], table[s, 3], table[s, 4], table[s, 5], table[s, 6] = cd.numel, item, offsets[i], cd.k, out_off, draw
+            item_seg += [s] * items
+            item += items
+            draw += cd.k
+            self.out_off.append(out_off)
+            out_off += -(-cd.numel // 4) * 4      # (16-byte aligned views)
+        self.out_floats, self.ndraws = out_off, draw
+        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
+        self._item_seg, self._nitems = self.item_seg, item
+        self._setup(table, None, device, slots, user_bytes, dense)
+        self.align = 4
+        rng = self.codecs[0]._rng
+        self.random = True
+        self.counter = rng == "device"          # the quantizer gives such a group its { seed, step } pairs (PSQuantizer._make_group)
+        self.reference_draws = rng == "reference"
+        # the sampler's scratch (include/gq_maurey.h): nothing in it has to be zero, every launch sequence rewrites what it reads
+        self._sums = torch.empty(item * 4, dtype=torch.float64, device=device)
+        self._totals = torch.empty(nseg, dtype=torch.float64, device=device)
+        self._counts = torch.empty(item * 3, dtype=torch.int32, device=device)
+        self._draw_item = torch.empty(draw, dtype=torch.int32, device=device)
+        self._bucket = torch.empty(draw, dtype=torch.float32, device=device)
+        self._r_gather = None
+        self._ef_out = None         # the decoded tensors an error-feedback record needs and nobody asked for
+        self._batch = native.MaureyBatch(self._dev[:self._table_words], self.item_seg, nseg, item, draw, self._sums, self._totals,
+                                         self._counts, self._draw_item, self._bucket)
+
+    def graphable(self):
+        """As BatchedPVQ.graphable: only the draws keyed by the device step words leave every launch argument unchanged."""
+        return self.counter and self.rng_pairs is not None and not self.reference_draws
+
+    def _given_draws(self, draws):
+        """draws = (r_all on the device, {parameter index: offset of its k draws}) -> float32 [ndraws] in the group's layout (every
+        tensor's draws at its first draw), one gather through an index built once (as BatchedHSQ._given_draws)."""
+        r_all, offsets = draws
+        if self._r_gather is None:
+            idx = torch.cat([torch.arange(offsets[i], offsets[i] + cd.k) for i, cd in zip(self.idxs, self.codecs)])
+            self._r_gather = (idx.to(self.device), torch.empty(self.ndraws, dtype=torch.float32, device=self.device))
+        torch.index_select(r_all, 0, self._r_gather[0], out=self._r_gather[1])
+        return self._r_gather[1]
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None, seed=None):
+        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
+        feedback in the same launches (t += ef_scale*err before the sums, err = t - decoded in the last launch, both in place).
+        draws (given uniforms, see _given_draws): required for gq_rng "reference", taken in any mode when handed in.
+        seed: the device generator's seed for this call.  graph_header, dense, table_current, rng_slot: see BatchedHSQ.encode."""
+        given = draws is not None and all(i in draws[1] for i in self.idxs)
+        if self.reference_draws and not given:
+            return False
+        if graph_header is not None:
+            self._graph_tables(graph_header, dense)
+        elif table_current:
+            self._batch.set_table(self._dev[:self._table_words])
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        elif not self._upload(tensors, slot, self.align, errs, dense):
+            return False
+        else:
+            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        ef = ef_scale if errs is not None else None
+        if ef is not None and out is None:
+            if self._ef_out is None or self._ef_out.device != wire_user.device:
+                self._ef_out = torch.empty(self.out_floats, dtype=torch.float32, device=wire_user.device)
+            out = self._ef_out
+        counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
+        if given:
+            mode, sd, r = native.RANDOM_GIVEN, 0, self._given_draws(draws)
+        elif seed is not None:
+            mode, sd, r = native.RANDOM_DEVICE, int(seed), None
+        elif self.counter and counter_seed is not None:
+            mode, sd, r = native.RANDOM_DEVICE_COUNTER, counter_seed, None
+        else:
+            mode, sd, r = native.RANDOM_DEVICE, _next_seed() ^ salt, None
+        try:
+            self._batch.compress(wire_user, mode, sd, r, out, ef)
+        except BaseException:
+            if graph_header is not None:
+                self.graph_tables_abort()
+            raise
+        if graph_header is not None:
+            self._graph_tables_done(defer_reset)
+        return True
+
+    def decode_into(self, gathered, R, out, plain=False):
+        """The decode-mean launch into a caller's buffer (MaureyCodec: a one-tensor group, its section at offset 0 of the rows)."""
+        if not self.ready:
+            self.upload_layout()
+        self._batch.decode(gathered, R, out, plain=plain)
+
+    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
+        """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode, no decode launch.
+        See _BatchedBase.roundtrip."""
+        if self._tmp_wire is None:
+            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
+        out, views = self._out_buffer(self.device)
+        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
+        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, draws=draws, rng_slot=rng_slot, out=out, **kw):
+            self._out_turn ^= 1      # (the buffer was not used)
+            return None
+        return views
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -1627,6 +1828,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return TopKCodec(compressor, numel, shape)
     if isinstance(compressor, SignSGDCompressor):
         return SignCodec(compressor, numel, shape)
+    if isinstance(compressor, MaureySparsification):
+        return MaureyCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

@@ -444,8 +444,9 @@ class ResidualCompressor(object):
 
 
 # ---- exported for `from compressors import *` in the reference's main.py ----------------
-# SignSGD and TopK run on HIP kernels for device float32 tensors (libgq_sign.so, libgq_topk.so; the quantizers ship them on a
-# 2-bit and a sparse wire, gq_amd.codecs.SignCodec / TopKCodec) and keep the reference's torch expressions for CPU tensors.
+# SignSGD, TopK and Maurey run on HIP kernels for device float32 tensors (libgq_sign.so, libgq_topk.so, libgq_maurey.so; the
+# quantizers ship them on a 2-bit and two sparse wires, gq_amd.codecs.SignCodec / TopKCodec / MaureyCodec) and keep torch
+# expressions for CPU tensors.
 
 class SignSGDCompressor(object):
     """sign(v) (signsgd_compressor.py:4-12)."""
@@ -513,10 +514,12 @@ class TopKSparsificationCompressor(object):
 
 class MaureySparsification(object):
     """Maurey sampling (maurey_sparsification.py:4-50): k coordinates drawn with probability |v_i| / ||v||_1, each
-    carrying sign(v_i) * ||v||_1 / k.  A name export like the two classes above (the reference does not wire it into
-    main.py's table either): same constructor arithmetic for k, the draws come from torch.multinomial on the
-    tensor's device instead of a k x size cumulative-sum comparison on the CPU -- the same distribution, other
-    random numbers."""
+    carrying sign(v_i) * ||v||_1 / k; same constructor arithmetic for cr and k, the same signature [scale, codes, signs] and
+    the same decompress.  The reference compares cumsum(p) with a k x size matrix of independent uniforms on the CPU, which is
+    not an inverse-CDF sample and cannot run at size; here the draws are i.i.d. samples of that distribution.  A CUDA float32
+    tensor is sampled by the HIP kernels (libgq_maurey.so, gq_amd.codecs.MaureyCodec: an inverse-CDF sample of one uniform per
+    draw over the f64 running sum of |v|; codes ascending; a tensor whose l1 norm is zero or not finite gives k times index 0
+    with a plus sign -- include/gq_maurey.h), every other tensor by torch.multinomial on the tensor's device."""
 
     def __init__(self, size, shape, args):
         self.cr = 32 * args.c_dim // (args.k_bit + args.n_bit)
@@ -524,13 +527,30 @@ class MaureySparsification(object):
         self.k = max(1, 32 * size // ((bit_for_idx + 1) * self.cr))
         self.cuda = not args.no_cuda
         self.size, self.shape = size, shape
+        self._rng = _rng_mode(args)      # where the kernels' uniforms come from (MaureyCodec)
 
     def compress(self, vec):
+        if vec.device.type == "cuda" and vec.dtype == torch.float32 and vec.numel() > 0:
+            return self._device_compress(vec)
         flat = vec.reshape(-1)
         mag = flat.abs()
         l1_norm = mag.sum()
         codes = torch.multinomial(mag / l1_norm, self.k, replacement=True)
         return [l1_norm / self.k, codes, torch.sign(flat[codes])]
+
+    def _device_compress(self, vec):
+        """The signature read back from the sparse wire of the kernels: scale (0-dim f32), codes int64[k] ascending, signs f32[k]."""
+        from .codecs import MaureyCodec      # (codecs imports this module)
+        n = vec.numel()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = MaureyCodec(self, n, (n,))
+        wire = torch.empty(codec.nbytes, dtype=torch.uint8, device=vec.device)
+        codec.encode_into(vec.reshape(-1), wire, 0, 0)
+        words = wire[native.MAUREY_HEADER_BYTES:native.MAUREY_HEADER_BYTES + 4 * codec.k].view(torch.int32)
+        signs = torch.where(words < 0, -1.0, 1.0).to(torch.float32)
+        return [wire[:4].view(torch.float32)[0].clone(), (words & 0x7fffffff).to(torch.int64), signs]
 
     def decompress(self, signature):
         scale, codes, signs = signature

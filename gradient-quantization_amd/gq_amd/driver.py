@@ -32,8 +32,8 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (IdenticalCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor, QSGDCompressor,
-                          ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
+from .compressors import (IdenticalCompressor, MaureySparsification, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
 quantizer_choices = {          # main.py:20-26
@@ -44,6 +44,7 @@ quantizer_choices = {          # main.py:20-26
     'topk': TopKSparsificationCompressor,
     'pvq': ProbabilisticVectorCompressor,      # the unbiased vector quantiser (not in main.py's table: INTEGRATION.md)
     'rq': ResidualCompressor,                  # two stages: hsq, then pvq on what it leaves (not in main.py's table either)
+    'maurey': MaureySparsification,            # the unbiased sparsifier: k draws with P(i) = |v_i| / ||v||_1 (likewise)
 }
 
 

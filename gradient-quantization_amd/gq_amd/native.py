@@ -939,3 +939,99 @@ class RQBatch(object):
         rc = self.RL.gq_rq_decode_sum_batched(self.ref, self.b1._wire(gathered), ctypes.c_int64(stride), ctypes.c_int(R), op,
                                               ctypes.c_int(mode), _stream())
         _check_rq(rc, "gq_rq_decode_sum_batched")
+
+
+# ---- Maurey sparsification on a sparse wire: libgq_maurey.so (include/gq_maurey.h) ------------------------------------------
+MAUREY_LIB_PATH = os.environ.get("GQ_MAUREY_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_maurey.so")
+MAUREY_ABI_VERSION = 1
+MAUREY_EXPORTS = ["gq_maurey_abi_version", "gq_maurey_last_error", "gq_maurey_compress_batched", "gq_maurey_decode_sum_batched"]
+MAUREY_CHUNK = 4096         # GQ_MAUREY_CHUNK: elements per item
+MAUREY_HEADER_BYTES = 16    # GQ_MAUREY_HEADER_BYTES: scale + 12 zero bytes in front of a section's words
+
+_maurey_lib = None
+
+
+def maurey_lib():
+    """Load libgq_maurey.so; fail loudly if it was not built (as lib())."""
+    global _maurey_lib
+    if _maurey_lib is None:
+        if not os.path.exists(MAUREY_LIB_PATH):
+            raise GQNativeError("libgq_maurey.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                "(there is no CPU fallback)" % MAUREY_LIB_PATH)
+        L = ctypes.CDLL(MAUREY_LIB_PATH)
+        L.gq_maurey_last_error.restype = ctypes.c_char_p
+        L.gq_maurey_abi_version.restype = ctypes.c_int
+        for name in MAUREY_EXPORTS:
+            getattr(L, name)
+        if L.gq_maurey_abi_version() != MAUREY_ABI_VERSION:
+            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
+                                % (MAUREY_LIB_PATH, L.gq_maurey_abi_version(), MAUREY_ABI_VERSION))
+        _maurey_lib = L
+    return _maurey_lib
+
+
+def _check_maurey(rc, what):
+    CALLS[0] += 1
+    if rc != 0:
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, maurey_lib().gq_maurey_last_error().decode()))
+
+
+class _MaureyBatchStruct(ctypes.Structure):   # gq_maurey_batch (include/gq_maurey.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64), ("ndraws", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("totals", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("draw_item", ctypes.c_void_p), ("bucket", ctypes.c_void_p),
+                ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class MaureyBatch(object):
+    """The multi-tensor Maurey launches: gq_maurey_compress_batched (the sampler's six launches, + the dense decoded tensors and
+    the residual) and gq_maurey_decode_sum_batched.  sums (float64 [nitems * 4]), totals (float64 [nseg]), counts
+    (int32 [nitems * 3]), draw_item (int32 [ndraws]) and bucket (float32 [ndraws]) are the caller's scratch; nothing in them
+    has to be zero (include/gq_maurey.h)."""
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, ndraws=0, sums=None, totals=None, counts=None, draw_item=None, bucket=None):
+        self.L = maurey_lib()
+        self.keep = (seg_table, item_seg, sums, totals, counts, draw_item, bucket)
+        ptr = lambda t, dt, name: _dev_ptr(t, dt, name).value if t is not None else None
+        self.s = _MaureyBatchStruct(ctypes.sizeof(_MaureyBatchStruct), int(nseg), int(nitems), int(ndraws),
+                                    _dev_ptr(seg_table, torch.int64, "seg_table").value, _dev_ptr(item_seg, torch.int32, "item_seg").value,
+                                    ptr(sums, torch.float64, "sums"), ptr(totals, torch.float64, "totals"), ptr(counts, torch.int32, "counts"),
+                                    ptr(draw_item, torch.int32, "draw_item"), ptr(bucket, torch.float32, "bucket"), None, 0, 0)
+        self.ref = ctypes.byref(self.s)
+
+    def set_table(self, seg_table):
+        """As HSQBatch.set_table."""
+        self.keep_table = seg_table
+        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
+
+    def set_dense(self, dense_table, ndense):
+        """As QSGDBatch.set_dense: the compress's last launch also copies the uncompressed tensors into the wire."""
+        self.keep_dense = dense_table
+        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
+        self.s.ndense = int(ndense) if dense_table is not None else 0
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
+        return MaureyBatch(seg_table, item_seg, nseg, nitems)
+
+    def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
+        """random_mode: RANDOM_GIVEN (r: float32 [ndraws], tensor s reads r[first draw + j]), RANDOM_DEVICE (seed) or
+        RANDOM_DEVICE_COUNTER (seed = the address of a { seed, step } pair).  out: the dense decoded tensors (float32, at the
+        table's out offsets); ef_scale given: error feedback in the same launches (seg_table[:, 7] = error buffers; needs out)."""
+        if r is not None:
+            assert r.numel() >= self.s.ndraws
+        rc = self.L.gq_maurey_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
+                                               _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
+                                               ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                               ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                               _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check_maurey(rc, "gq_maurey_compress_batched")
+
+    def decode(self, gathered, R, out, plain=False):
+        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
+        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
+        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
+        rc = self.L.gq_maurey_decode_sum_batched(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride),
+                                                 ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
+                                                 _stream())
+        _check_maurey(rc, "gq_maurey_decode_sum_batched")

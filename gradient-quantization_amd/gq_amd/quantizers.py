@@ -46,8 +46,8 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedHSQ, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec, QSGDCodec,
-    ResidualCodec, SignCodec, TopKCodec,
+    BatchedHSQ, BatchedMaurey, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
+    MaureyCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -219,7 +219,7 @@ class PSQuantizer(object):
         self._step_tail = os.environ.get("GQ_STEP_TAIL", "1") != "0"       # (see _decode_all)
         self._fuse_levels = os.environ.get("GQ_FUSE_LEVELS", "1") != "0"   # (see _can_fuse_levels)
         BatchedQSGD.place_lone_buckets(self.codecs)
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, BatchedTopK, BatchedSign):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, BatchedTopK, BatchedSign, BatchedMaurey):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -260,10 +260,11 @@ class PSQuantizer(object):
         # multi-tensor kernels and the per-tensor path both take their slices from it.  A ProbabilisticVectorCompressor tensor
         # draws twice (probabilistic_vector_compressor.py:52 for the codewords, then the level quantiser's): it owns two
         # consecutive slices in that order (PVQCodec.draw_count); a ResidualCompressor tensor up to three: stage 1's level draws,
-        # stage 2's codeword draws, stage 2's level draws (residual_compressor.py:17-24; ResidualCodec.draw_runs).
+        # stage 2's codeword draws, stage 2's level draws (residual_compressor.py:17-24; ResidualCodec.draw_runs).  A
+        # MaureySparsification tensor owns k: one uniform per draw (MaureyCodec; not the reference's k x n matrix).
         self._draw_off, n = {}, 0
         for i, c in enumerate(self.codecs):
-            if isinstance(c, (HSQCodec, ResidualCodec)) and c.uses_reference_draws():
+            if isinstance(c, (HSQCodec, ResidualCodec, MaureyCodec)) and c.uses_reference_draws():
                 self._draw_off[i] = n
                 n += c.draw_count()
         self._draw_total = n
