@@ -1,10 +1,9 @@
 #!/usr/bin/env python3
-"""Build libgq_hsq.so (the C-ABI HIP library) in-tree with hipcc for gfx950.
+"""Build libgq_hsq.so (the C-ABI HIP library) and the small libraries beside it (LIBS) in-tree with hipcc for gfx950.
 
     python gradient-quantization_amd/build.py [--force]
 
-hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU
-box with the source snapshot.
+hipcc cross-compiles without a GPU.  The libraries are git-ignored.
 """
 import os
 import shutil
@@ -15,22 +14,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgq_hsq.so")
-# top-k sparsification (include/gq_topk.h): a library of its own, so that libgq_hsq.so's entry points stay as they are
-TOPK_LIB = os.path.join(HERE, "libgq_topk.so")
-TOPK_SOURCES = ["topk.hip"]
-# signSGD on a 2-bit wire (include/gq_sign.h): a library of its own too
-SIGN_LIB = os.path.join(HERE, "libgq_sign.so")
-SIGN_SOURCES = ["sign.hip"]
-# the multi-tensor ProbabilisticVectorCompressor encode (include/gq_pvq.h): likewise; it shares the walk with pvq.hip (csrc/pvq_walk.hpp)
-PVQ_LIB = os.path.join(HERE, "libgq_pvq.so")
-PVQ_SOURCES = ["pvq_batched.hip"]
-# the ResidualCompressor's own two launches (include/gq_rq.h): stage 2's multi-tensor encode (the same walk) and the two-stage decode-mean
-RQ_LIB = os.path.join(HERE, "libgq_rq.so")
-RQ_SOURCES = ["rq_batched.hip"]
-# Maurey sparsification on a sparse wire (include/gq_maurey.h): the sampler's six launches and the decode-mean
-MAUREY_LIB = os.path.join(HERE, "libgq_maurey.so")
-MAUREY_SOURCES = ["maurey.hip"]
 SOURCES = ["gq_common.hip", "gq_api.hip", "hsq_encode.hip", "hsq_encode_pf.hip", "hsq_encode_pfd.hip", "hsq_levels.hip", "hsq_batched.hip", "hsq_decode.hip", "qsgd.hip", "qsgd_batched.hip", "qsgd_wide.hip", "pvq.hip"]
+# library -> its sources.  Every compressor after HSQ / QSGD is a library of its own (include/gq_<name>.h), so that libgq_hsq.so's
+# entry points stay as they are; each is one file that starts from csrc/gq_lib_prelude.hpp.
+LIBS = {
+    LIB: SOURCES,
+    os.path.join(HERE, "libgq_topk.so"): ["topk.hip"],            # top-k sparsification
+    os.path.join(HERE, "libgq_sign.so"): ["sign.hip"],            # signSGD on a 2-bit wire
+    os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],      # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
+    os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean
+    os.path.join(HERE, "libgq_maurey.so"): ["maurey.hip"],        # Maurey sparsification: the sampler's six launches and the decode-mean
+}
 # -ffp-contract=off: the reference's elementwise ops are separately rounded; hipcc's
 # default ("fast") would fuse the decode's mul/add and the level quantiser's sub/div.
 # -packed-fp32-ops (target feature off): no v_pk_{fma,mul,add}_f32.  One instantiation of the encode kernel came out
@@ -54,14 +48,12 @@ HOST_EXT = os.path.join(HERE, "gq_amd", "_gq_host.so")
 
 
 def needs_build():
-    if (not os.path.exists(LIB) or not os.path.exists(os.path.join(HERE, "libgq_hsq_clock.so")) or not os.path.exists(HOST_EXT)
-            or not os.path.exists(TOPK_LIB) or not os.path.exists(SIGN_LIB) or not os.path.exists(PVQ_LIB) or not os.path.exists(RQ_LIB)
-            or not os.path.exists(MAUREY_LIB)):
+    built = list(LIBS) + [CLOCK_LIB, HOST_EXT]
+    if not all(os.path.exists(p) for p in built):
         return True
-    t = min(os.path.getmtime(LIB), os.path.getmtime(HOST_EXT), os.path.getmtime(TOPK_LIB), os.path.getmtime(SIGN_LIB), os.path.getmtime(PVQ_LIB),
-            os.path.getmtime(RQ_LIB), os.path.getmtime(MAUREY_LIB))
-    deps = ([os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(ROOT, "include", h) for h in ("gq_hsq.h", "gq_topk.h", "gq_sign.h", "gq_pvq.h", "gq_rq.h", "gq_maurey.h")]
-            + [__file__])
+    t = min(os.path.getmtime(p) for p in built)
+    include = os.path.join(ROOT, "include")
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(include, h) for h in os.listdir(include)] + [__file__]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -79,53 +71,42 @@ EXTRA = {
 }
 
 
+def _obj(src):
+    return os.path.join(HERE, "build", src.replace(".hip", ".o"))
+
+
+def _link(out, objs, verbose=False):
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + objs
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+
+
 def build(force=False, verbose=False):
     if not force and not needs_build():
         return LIB
-    objdir = os.path.join(HERE, "build")
-    os.makedirs(objdir, exist_ok=True)
+    os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     compile_flags = [f for f in FLAGS if f != "-shared"]
     procs = []
-    for src in SOURCES:
-        obj = os.path.join(objdir, src.replace(".hip", ".o"))
-        cmd = [hipcc()] + compile_flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
+    for src in [src for srcs in LIBS.values() for src in srcs]:
+        cmd = [hipcc()] + compile_flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", _obj(src)]
         if verbose:
             print(" ".join(cmd))
-        procs.append((cmd, subprocess.Popen(cmd), obj))
-    topk_objs, sign_objs, pvq_objs, rq_objs, maurey_objs = [], [], [], [], []
-    for srcs, own in ((TOPK_SOURCES, topk_objs), (SIGN_SOURCES, sign_objs), (PVQ_SOURCES, pvq_objs), (RQ_SOURCES, rq_objs),
-                      (MAUREY_SOURCES, maurey_objs)):
-        for src in srcs:
-            obj = os.path.join(objdir, src.replace(".hip", ".o"))
-            cmd = [hipcc()] + compile_flags + EXTRA.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj]
-            if verbose:
-                print(" ".join(cmd))
-            procs.append((cmd, subprocess.Popen(cmd), obj))
-            own.append(obj)
-    objs = []
-    for cmd, p, obj in procs:
+        procs.append((cmd, subprocess.Popen(cmd)))
+    for cmd, p in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
-        if obj not in topk_objs and obj not in sign_objs and obj not in pvq_objs and obj not in rq_objs and obj not in maurey_objs:
-            objs.append(obj)
-    link = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
-    if verbose:
-        print(" ".join(link))
     host = None
     try:
-        host = build_host_ext(verbose, wait=False)      # g++ against libtorch: ~25 s, next to the link and the clock twin
+        host = build_host_ext(verbose, wait=False)      # g++ against libtorch: ~25 s, next to the links and the clock twin
     except Exception as e:      # (no libtorch headers, no g++): the helper is optional, quantizers.py walks in Python without it
         print("build.py: host helper not built (%s); gq_amd falls back to its Python walks" % (e,), file=sys.stderr)
     try:
-        subprocess.check_call(link)
-        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", TOPK_LIB] + topk_objs)
-        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SIGN_LIB] + sign_objs)
-        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PVQ_LIB] + pvq_objs)
-        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", RQ_LIB] + rq_objs)
-        subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", MAUREY_LIB] + maurey_objs)
-        build_clock_lib(objs, verbose)
+        for out, srcs in LIBS.items():
+            _link(out, [_obj(src) for src in srcs], verbose)
+        build_clock_lib(verbose=verbose)
     finally:
-        if host is not None and host[1].wait() != 0:     # (always reaped, also when the link above raised)
+        if host is not None and host[1].wait() != 0:     # (always reaped, also when a link above raised)
             print("build.py: host helper failed to compile (exit %d); gq_amd falls back to its Python walks" % host[1].returncode,
                   file=sys.stderr)
     return LIB
@@ -158,11 +139,10 @@ def build_clock_lib(objs=None, verbose=False, source=None, out=None):
     s_memrealtime stamps around the phases of a tile; see the macro's comment in the file).  Never loaded by the product:
     `bench.py` runs it in a child process to read the in-kernel clock (roofline.in_kernel_clock_ghz), tools/stamp_read.py
     prints the whole breakdown.  `source` / `out`: a variant of the file (tools/stamp_build.py)."""
-    objdir = os.path.join(HERE, "build")
     if objs is None:
-        objs = [os.path.join(objdir, f.replace(".hip", ".o")) for f in SOURCES]
+        objs = [_obj(f) for f in SOURCES]
     src = source or os.path.join(CSRC, "hsq_encode_pf.hip")
-    obj = os.path.join(objdir, "stamps", "hsq_encode_pf_stamps.o" if out is None else os.path.basename(out) + ".o")   # (a directory of its own: build/*.o are the product's objects)
+    obj = os.path.join(HERE, "build", "stamps", "hsq_encode_pf_stamps.o" if out is None else os.path.basename(out) + ".o")   # (a directory of its own: build/*.o are the product's objects)
     os.makedirs(os.path.dirname(obj), exist_ok=True)
     flags = [f for f in FLAGS if f != "-shared"] + EXTRA.get("hsq_encode_pf.hip", [])
     cmd = [hipcc()] + flags + ["-DGQ_PF_STAMPS", "-c", src, "-o", obj]
@@ -170,7 +150,7 @@ def build_clock_lib(objs=None, verbose=False, source=None, out=None):
         print(" ".join(cmd))
     subprocess.check_call(cmd, stderr=None if verbose else subprocess.DEVNULL)
     others = [o for o in objs if os.path.basename(o) != "hsq_encode_pf.o"]
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out or CLOCK_LIB, obj] + others)
+    _link(out or CLOCK_LIB, [obj] + others, verbose)
     return out or CLOCK_LIB
 
 

@@ -18,14 +18,10 @@
 // decode     one workgroup per chunk of the output (topk_decode_kernel's shape): for every payload in order, the run of its
 //            words that falls into the chunk is found by binary search and counted into an LDS integer accumulator (+-1 per
 //            word), then D = scale * (float)count is added into the LDS sum -- no float atomics, a fixed order of additions.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 
 #include "gq_common.hpp"
-#include "gq_hsq.h"
+#include "gq_lib_prelude.hpp"
 #include "gq_maurey.h"
 
 #define GQM_API extern "C" __attribute__((visibility("default")))
@@ -41,22 +37,9 @@ constexpr int PADDED = CHUNK + CHUNK / PER_THREAD;    // an LDS array of one wor
 static_assert(PER_THREAD == 16 && THREADS == 256, "the order of additions (gq_maurey.h) is 16 x 16 x 16");
 static_assert(sizeof(gq_maurey_batch) == 96, "gq_maurey_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
-// the text of the last failure (gq_maurey_last_error); one buffer for the process, as in libgq_topk.so
-static char err_buf[512];
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf, sizeof(err_buf), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define GQM_CHECK_LAUNCH(what)                                                                       \
-    do {                                                                                             \
-        hipError_t e__ = hipGetLastError();                                                          \
-        if (e__ != hipSuccess) return gqm::fail(GQ_ERR_HIP, "%s: %s", what, hipGetErrorString(e__)); \
-    } while (0)
+using gql::copy_dense;
+using gql::err_buf;
+using gql::fail;
 
 // element e of an item in an LDS array: a thread's 16 words are contiguous, the pad spreads the threads over the banks
 __device__ __forceinline__ int phys(int e) { return e + (e >> 4); }
@@ -305,22 +288,13 @@ __global__ __launch_bounds__(THREADS) void maurey_place_kernel(const int64_t *__
     if (pos < rec[4]) bucket[rec[6] + pos] = draw_u(random_mode, r, seed, d);
 }
 
-__device__ __forceinline__ void copy_dense(const int64_t *__restrict__ dense_table, int ndense, uint8_t *__restrict__ wire) {
-    for (int t = blockIdx.x; t < ndense; t += gridDim.x) {
-        const float *src = reinterpret_cast<const float *>(dense_table[3 * t]);
-        float *dst = reinterpret_cast<float *>(wire + dense_table[3 * t + 1]);
-        const int64_t n = dense_table[3 * t + 2];
-        for (int64_t i = threadIdx.x; i < n; i += THREADS) dst[i] = src[i];
-    }
-}
-
 template <bool EF>
 __global__ __launch_bounds__(THREADS) void maurey_item_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                               const double *__restrict__ sums, const double *__restrict__ totals,
                                                               const int32_t *__restrict__ counts, const float *__restrict__ bucket,
                                                               uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
                                                               const int64_t *__restrict__ dense_table, int ndense) {
-    copy_dense(dense_table, ndense, wire);
+    copy_dense<THREADS>(dense_table, ndense, wire);
     __shared__ double cdf[PADDED];
     __shared__ uint32_t hit[PADDED];
     __shared__ double lds_tot[THREADS], lds_grp[16];
@@ -507,20 +481,20 @@ static int maurey_compress(const gq_maurey_batch *b, uint8_t *wire, int random_m
     using namespace gqm;
     const dim3 items((unsigned)b->nitems), segs((unsigned)b->nseg), draws((unsigned)((b->ndraws + THREADS - 1) / THREADS)), block(THREADS);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(maurey_sum_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->sums, ef_scale);
-    GQM_CHECK_LAUNCH("gq_maurey_compress_batched (sum)");
+    GQL_CHECK_LAUNCH("gq_maurey_compress_batched (sum)");
     hipLaunchKernelGGL(maurey_scan_kernel, segs, block, 0, st, b->seg_table, b->sums, b->totals, b->counts, wire);
-    GQM_CHECK_LAUNCH("gq_maurey_compress_batched (scan)");
+    GQL_CHECK_LAUNCH("gq_maurey_compress_batched (scan)");
     hipLaunchKernelGGL(maurey_count_kernel, draws, block, 0, st, b->seg_table, b->nseg, b->ndraws, b->sums, b->totals, b->counts,
                        b->draw_item, random_mode, r, seed);
-    GQM_CHECK_LAUNCH("gq_maurey_compress_batched (count)");
+    GQL_CHECK_LAUNCH("gq_maurey_compress_batched (count)");
     hipLaunchKernelGGL(maurey_offsets_kernel, segs, block, 0, st, b->seg_table, b->counts);
-    GQM_CHECK_LAUNCH("gq_maurey_compress_batched (offsets)");
+    GQL_CHECK_LAUNCH("gq_maurey_compress_batched (offsets)");
     hipLaunchKernelGGL(maurey_place_kernel, draws, block, 0, st, b->seg_table, b->nseg, b->ndraws, b->counts, b->draw_item, b->bucket,
                        random_mode, r, seed);
-    GQM_CHECK_LAUNCH("gq_maurey_compress_batched (place)");
+    GQL_CHECK_LAUNCH("gq_maurey_compress_batched (place)");
     hipLaunchKernelGGL(HIP_KERNEL_NAME(maurey_item_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->sums, b->totals, b->counts,
                        b->bucket, wire, out, ef_scale, b->dense_table, b->ndense);
-    GQM_CHECK_LAUNCH("gq_maurey_compress_batched (item)");
+    GQL_CHECK_LAUNCH("gq_maurey_compress_batched (item)");
     return GQ_OK;
 }
 
@@ -553,6 +527,6 @@ GQM_API int gq_maurey_decode_sum_batched(const gq_maurey_batch *b, const uint8_t
         return gqm::fail(GQ_ERR_INVALID_ARG, "gq_maurey_decode_sum_batched: the gathered wire must be 4-byte aligned");
     hipLaunchKernelGGL(gqm::maurey_decode_kernel, dim3((unsigned)b->nitems), dim3(gqm::THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                        b->seg_table, b->item_seg, gathered, user_stride_bytes, R, out, plain ? 1 : 0);
-    GQM_CHECK_LAUNCH("gq_maurey_decode_sum_batched");
+    GQL_CHECK_LAUNCH("gq_maurey_decode_sum_batched");
     return GQ_OK;
 }

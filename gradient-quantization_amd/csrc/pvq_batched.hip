@@ -10,9 +10,9 @@
 // (min, max) of u into the tensor's order-mapped words, which the level launch of libgq_hsq.so unmaps into (lb, ub).
 // Like the flat kernel's fminf / fmaxf fold, the words never see a NaN projection (a subvector with a NaN element).
 #include <math.h>
-#include <stdarg.h>
 #include <stdlib.h>
 
+#include "gq_lib_prelude.hpp"
 #include "gq_pvq.h"
 #include "hsq_pf_common.hpp"
 #include "pvq_walk.hpp"
@@ -25,16 +25,8 @@ using namespace gq;
 
 static_assert(sizeof(gq_pvq_batch) == 24, "gq_pvq_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
-// the text of the last failure (gq_pvq_last_error); one buffer for the process, as in libgq_sign.so
-static char err_buf[512];
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf, sizeof(err_buf), fmt, ap);
-    va_end(ap);
-    return code;
-}
+using gql::err_buf;
+using gql::fail;
 
 static int cu_count_here() {
     static int cus = [] {
@@ -230,8 +222,7 @@ static int launch(const PvbArgs &a, hipStream_t st) {
     b.tiles_per_wave = (int)(a.ntiles / waves);
     b.waves_with_one_more = (int)(a.ntiles - (int64_t)b.tiles_per_wave * waves);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(pvq_encode_walk_batched_kernel<D, EF>), dim3((unsigned)blocks), dim3(ENC_THREADS), lds_bytes, st, b);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GQ_ERR_HIP, "gq_pvq_encode_batched: %s", hipGetErrorString(e));
+    GQL_CHECK_LAUNCH("gq_pvq_encode_batched");
     return GQ_OK;
 }
 

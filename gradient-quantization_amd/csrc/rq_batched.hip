@@ -12,9 +12,9 @@
 //  * rq_decode_sum_kernel: acc = x_0, acc += x_r with x_r = (0 + d1_r) + d2_r rounded first -- torch.stack([d1, d2]).sum(0)
 //    per user, then stack(users).mean(0).  Feeding 2R payloads to the HSQ decode would give ((d1_0 + d2_0) + d1_1) + d2_1.
 #include <math.h>
-#include <stdarg.h>
 #include <stdlib.h>
 
+#include "gq_lib_prelude.hpp"
 #include "gq_rq.h"
 #include "hsq_pf_common.hpp"
 #include "pvq_walk.hpp"
@@ -27,16 +27,8 @@ using namespace gq;
 
 static_assert(sizeof(gq_rq_batch) == 40, "gq_rq_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
-// the text of the last failure (gq_rq_last_error); one buffer for the process, as in libgq_pvq.so
-static char err_buf[512];
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf, sizeof(err_buf), fmt, ap);
-    va_end(ap);
-    return code;
-}
+using gql::err_buf;
+using gql::fail;
 
 static int cu_count_here() {
     static int cus = [] {
@@ -273,8 +265,7 @@ static int launch_encode2(const RqEncArgs &a, hipStream_t st) {
     b.tiles_per_wave = (int)(a.ntiles / waves);
     b.waves_with_one_more = (int)(a.ntiles - (int64_t)b.tiles_per_wave * waves);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(rq_encode2_batched_kernel<D>), dim3((unsigned)blocks), dim3(ENC_THREADS), lds_bytes, st, b);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GQ_ERR_HIP, "gq_rq_encode2_batched: %s", hipGetErrorString(e));
+    GQL_CHECK_LAUNCH("gq_rq_encode2_batched");
     return GQ_OK;
 }
 
@@ -379,8 +370,7 @@ static int launch_decode(const RqDecArgs &a, hipStream_t st) {
     const int64_t cap = (int64_t)cu_count_here() * 8;
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(rq_decode_sum_kernel<D, ERR>), dim3((unsigned)blocks), dim3(DEC_THREADS), lds_bytes, st, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GQ_ERR_HIP, "gq_rq_decode_sum_batched: %s", hipGetErrorString(e));
+    GQL_CHECK_LAUNCH("gq_rq_decode_sum_batched");
     return GQ_OK;
 }
 

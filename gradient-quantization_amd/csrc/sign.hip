@@ -15,13 +15,9 @@
 // decode    the same items; a lane reads its byte of each of the R payloads in order, sums the four sign-extended fields as
 //           integers (exact) and writes (float)sum / (float)R with a float4 store.
 // Every launch's arguments depend on the layout alone: both replay from a HIP graph.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 
-#include "gq_hsq.h"
+#include "gq_lib_prelude.hpp"
 #include "gq_sign.h"
 
 #define GQS_API extern "C" __attribute__((visibility("default")))
@@ -34,22 +30,10 @@ constexpr int PER_THREAD = ITEM_BYTES / THREADS;      // wire bytes (four elemen
 static_assert(ITEM_BYTES % THREADS == 0 && THREADS % 4 == 0, "an item is a whole number of block-wide steps of whole words");
 static_assert(sizeof(gq_sign_batch) == 48, "gq_sign_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
-// the text of the last failure (gq_sign_last_error); one buffer for the process, as in libgq_topk.so
-static char err_buf[512];
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf, sizeof(err_buf), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define GQS_CHECK_LAUNCH(what)                                                                       \
-    do {                                                                                             \
-        hipError_t e__ = hipGetLastError();                                                          \
-        if (e__ != hipSuccess) return gqs::fail(GQ_ERR_HIP, "%s: %s", what, hipGetErrorString(e__)); \
-    } while (0)
+using gql::aligned16;
+using gql::copy_dense;
+using gql::err_buf;
+using gql::fail;
 
 // the section of a tensor of n elements: ceil(n / 16) words, rounded up to 16 bytes (gq_amd.codecs._up)
 __host__ __device__ constexpr int64_t section_bytes(int64_t n) { return (((n + 15) / 16) * 4 + 15) / 16 * 16; }
@@ -63,22 +47,11 @@ __device__ __forceinline__ uint32_t code_of(float w) {
 // the field of element k (0..3) of a wire byte as a signed integer: to the top of the word and back, arithmetically
 __device__ __forceinline__ int field(uint32_t byte, int k) { return (int32_t)(byte << (30 - 2 * k)) >> 30; }
 
-__device__ __forceinline__ void copy_dense(const int64_t *__restrict__ dense_table, int ndense, uint8_t *__restrict__ wire) {
-    for (int t = blockIdx.x; t < ndense; t += gridDim.x) {
-        const float *src = reinterpret_cast<const float *>(dense_table[3 * t]);
-        float *dst = reinterpret_cast<float *>(wire + dense_table[3 * t + 1]);
-        const int64_t n = dense_table[3 * t + 2];
-        for (int64_t i = threadIdx.x; i < n; i += THREADS) dst[i] = src[i];
-    }
-}
-
-__device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <bool EF>
 __global__ __launch_bounds__(THREADS) void sign_compress_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                                 uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
                                                                 const int64_t *__restrict__ dense_table, int ndense) {
-    copy_dense(dense_table, ndense, wire);
+    copy_dense<THREADS>(dense_table, ndense, wire);
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
@@ -223,7 +196,7 @@ GQS_API int gq_sign_compress_batched(const gq_sign_batch *b, uint8_t *wire, floa
     else
         hipLaunchKernelGGL(HIP_KERNEL_NAME(sign_compress_kernel<false>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out, 0.0f,
                            b->dense_table, b->ndense);
-    GQS_CHECK_LAUNCH("gq_sign_compress_batched");
+    GQL_CHECK_LAUNCH("gq_sign_compress_batched");
     return GQ_OK;
 }
 
@@ -238,6 +211,6 @@ GQS_API int gq_sign_decode_sum_batched(const gq_sign_batch *b, const uint8_t *ga
     if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "gq_sign_decode_sum_batched: out must be 4-byte aligned");
     hipLaunchKernelGGL(sign_decode_kernel, dim3((unsigned)b->nitems), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream), b->seg_table,
                        b->item_seg, gathered, user_stride_bytes, R, out, plain ? 1 : 0);
-    GQS_CHECK_LAUNCH("gq_sign_decode_sum_batched");
+    GQL_CHECK_LAUNCH("gq_sign_decode_sum_batched");
     return GQ_OK;
 }

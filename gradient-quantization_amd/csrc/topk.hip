@@ -18,13 +18,9 @@
 //                                    (ascending) indices that falls into the chunk is found by binary search and added into
 //                                    an LDS accumulator -- no float atomics, a fixed order of additions.
 // Every launch's arguments depend on the layout alone: the eight compress launches replay from a HIP graph.
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
 
-#include "gq_hsq.h"
+#include "gq_lib_prelude.hpp"
 #include "gq_topk.h"
 
 #define GQT_API extern "C" __attribute__((visibility("default")))
@@ -40,23 +36,9 @@ constexpr uint32_t NO_KEY = 0x80000000u;      // above every key: the threshold 
 static_assert(CHUNK % THREADS == 0, "an item is a whole number of block-wide steps");
 static_assert(sizeof(gq_topk_batch) == 72, "gq_topk_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
-// the text of the last failure (gq_topk_last_error); one buffer for the process: the checks fail before any launch, and a
-// caller that drives the library from several threads at once reads the text of whichever failure came last
-static char err_buf[512];
-
-static int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err_buf, sizeof(err_buf), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define GQT_CHECK_LAUNCH(what)                                                                       \
-    do {                                                                                             \
-        hipError_t e__ = hipGetLastError();                                                          \
-        if (e__ != hipSuccess) return gqt::fail(GQ_ERR_HIP, "%s: %s", what, hipGetErrorString(e__)); \
-    } while (0)
+using gql::copy_dense;
+using gql::err_buf;
+using gql::fail;
 
 // pass p of the select: the key bits [shift, shift + nb)
 __host__ __device__ constexpr int pass_shift(int p) { return p == 0 ? 20 : (p == 1 ? 9 : 0); }
@@ -241,21 +223,12 @@ __global__ __launch_bounds__(THREADS) void topk_scan_kernel(const int64_t *__res
     }
 }
 
-__device__ __forceinline__ void copy_dense(const int64_t *__restrict__ dense_table, int ndense, uint8_t *__restrict__ wire) {
-    for (int t = blockIdx.x; t < ndense; t += gridDim.x) {
-        const float *src = reinterpret_cast<const float *>(dense_table[3 * t]);
-        float *dst = reinterpret_cast<float *>(wire + dense_table[3 * t + 1]);
-        const int64_t n = dense_table[3 * t + 2];
-        for (int64_t i = threadIdx.x; i < n; i += THREADS) dst[i] = src[i];
-    }
-}
-
 template <bool EF>
 __global__ __launch_bounds__(THREADS) void topk_write_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                              const int32_t *__restrict__ state, const int32_t *__restrict__ counts,
                                                              uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
                                                              const int64_t *__restrict__ dense_table, int ndense) {
-    copy_dense(dense_table, ndense, wire);
+    copy_dense<THREADS>(dense_table, ndense, wire);
     __shared__ uint32_t lds[2][2][WAVES];      // [step parity][> T, == T][wave]
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
@@ -387,17 +360,17 @@ static int topk_compress(const gq_topk_batch *b, uint8_t *wire, float ef_scale, 
     for (int p = 0; p < 3; ++p) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(topk_hist_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->state, b->hist, p,
                            ef_scale);
-        GQT_CHECK_LAUNCH("gq_topk_compress_batched (hist)");
+        GQL_CHECK_LAUNCH("gq_topk_compress_batched (hist)");
         hipLaunchKernelGGL(topk_pick_kernel, segs, block, 0, st, b->seg_table, b->state, b->hist, p);
-        GQT_CHECK_LAUNCH("gq_topk_compress_batched (pick)");
+        GQL_CHECK_LAUNCH("gq_topk_compress_batched (pick)");
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(topk_count_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->state, b->counts, ef_scale);
-    GQT_CHECK_LAUNCH("gq_topk_compress_batched (count)");
+    GQL_CHECK_LAUNCH("gq_topk_compress_batched (count)");
     hipLaunchKernelGGL(topk_scan_kernel, segs, block, 0, st, b->seg_table, b->counts);
-    GQT_CHECK_LAUNCH("gq_topk_compress_batched (scan)");
+    GQL_CHECK_LAUNCH("gq_topk_compress_batched (scan)");
     hipLaunchKernelGGL(HIP_KERNEL_NAME(topk_write_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->state, b->counts, wire, out,
                        ef_scale, b->dense_table, b->ndense);
-    GQT_CHECK_LAUNCH("gq_topk_compress_batched (write)");
+    GQL_CHECK_LAUNCH("gq_topk_compress_batched (write)");
     return GQ_OK;
 }
 
@@ -422,6 +395,6 @@ GQT_API int gq_topk_decode_sum_batched(const gq_topk_batch *b, const uint8_t *ga
         return gqt::fail(GQ_ERR_INVALID_ARG, "gq_topk_decode_sum_batched: the gathered wire must be 4-byte aligned");
     hipLaunchKernelGGL(gqt::topk_decode_kernel, dim3((unsigned)b->nitems), dim3(gqt::THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                        b->seg_table, b->item_seg, gathered, user_stride_bytes, R, out, plain ? 1 : 0);
-    GQT_CHECK_LAUNCH("gq_topk_decode_sum_batched");
+    GQL_CHECK_LAUNCH("gq_topk_decode_sum_batched");
     return GQ_OK;
 }

@@ -17,6 +17,7 @@ device memory, through gq_amd.native).
 `codec_factory` arguments of the quantizers exist so that the host logic can be exercised without a GPU by the tests
 (with the CPU oracle as the checker codec: tests/oracle_codec.py).
 """
+import itertools
 import operator
 import os
 
@@ -538,7 +539,57 @@ class QSGDCodec(object):
         return out.view(self.shape)
 
 
-class TopKCodec(object):
+class _SparseCodec(object):
+    """What TopKCodec, SignCodec and MaureyCodec share: every call is a one-tensor group of the codec's multi-tensor class
+    (GROUP, set below that class), and roundtrip / encode_decode_into return the compress launches' own dense decode, not a
+    decode of the wire.  A subclass sets numel, shape and nbytes; `extra` are further arguments of its group's encode."""
+
+    GROUP = None
+    _single = None
+
+    def _wire_bytes(self):
+        """Bytes of a wire of this tensor alone (a launch is handed a valid address also when the section is empty)."""
+        return max(16, self.nbytes)
+
+    def _batched1(self, dev):
+        if self._single is None or self._single.device != dev:
+            self._single = self.GROUP([self], [0], [0], dev, 1, self._wire_bytes())
+        return self._single
+
+    @staticmethod
+    def _at(wire_user, off):
+        return wire_user[off:]
+
+    def encode_decode_into(self, grad, wire_user, off, salt, out, **extra):
+        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch sequence."""
+        self.encode_into(grad, wire_user, off, salt, out=out.view(-1), **extra)
+
+    def encode_into(self, grad, wire_user, off, salt, **extra):
+        name = type(self).__name__
+        _require_device(grad, name + (".encode_decode_into" if extra.get("out") is not None else ".encode_into"))
+        flat = grad.contiguous().view(-1)
+        ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt, **extra)
+        assert ok, name + ": the gradient must be a float32 tensor on the current device"
+
+    def roundtrip(self, grad, salt, **extra):
+        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
+        tmp = torch.empty(self._wire_bytes(), dtype=torch.uint8, device=grad.device)
+        self.encode_decode_into(grad, tmp, 0, salt, out, **extra)
+        return out.view(self.shape)
+
+    def decode_wire(self, wire_user, off, out):
+        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
+
+    def _decode_rows(self, gathered, off, R, out, plain=False):
+        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
+
+    def decode_mean(self, gathered, off, R, plain=False):
+        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        self._decode_rows(gathered, off, R, out, plain=plain)
+        return out.view(self.shape)
+
+
+class TopKCodec(_SparseCodec):
     """TopKSparsificationCompressor on the HIP kernels (libgq_topk.so).  Wire per tensor: k = numel // cr ascending uint32
     indices, then the k f32 values -- 8k bytes.  Every call is a one-tensor BatchedTopK; roundtrip / encode_decode_into return the
     compress launch's own dense decode (v * mask, the reference's signed zeros and NaNs included), not a decode of the wire."""
@@ -549,50 +600,17 @@ class TopKCodec(object):
         if not 0 <= self.k <= numel:
             raise ValueError("TopKCodec: k = %d for a tensor of %d elements" % (self.k, numel))
         self.nbytes = 8 * self.k
-        self._single = None
-
-    def _batched1(self, dev):
-        if self._single is None or self._single.device != dev:
-            self._single = BatchedTopK([self], [0], [0], dev, 1, max(16, self.nbytes))
-        return self._single
 
     @staticmethod
     def _at(wire_user, off):
         # (k = 0 writes nothing: any valid address will do when the section is empty and ends the buffer)
         return wire_user[off:] if off < wire_user.numel() else wire_user
 
-    def encode_decode_into(self, grad, wire_user, off, salt, out):
-        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch sequence."""
-        _require_device(grad, "TopKCodec.encode_decode_into")
-        flat = grad.contiguous().view(-1)
-        ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt, out=out.view(-1))
-        assert ok, "TopKCodec: the gradient must be a float32 tensor on the current device"
-
-    def encode_into(self, grad, wire_user, off, salt):
-        _require_device(grad, "TopKCodec.encode_into")
-        flat = grad.contiguous().view(-1)
-        ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt)
-        assert ok, "TopKCodec: the gradient must be a float32 tensor on the current device"
-
-    def roundtrip(self, grad, salt):
-        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
-        tmp = torch.empty(max(16, self.nbytes), dtype=torch.uint8, device=grad.device)
-        self.encode_decode_into(grad, tmp, 0, salt, out)
-        return out.view(self.shape)
-
-    def decode_wire(self, wire_user, off, out):
-        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
-
     def _decode_rows(self, gathered, off, R, out, plain=False):
         if self.k == 0:
             out.zero_()
             return
-        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
-
-    def decode_mean(self, gathered, off, R, plain=False):
-        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
-        self._decode_rows(gathered, off, R, out, plain=plain)
-        return out.view(self.shape)
+        _SparseCodec._decode_rows(self, gathered, off, R, out, plain=plain)
 
 
 def sign_section_bytes(numel):
@@ -600,7 +618,7 @@ def sign_section_bytes(numel):
     return _up(-(-numel // 16) * 4)
 
 
-class SignCodec(object):
+class SignCodec(_SparseCodec):
     """SignSGDCompressor on the HIP kernels (libgq_sign.so).  Wire per tensor: one 2-bit code per element, 00 = +0, 01 = +1,
     11 = -1, sixteen to a little-endian uint32 word (element i in bits 2*(i%16) of word i/16) -- _up(ceil(numel/16) * 4) bytes.
     torch.sign never returns -0 or NaN on the device, so the wire holds the decoded tensor exactly.  Every call is a one-tensor
@@ -609,45 +627,9 @@ class SignCodec(object):
     def __init__(self, compressor, numel, shape):
         self.c, self.numel, self.shape = compressor, numel, shape
         self.nbytes = sign_section_bytes(numel)
-        self._single = None
-
-    def _batched1(self, dev):
-        if self._single is None or self._single.device != dev:
-            self._single = BatchedSign([self], [0], [0], dev, 1, max(16, self.nbytes))
-        return self._single
-
-    def encode_decode_into(self, grad, wire_user, off, salt, out):
-        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch."""
-        _require_device(grad, "SignCodec.encode_decode_into")
-        flat = grad.contiguous().view(-1)
-        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt, out=out.view(-1))
-        assert ok, "SignCodec: the gradient must be a float32 tensor on the current device"
-
-    def encode_into(self, grad, wire_user, off, salt):
-        _require_device(grad, "SignCodec.encode_into")
-        flat = grad.contiguous().view(-1)
-        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt)
-        assert ok, "SignCodec: the gradient must be a float32 tensor on the current device"
-
-    def roundtrip(self, grad, salt):
-        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
-        tmp = torch.empty(max(16, self.nbytes), dtype=torch.uint8, device=grad.device)
-        self.encode_decode_into(grad, tmp, 0, salt, out)
-        return out.view(self.shape)
-
-    def decode_wire(self, wire_user, off, out):
-        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
-
-    def _decode_rows(self, gathered, off, R, out, plain=False):
-        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
-
-    def decode_mean(self, gathered, off, R, plain=False):
-        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
-        self._decode_rows(gathered, off, R, out, plain=plain)
-        return out.view(self.shape)
 
 
-class MaureyCodec(object):
+class MaureyCodec(_SparseCodec):
     """MaureySparsification on the HIP kernels (libgq_maurey.so).  Wire per tensor: a 16-byte header (scale = ||w||_1 / k as
     f32, 12 zero bytes), then k little-endian uint32 words  index | (w_index < 0) << 31, ascending by index (an index drawn m
     times appears m times), zero padding to 16 bytes -- 16 + _up(4k) bytes.  Every call is a one-tensor BatchedMaurey; roundtrip /
@@ -665,7 +647,6 @@ class MaureyCodec(object):
             raise ValueError("MaureyCodec: k = %d draws for a tensor of %d elements" % (self.k, numel))
         self.nbytes = native.MAUREY_HEADER_BYTES + _up(4 * self.k)
         self._rng = getattr(compressor, "_rng", "device")
-        self._single = None
 
     def uses_reference_draws(self):
         return self._rng == "reference"
@@ -673,46 +654,16 @@ class MaureyCodec(object):
     def draw_count(self):
         return self.k
 
-    def _batched1(self, dev):
-        if self._single is None or self._single.device != dev:
-            self._single = BatchedMaurey([self], [0], [0], dev, 1, self.nbytes)
-        return self._single
+    def _wire_bytes(self):
+        return self.nbytes      # (never empty: the header)
 
     def _draws(self, r, dev):
         if r is None and self.uses_reference_draws():
             r = torch.rand(self.k).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
         return (r, {0: 0}) if r is not None else None
 
-    def encode_decode_into(self, grad, wire_user, off, salt, out, r=None, seed=None):
-        """The payload into the wire and decompress(compress(grad)) into `out` (ps_quantizer.py:37), one launch sequence."""
-        _require_device(grad, "MaureyCodec.encode_decode_into")
-        flat = grad.contiguous().view(-1)
-        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt, draws=self._draws(r, flat.device), out=out.view(-1),
-                                                seed=seed)
-        assert ok, "MaureyCodec: the gradient must be a float32 tensor on the current device"
-
-    def encode_into(self, grad, wire_user, off, salt, r=None, seed=None):
-        _require_device(grad, "MaureyCodec.encode_into")
-        flat = grad.contiguous().view(-1)
-        ok = self._batched1(flat.device).encode([flat], wire_user[off:], 0, salt, draws=self._draws(r, flat.device), seed=seed)
-        assert ok, "MaureyCodec: the gradient must be a float32 tensor on the current device"
-
-    def roundtrip(self, grad, salt, r=None, seed=None):
-        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
-        tmp = torch.empty(self.nbytes, dtype=torch.uint8, device=grad.device)
-        self.encode_decode_into(grad, tmp, 0, salt, out, r=r, seed=seed)
-        return out.view(self.shape)
-
-    def decode_wire(self, wire_user, off, out):
-        self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
-
-    def _decode_rows(self, gathered, off, R, out, plain=False):
-        self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
-
-    def decode_mean(self, gathered, off, R, plain=False):
-        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
-        self._decode_rows(gathered, off, R, out, plain=plain)
-        return out.view(self.shape)
+    def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None):
+        _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out)
 
 
 _DATA_PTR = torch.Tensor.data_ptr
@@ -808,6 +759,37 @@ class _BatchedBase(object):
             else:
                 _kernel_copy(self._dev[self._table_words:self._dense_at], self._acc_init)
         self._batch.set_table(self._dev[:self._table_words])
+
+    def _choose_header(self, tensors, slot, align, errs, dense, graph_header, table_current):
+        """Where an encode's launches read their tables from.  graph_header (stream capture): a device copy of the header of
+        exactly these tensors that nobody rewrites (no events, no validation: the caller has just run the same call eagerly).
+        table_current (capture of an ADDRESS-FREE graph, PSQuantizer._capture_generic): the shared device header as it is, which
+        the caller refreshes by upload() in front of every replay -- pointers and accumulator resets -- as an eager step does.
+        Otherwise the shared header, with these tensors' pointers sent to it now; False -- nothing changed, nothing to launch
+        -- when a tensor cannot be addressed that way."""
+        if graph_header is not None:
+            self._graph_tables(graph_header, dense)
+            return True
+        if table_current:
+            self._batch.set_table(self._dev[:self._table_words])
+        elif not self._upload(tensors, slot, align, errs, dense):
+            return False
+        else:
+            self._acc_clean = False
+        self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
+        return True
+
+    def _launch(self, graph_header, defer_reset, launches, *args):
+        """launches(*args) -- an encode's launches behind _choose_header -- with the descriptor taken back from a graph's own
+        tables behind them: _graph_tables_done, or graph_tables_abort when one of them raised."""
+        try:
+            launches(*args)
+        except BaseException:
+            if graph_header is not None:
+                self.graph_tables_abort()
+            raise
+        if graph_header is not None:
+            self._graph_tables_done(defer_reset)
 
     def graph_tables_abort(self):
         """A launch failed between _graph_tables and _graph_tables_done (an invalidated capture, a launch error): the callers
@@ -1091,24 +1073,13 @@ class BatchedHSQ(_BatchedBase):
         tensor on this device: the caller then takes the per-tensor path for this step.
         With `errs` (error feedback, ps_quantizer.py:34-39) the same launches also do
         t += ef_scale*err (in place, before encoding) and err = t - decoded (in place, after).
-        graph_header (stream capture): a device copy of the header of exactly these tensors that nobody rewrites; it is
-        copied instead of the shared pinned buffers (no events, no validation: the caller has just run the same call eagerly)."""
+        graph_header, table_current: see _choose_header."""
         if self.reference_draws and draws is None:
             return False
         if self._batch.path == 0:       # e.g. more than 384 tensors of d = 8 / 32 and no exact kernel for the shape
             return False
-        if graph_header is not None:
-            self._graph_tables(graph_header, dense)
-        elif table_current:
-            # (capture of an ADDRESS-FREE graph, PSQuantizer._capture_generic: the launches read the shared device header, which
-            # the caller refreshes by upload() in front of every replay -- pointers and accumulator resets -- as an eager step does)
-            self._batch.set_table(self._dev[:self._table_words])
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        elif not self._upload(tensors, slot, self.align, errs, dense):
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        else:
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-            self._acc_clean = False
         ef = ef_scale if errs is not None else None
         counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
         try:
@@ -1310,36 +1281,24 @@ class BatchedResidual(BatchedHSQ):
             return False
         if self._batch.path == 0:
             return False
-        if graph_header is not None:
-            self._graph_tables(graph_header, dense)
-        elif table_current:
-            self._batch.set_table(self._dev[:self._table_words])
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        elif not self._upload(tensors, slot, self.align, errs, dense):
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        else:
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-            self._acc_clean = False
         ef = ef_scale if errs is not None else None
         counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
-        b = self._batch
-        try:
-            b.b1.encode(wire_user, ef)
-            mode, seed, r_flat = self._draws_for(0, salt, counter_seed, draws)
-            b.b1.levels(wire_user, mode, seed, r_flat)
-            mode, seed, r_flat = self._draws_for(1, salt, counter_seed, draws)
-            b.encode2(wire_user, mode, seed, r_flat)
-            mode, seed, r_flat = self._draws_for(2, salt, counter_seed, draws)
-            b.b2.levels(wire_user, mode, seed, r_flat)
-            if errs is not None:      # error = v - ((0 + d1) + d2)  (ps_quantizer.py:37-39)
-                b.decode(wire_user.view(1, -1), 1, None, mode=native.RQ_ERROR)
-        except BaseException:
-            if graph_header is not None:
-                self.graph_tables_abort()
-            raise
-        if graph_header is not None:
-            self._graph_tables_done(defer_reset)
+        self._launch(graph_header, defer_reset, self._launches, wire_user, ef, errs is not None, salt, counter_seed, draws)
         return True
+
+    def _launches(self, wire_user, ef, write_error, salt, counter_seed, draws):
+        b = self._batch
+        b.b1.encode(wire_user, ef)
+        mode, seed, r_flat = self._draws_for(0, salt, counter_seed, draws)
+        b.b1.levels(wire_user, mode, seed, r_flat)
+        mode, seed, r_flat = self._draws_for(1, salt, counter_seed, draws)
+        b.encode2(wire_user, mode, seed, r_flat)
+        mode, seed, r_flat = self._draws_for(2, salt, counter_seed, draws)
+        b.b2.levels(wire_user, mode, seed, r_flat)
+        if write_error:      # error = v - ((0 + d1) + d2)  (ps_quantizer.py:37-39)
+            b.decode(wire_user.view(1, -1), 1, None, mode=native.RQ_ERROR)
 
     def _range(self, lo, hi):
         if lo >= hi:
@@ -1471,18 +1430,10 @@ class BatchedQSGD(_BatchedBase):
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False):
         """With `errs`: error feedback in the same launch (t += ef_scale*err, err = t - decoded, both in place).
-        graph_header, dense, rng_slot: see BatchedHSQ.encode."""
+        graph_header, table_current: see _choose_header; dense, rng_slot: see BatchedHSQ.encode."""
         counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
-        if graph_header is not None:
-            self._graph_tables(graph_header, dense)
-        elif table_current:      # (see BatchedHSQ.encode)
-            self._batch.set_table(self._dev[:self._table_words])
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        elif not self._upload(tensors, slot, 8, errs, dense):
+        if not self._choose_header(tensors, slot, 8, errs, dense, graph_header, table_current):
             return False
-        else:
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-            self._acc_clean = False
         if self.keyed:      # gq_rng = "keyed": every bucket's draws keyed by its norm, the seed never changes
             mode, seed = native.RANDOM_DEVICE_KEYED, (salt * 0x2545F4914F6CDD1D + 0x5851F42D4C957F2D) & (2 ** 63 - 1)
         elif self.counter and counter_seed is not None:      # gq_rng = "device": keyed by the slot's device step word
@@ -1490,25 +1441,79 @@ class BatchedQSGD(_BatchedBase):
         else:
             mode = native.RANDOM_DEVICE if self.random else native.RANDOM_OFF
             seed = (_next_seed() ^ salt) if self.random else 0
-        try:
-            self._batch.compress(wire_user, mode, seed, ef_scale if errs is not None else None)
-        except BaseException:
-            if graph_header is not None:
-                self.graph_tables_abort()
-            raise
-        if graph_header is not None:
-            self._graph_tables_done(defer_reset)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, mode, seed, ef_scale if errs is not None else None)
         return True
 
 
-class BatchedTopK(_BatchedBase):
+class _ItemGroup(_BatchedBase):
+    """What BatchedTopK, BatchedSign and BatchedMaurey share: a segment table over an item table (native._ItemBatch), a compress
+    that also writes the dense decoded tensors where a caller asks for them -- which is what roundtrip returns -- and a
+    decode-mean without a step tail."""
+
+    takes_tail = False
+    align = 4
+
+    def _item_setup(self, codecs, offsets, idxs, device, slots, user_bytes, dense, items_of, columns, out_pad):
+        """The group's tables and header.  items_of(codec): the items of a tensor; columns: {column of the segment table: its
+        value per tensor} beside elements (1), first item (2), wire offset (3) and out offset (5); out_pad: a tensor's views in
+        the output buffer start on a multiple of so many floats.  Returns (tensors, items)."""
+        self.idxs = list(idxs)
+        self.codecs = [codecs[i] for i in self.idxs]
+        nseg = len(self.idxs)
+        table = torch.zeros((nseg, 8), dtype=torch.int64)
+        item_seg = []
+        item, out_off = 0, 0
+        self.out_off = []
+        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
+            items = items_of(cd)
+            table[s, 1], table[s, 2], table[s, 3], table[s, 5] = cd.numel, item, offsets[i], out_off
+            for col, values in columns.items():
+                table[s, col] = values[s]
+            item_seg += [s] * items
+            item += items
+            self.out_off.append(out_off)
+            out_off += -(-cd.numel // out_pad) * out_pad
+        self.out_floats = out_off
+        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
+        self._item_seg, self._nitems = self.item_seg, item
+        self._setup(table, None, device, slots, user_bytes, dense)
+        self._ef_out = None
+        return nseg, item
+
+    def graphable(self):
+        return True
+
+    def _ef_buffer(self, device):
+        """The decoded tensors an error-feedback record needs and nobody asked for."""
+        if self._ef_out is None or self._ef_out.device != device:
+            self._ef_out = torch.empty(self.out_floats, dtype=torch.float32, device=device)
+        return self._ef_out
+
+    def decode_into(self, gathered, R, out, plain=False):
+        """The decode-mean launch into a caller's buffer (_SparseCodec: a one-tensor group, its section at offset 0 of the rows)."""
+        if not self.ready:
+            self.upload_layout()
+        self._batch.decode(gathered, R, out, plain=plain)
+
+    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
+        """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode (the reference's signed
+        zeros and NaNs, which the wire does not carry), no decode launch.  See _BatchedBase.roundtrip."""
+        if self._tmp_wire is None:
+            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
+        out, views = self._out_buffer(self.device)
+        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
+        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, draws=draws, rng_slot=rng_slot, out=out, **kw):
+            self._out_turn ^= 1      # (the buffer was not used)
+            return None
+        return views
+
+
+class BatchedTopK(_ItemGroup):
     """All TopKSparsificationCompressor tensors in ONE gq_topk_compress_batched sequence (eight launches: three radix passes with
     a per-tensor pick behind each, counts, scan, write -- include/gq_topk.h) and ONE gq_topk_decode_sum_batched launch.  No
     draws: every launch replays from a HIP graph.  The compress also writes the dense decoded tensors (v * mask) where a caller
     asks for them: error feedback takes its residual from them, and the two-phase re-compress returns them, bit for bit the
     reference's decompress(compress(g))."""
-
-    takes_tail = False
 
     @staticmethod
     def eligible(codec):
@@ -1519,93 +1524,39 @@ class BatchedTopK(_BatchedBase):
         return ()
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
-        self.idxs = list(idxs)
-        self.codecs = [codecs[i] for i in self.idxs]
-        nseg = len(self.idxs)
-        chunk = native.TOPK_CHUNK
-        table = torch.zeros((nseg, 8), dtype=torch.int64)
-        item_seg = []
-        item, out_off = 0, 0
-        self.out_off = []
-        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
-            items = max(1, -(-cd.numel // chunk))
-            table[s, 1], table[s, 2], table[s, 3], table[s, 4], table[s, 5] = cd.numel, item, offsets[i], cd.k, out_off
-            item_seg += [s] * items
-            item += items
-            self.out_off.append(out_off)
-            out_off += cd.numel
-        self.out_floats = out_off
-        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
-        self._item_seg, self._nitems = self.item_seg, item
-        self._setup(table, None, device, slots, user_bytes, dense)
-        self.align = 4
+        # an item is a chunk of elements; a tensor's views in the output buffer are packed back to back
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                      lambda cd: max(1, -(-cd.numel // native.TOPK_CHUNK)), {4: [codecs[i].k for i in idxs]}, 1)
         self.random = False
         # the select's scratch (include/gq_topk.h): the histograms start zero and every compress leaves them zero
         self._hist = torch.zeros(nseg * native.TOPK_HIST_BINS, dtype=torch.int32, device=device)
         self._state = torch.zeros(nseg * 4, dtype=torch.int32, device=device)
         self._counts = torch.zeros(item * 2, dtype=torch.int32, device=device)
-        self._ef_out = None         # the decoded tensors an error-feedback record needs and nobody asked for
         self._batch = native.TopKBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self._hist, self._state, self._counts)
-
-    def graphable(self):
-        return True
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False, out=None):
         """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
         feedback in the same launches (t += ef_scale*err before the select, err = t - decoded after it, both in place).
-        graph_header, dense, table_current: see BatchedHSQ.encode."""
-        if graph_header is not None:
-            self._graph_tables(graph_header, dense)
-        elif table_current:
-            self._batch.set_table(self._dev[:self._table_words])
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        elif not self._upload(tensors, slot, self.align, errs, dense):
+        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        else:
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
         ef = ef_scale if errs is not None else None
         if ef is not None and out is None:
-            if self._ef_out is None or self._ef_out.device != wire_user.device:
-                self._ef_out = torch.empty(self.out_floats, dtype=torch.float32, device=wire_user.device)
-            out = self._ef_out
-        try:
-            self._batch.compress(wire_user, out, ef)
-        except BaseException:
-            if graph_header is not None:
-                self.graph_tables_abort()
-            raise
-        if graph_header is not None:
-            self._graph_tables_done(defer_reset)
+            out = self._ef_buffer(wire_user.device)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef)
         return True
 
-    def decode_into(self, gathered, R, out, plain=False):
-        """The decode-mean launch into a caller's buffer (TopKCodec: a one-tensor group, its section at offset 0 of the rows)."""
-        if not self.ready:
-            self.upload_layout()
-        self._batch.decode(gathered, R, out, plain=plain)
 
-    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
-        """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode (the reference's signed
-        zeros and NaNs, which the wire does not carry).  See _BatchedBase.roundtrip."""
-        if self._tmp_wire is None:
-            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
-        out, views = self._out_buffer(self.device)
-        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
-        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, out=out, **kw):
-            self._out_turn ^= 1      # (the buffer was not used)
-            return None
-        return views
+TopKCodec.GROUP = BatchedTopK
 
 
-class BatchedSign(_BatchedBase):
+class BatchedSign(_ItemGroup):
     """All SignSGDCompressor tensors in ONE gq_sign_compress_batched launch and ONE gq_sign_decode_sum_batched launch
     (include/gq_sign.h).  No draws and no scratch: both replay from a HIP graph.  The compress also writes the dense sign(w)
     where a caller asks for it (the two-phase re-compress returns it); with error feedback it updates the gradient and the
     residual in the same launch.  The decode-mean sums the codes as integers and divides by R: gq_mean_rows' result over the
     dense signs, bit for bit."""
-
-    takes_tail = False
 
     @staticmethod
     def eligible(codec):
@@ -1616,75 +1567,27 @@ class BatchedSign(_BatchedBase):
         return ()
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
-        self.idxs = list(idxs)
-        self.codecs = [codecs[i] for i in self.idxs]
-        nseg = len(self.idxs)
-        table = torch.zeros((nseg, 8), dtype=torch.int64)
-        item_seg = []
-        item, out_off = 0, 0
-        self.out_off = []
-        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
-            items = max(1, -(-cd.nbytes // native.SIGN_ITEM_BYTES))
-            table[s, 1], table[s, 2], table[s, 3], table[s, 5] = cd.numel, item, offsets[i], out_off
-            item_seg += [s] * items
-            item += items
-            self.out_off.append(out_off)
-            out_off += -(-cd.numel // 4) * 4      # (16-byte aligned views: the launches store float4 there)
-        self.out_floats = out_off
-        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
-        self._item_seg, self._nitems = self.item_seg, item
-        self._setup(table, None, device, slots, user_bytes, dense)
-        self.align = 4
+        # an item is a run of wire bytes; 16-byte aligned views in the output buffer: the launches store float4 there
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                      lambda cd: max(1, -(-cd.nbytes // native.SIGN_ITEM_BYTES)), {}, 4)
         self.random = False
         self._batch = native.SignBatch(self._dev[:self._table_words], self.item_seg, nseg, item)
-
-    def graphable(self):
-        return True
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False, out=None):
         """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense sign.  With `errs`: error feedback
         in the same launch (t += ef_scale*err before the sign, err = t - sign(t) after it, both in place).
-        graph_header, dense, table_current: see BatchedHSQ.encode."""
-        if graph_header is not None:
-            self._graph_tables(graph_header, dense)
-        elif table_current:
-            self._batch.set_table(self._dev[:self._table_words])
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        elif not self._upload(tensors, slot, self.align, errs, dense):
+        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        else:
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        try:
-            self._batch.compress(wire_user, out, ef_scale if errs is not None else None)
-        except BaseException:
-            if graph_header is not None:
-                self.graph_tables_abort()
-            raise
-        if graph_header is not None:
-            self._graph_tables_done(defer_reset)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None)
         return True
 
-    def decode_into(self, gathered, R, out, plain=False):
-        """The decode-mean launch into a caller's buffer (SignCodec: a one-tensor group, its section at offset 0 of the rows)."""
-        if not self.ready:
-            self.upload_layout()
-        self._batch.decode(gathered, R, out, plain=plain)
 
-    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
-        """decompress(compress(t)) for every tensor of the group: the compress launch's own dense sign, no decode launch.
-        See _BatchedBase.roundtrip."""
-        if self._tmp_wire is None:
-            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
-        out, views = self._out_buffer(self.device)
-        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
-        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, out=out, **kw):
-            self._out_turn ^= 1      # (the buffer was not used)
-            return None
-        return views
+SignCodec.GROUP = BatchedSign
 
 
-class BatchedMaurey(_BatchedBase):
+class BatchedMaurey(_ItemGroup):
     """All MaureySparsification tensors in ONE gq_maurey_compress_batched sequence (six launches: item sums, their scan, the
     draws counted, the counts' scan, the draws bucketed, the per-item placement -- include/gq_maurey.h) and ONE
     gq_maurey_decode_sum_batched launch.  Tensor s owns the draws [first draw, first draw + k) of the group's stream.  The compress
@@ -1692,8 +1595,6 @@ class BatchedMaurey(_BatchedBase):
     two-phase re-compress returns them.  gq_rng "device" with the quantizer's { seed, step } pairs: nothing in the launches changes
     from record to record, they replay from a HIP graph and draw afresh every step; "reference": the quantizer's draw plan
     (torch.rand(k) per tensor, in parameter order) as given draws; "keyed" / a group without pairs: a fresh seed per call."""
-
-    takes_tail = False
 
     @staticmethod
     def eligible(codec):
@@ -1704,27 +1605,13 @@ class BatchedMaurey(_BatchedBase):
         return (codec._rng,)
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
-        self.idxs = list(idxs)
-        self.codecs = [codecs[i] for i in self.idxs]
-        nseg = len(self.idxs)
-        chunk = native.MAUREY_CHUNK
-        table = torch.zeros((nseg, 8), dtype=torch.int64)
-        item_seg = []
-        item, out_off, draw = 0, 0, 0
-        self.out_off = []
-        for s, (i, cd) in enumerate(zip(self.idxs, self.codecs)):
-            items = -(-cd.numel // chunk)
-            table[s, 1], table[s, 2], table[s, 3], table[s, 4], table[s, 5], table[s, 6] = cd.numel, item, offsets[i], cd.k, out_off, draw
-            item_seg += [s] * items
-            item += items
-            draw += cd.k
-            self.out_off.append(out_off)
-            out_off += -(-cd.numel // 4) * 4      # (16-byte aligned views)
-        self.out_floats, self.ndraws = out_off, draw
-        self.item_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
-        self._item_seg, self._nitems = self.item_seg, item
-        self._setup(table, None, device, slots, user_bytes, dense)
-        self.align = 4
+        ks = [codecs[i].k for i in idxs]
+        first_draw = list(itertools.accumulate([0] + ks[:-1]))      # tensor s owns the draws [first, first + k) of the group's stream
+        # an item is a chunk of elements (numel >= 1: never none); 16-byte aligned views in the output buffer
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                      lambda cd: -(-cd.numel // native.MAUREY_CHUNK),
+                                      {4: ks, 6: first_draw}, 4)
+        self.ndraws = draw = sum(ks)
         rng = self.codecs[0]._rng
         self.random = True
         self.counter = rng == "device"          # the quantizer gives such a group its { seed, step } pairs (PSQuantizer._make_group)
@@ -1736,7 +1623,6 @@ class BatchedMaurey(_BatchedBase):
         self._draw_item = torch.empty(draw, dtype=torch.int32, device=device)
         self._bucket = torch.empty(draw, dtype=torch.float32, device=device)
         self._r_gather = None
-        self._ef_out = None         # the decoded tensors an error-feedback record needs and nobody asked for
         self._batch = native.MaureyBatch(self._dev[:self._table_words], self.item_seg, nseg, item, draw, self._sums, self._totals,
                                          self._counts, self._draw_item, self._bucket)
 
@@ -1759,24 +1645,16 @@ class BatchedMaurey(_BatchedBase):
         """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
         feedback in the same launches (t += ef_scale*err before the sums, err = t - decoded in the last launch, both in place).
         draws (given uniforms, see _given_draws): required for gq_rng "reference", taken in any mode when handed in.
-        seed: the device generator's seed for this call.  graph_header, dense, table_current, rng_slot: see BatchedHSQ.encode."""
+        seed: the device generator's seed for this call.  graph_header, table_current: see _choose_header; dense, rng_slot: see
+        BatchedHSQ.encode."""
         given = draws is not None and all(i in draws[1] for i in self.idxs)
         if self.reference_draws and not given:
             return False
-        if graph_header is not None:
-            self._graph_tables(graph_header, dense)
-        elif table_current:
-            self._batch.set_table(self._dev[:self._table_words])
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
-        elif not self._upload(tensors, slot, self.align, errs, dense):
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        else:
-            self._batch.set_dense(self.dense_table_dev() if dense is not None else None, self.ndense)
         ef = ef_scale if errs is not None else None
         if ef is not None and out is None:
-            if self._ef_out is None or self._ef_out.device != wire_user.device:
-                self._ef_out = torch.empty(self.out_floats, dtype=torch.float32, device=wire_user.device)
-            out = self._ef_out
+            out = self._ef_buffer(wire_user.device)
         counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
         if given:
             mode, sd, r = native.RANDOM_GIVEN, 0, self._given_draws(draws)
@@ -1786,33 +1664,11 @@ class BatchedMaurey(_BatchedBase):
             mode, sd, r = native.RANDOM_DEVICE_COUNTER, counter_seed, None
         else:
             mode, sd, r = native.RANDOM_DEVICE, _next_seed() ^ salt, None
-        try:
-            self._batch.compress(wire_user, mode, sd, r, out, ef)
-        except BaseException:
-            if graph_header is not None:
-                self.graph_tables_abort()
-            raise
-        if graph_header is not None:
-            self._graph_tables_done(defer_reset)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, mode, sd, r, out, ef)
         return True
 
-    def decode_into(self, gathered, R, out, plain=False):
-        """The decode-mean launch into a caller's buffer (MaureyCodec: a one-tensor group, its section at offset 0 of the rows)."""
-        if not self.ready:
-            self.upload_layout()
-        self._batch.decode(gathered, R, out, plain=plain)
 
-    def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
-        """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode, no decode launch.
-        See _BatchedBase.roundtrip."""
-        if self._tmp_wire is None:
-            self._tmp_wire = torch.zeros((1, max(16, self.user_bytes)), dtype=torch.uint8, device=self.device)
-        out, views = self._out_buffer(self.device)
-        kw = {"graph_header": graph_header, "defer_reset": defer_reset} if graph_header is not None else {}
-        if not self.encode(tensors, self._tmp_wire[0], slot, salt, errs, ef_scale, draws=draws, rng_slot=rng_slot, out=out, **kw):
-            self._out_turn ^= 1      # (the buffer was not used)
-            return None
-        return views
+MaureyCodec.GROUP = BatchedMaurey
 
 
 def default_codec_factory(compressor, numel, shape, packed6=False):

@@ -11,7 +11,42 @@ import os
 import torch
 
 _PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.environ.get("GQ_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_hsq.so")
+
+
+class GQNativeError(RuntimeError):
+    pass
+
+
+class Library(object):
+    """One native library as this binding expects it: its file (`env` names the variable that overrides the path), the prefix
+    of its <prefix>abi_version / <prefix>last_error, the ABI number the binding is written for, every entry point its header
+    declares and the result types that are not int.  `handle` caches the loaded library (_load)."""
+
+    def __init__(self, name, env, prefix, abi, exports, restypes=()):
+        self.name, self.prefix, self.abi, self.exports, self.restypes = name, prefix, abi, exports, tuple(restypes)
+        self.path = os.environ.get(env) or os.path.join(_PKG_DIR, name)
+        self.handle = None
+
+
+def _load(d):
+    """The library of description `d`; fails loudly if it was not built (python gradient-quantization_amd/build.py) or is stale."""
+    if d.handle is None:
+        if not os.path.exists(d.path):
+            raise GQNativeError("%s not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                "(there is no CPU fallback)" % (d.name, d.path))
+        L = ctypes.CDLL(d.path)
+        abi_version = getattr(L, d.prefix + "abi_version")
+        abi_version.restype = ctypes.c_int
+        getattr(L, d.prefix + "last_error").restype = ctypes.c_char_p
+        for name, restype in d.restypes:
+            getattr(L, name).restype = restype
+        for name in d.exports:
+            getattr(L, name)  # AttributeError if the library is stale
+        if abi_version() != d.abi:
+            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it" % (d.path, abi_version(), d.abi))
+        d.handle = L
+    return d.handle
+
 
 GQ_MAX_PARTIALS = 1024
 WS_LOG_FIRST = 2 * GQ_MAX_PARTIALS + 4      # f32-sized words in front of the workspace's log: (min, max) pairs, 4 flags (include/gq_hsq.h)
@@ -34,42 +69,24 @@ EXPORTS = [     # every entry point include/gq_hsq.h declares (tests/test_host_l
 ABI_VERSION = 5
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3      # GQ_ERR_* of include/gq_hsq.h
 
-_lib = None
-
-
-class GQNativeError(RuntimeError):
-    pass
+HSQ_LIBRARY = Library("libgq_hsq.so", "GQ_LIB_PATH", "gq_", ABI_VERSION, EXPORTS,
+                      [("gq_hsq_workspace_bytes", ctypes.c_size_t), ("gq_launch_plan_destroy", None)])
+LIB_PATH = HSQ_LIBRARY.path
 
 
 def lib():
     """Load libgq_hsq.so; fail loudly if it was not built (python gradient-quantization_amd/build.py)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise GQNativeError(
-                "libgq_hsq.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                "(there is no CPU fallback)" % LIB_PATH)
-        L = ctypes.CDLL(LIB_PATH)
-        L.gq_last_error.restype = ctypes.c_char_p
-        L.gq_abi_version.restype = ctypes.c_int
-        L.gq_hsq_workspace_bytes.restype = ctypes.c_size_t
-        L.gq_launch_plan_destroy.restype = None
-        for name in EXPORTS:
-            getattr(L, name)  # AttributeError if the library is stale
-        if L.gq_abi_version() != ABI_VERSION:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
-                                % (LIB_PATH, L.gq_abi_version(), ABI_VERSION))
-        _lib = L
-    return _lib
+    return HSQ_LIBRARY.handle or _load(HSQ_LIBRARY)
 
 
 CALLS = [0]      # entry-point calls that went through _check (each is one launch, or two for the wide QSGD compress): bench.py's `launches`
 
 
-def _check(rc, what):
+def _check(rc, what, owner=HSQ_LIBRARY):
+    """owner: the library the entry point belongs to (the failure's text is in its own *_last_error)."""
     CALLS[0] += 1
     if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, lib().gq_last_error().decode()))
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, getattr(_load(owner), owner.prefix + "last_error")().decode()))
 
 
 def _dev_ptr(t, dtype=None, name="tensor"):
@@ -276,11 +293,28 @@ class _HSQBatchStruct(ctypes.Structure):      # gq_hsq_batch (include/gq_hsq.h)
                 ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class _Tables(object):
+    """set_table / set_dense of every descriptor whose struct has seg_table, dense_table and ndense.  Every tensor whose address is
+    in the struct stays referenced for as long as the struct lives: `keep` (the constructor's), `keep_table`, `keep_dense`."""
+
+    def set_table(self, seg_table):
+        """Another copy of the segment table for the launches that follow (a captured graph's own, which nobody rewrites)."""
+        self.keep_table = seg_table
+        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
+
+    def set_dense(self, dense_table, ndense):
+        """dense_table (int64 [ndense, 3] on the device: source pointer, byte offset in one user's wire, elements): the compress
+        (HSQ: the level launch) also copies the uncompressed tensors into the wire.  None: no copies."""
+        self.keep_dense = dense_table
+        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
+        self.s.ndense = int(ndense) if dense_table is not None else 0
+
+
 _NAN = float("nan")
 BATCH_PREFILTER, BATCH_PAGED, BATCH_EXACT = 1, 2, 3
 
 
-class HSQBatch(object):
+class HSQBatch(_Tables):
     """The multi-tensor HSQ launches of one group of tensors that share a codebook: the gq_hsq_batch descriptor is
     filled ONCE (every pointer and size that does not change from step to step), a step's calls only hand over the
     wire and the stream -- ~3 us of marshalling per launch (the quantizer step is host-bound).  Which kernels serve
@@ -302,18 +336,6 @@ class HSQBatch(object):
                                  opt(seg_minmax, torch.int32, "seg_minmax"), opt(workspace, torch.float32, "workspace"), None, 0, 0)
         self.ref = ctypes.byref(self.s)
         self.path = int(self.L.gq_hsq_batched_path(self.ref))
-
-    def set_table(self, seg_table):
-        """Another copy of the segment table for the launches that follow (a captured graph's own, which nobody rewrites)."""
-        self.keep_table = seg_table
-        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
-
-    def set_dense(self, dense_table, ndense):
-        """dense_table (int64 [ndense, 3] on the device: source pointer, byte offset in one user's wire, elements): the level
-        launch also copies the uncompressed tensors into the wire.  None: no copies."""
-        self.keep_dense = dense_table
-        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
-        self.s.ndense = int(ndense) if dense_table is not None else 0
 
     def part(self, seg_table, tile_seg, nseg, ntiles):
         """The same configuration over another table (the head / tail of a split decode)."""
@@ -446,7 +468,7 @@ class _QSGDBatchStruct(ctypes.Structure):     # gq_qsgd_batch (include/gq_hsq.h)
                 ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
 
 
-class QSGDBatch(object):
+class QSGDBatch(_Tables):
     """The multi-tensor QSGD launches on the packed wire (buckets, or chunks of wide buckets: `wide`)."""
 
     def __init__(self, seg_table, item_seg, nseg, nitems, n_bit, bits, wide=False, norm_bits=None, bucket_hint=0):
@@ -458,17 +480,6 @@ class QSGDBatch(object):
                                   _dev_ptr(item_seg, torch.int32, "item_seg").value,
                                   _dev_ptr(norm_bits, torch.int32, "norm_bits").value if norm_bits is not None else None, None, 0, 0)
         self.ref = ctypes.byref(self.s)
-
-    def set_table(self, seg_table):
-        """As HSQBatch.set_table."""
-        self.keep_table = seg_table
-        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
-
-    def set_dense(self, dense_table, ndense):
-        """As HSQBatch.set_dense: the compress launch also copies the uncompressed tensors into the wire."""
-        self.keep_dense = dense_table
-        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
-        self.s.ndense = int(ndense) if dense_table is not None else 0
 
     def part(self, seg_table, item_seg, nseg, nitems):
         return QSGDBatch(seg_table, item_seg, nseg, nitems, self.s.n_bit, self.s.bits, bool(self.s.wide), self.keep[2], self.s.bucket_hint)
@@ -598,39 +609,53 @@ def qsgd_decode_sum(norm, signs, levels, d, n_bit, out, R=1):
     _check(rc, "gq_qsgd_decode_sum")
 
 
+# ---- the item-table libraries: one descriptor base for top-k, sign and Maurey ------------------------------------------------
+class _ItemBatch(_Tables):
+    """A descriptor over a segment table and an item table (item_seg names the tensor of every item) -- gq_topk_batch,
+    gq_sign_batch, gq_maurey_batch -- and its <prefix>decode_sum_batched launch.  A subclass names its library (LIBRARY) and
+    its ctypes struct (STRUCT), hands its scratch buffers to this constructor and has a compress of its own."""
+
+    LIBRARY = STRUCT = None
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, scratch=(), **sizes):
+        """scratch: ((field of the struct, int32 / float tensor or None, its dtype), ...); sizes: further integer fields."""
+        self.L = _load(self.LIBRARY)
+        self.keep = (seg_table, item_seg) + tuple(t for _, t, _ in scratch)
+        self.s = self.STRUCT(struct_bytes=ctypes.sizeof(self.STRUCT), nseg=int(nseg), nitems=int(nitems),
+                             seg_table=_dev_ptr(seg_table, torch.int64, "seg_table").value,
+                             item_seg=_dev_ptr(item_seg, torch.int32, "item_seg").value, **sizes)
+        for name, t, dtype in scratch:
+            if t is not None:
+                setattr(self.s, name, _dev_ptr(t, dtype, name).value)
+        self.ref = ctypes.byref(self.s)
+        self._decode_name = self.LIBRARY.prefix + "decode_sum_batched"
+        self._decode = getattr(self.L, self._decode_name)
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
+        return type(self)(seg_table, item_seg, nseg, nitems)
+
+    def decode(self, gathered, R, out, plain=False):
+        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
+        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
+        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
+        rc = self._decode(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R),
+                          _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0), _stream())
+        _check(rc, self._decode_name, self.LIBRARY)
+
+
 # ---- top-k sparsification: libgq_topk.so (include/gq_topk.h) ----------------------------------------------------------
-TOPK_LIB_PATH = os.environ.get("GQ_TOPK_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_topk.so")
 TOPK_ABI_VERSION = 1
 TOPK_EXPORTS = ["gq_topk_abi_version", "gq_topk_last_error", "gq_topk_compress_batched", "gq_topk_decode_sum_batched"]
 TOPK_CHUNK = 4096           # GQ_TOPK_CHUNK: elements per item
 TOPK_HIST_BINS = 2048       # GQ_TOPK_HIST_BINS: histogram words per tensor
 
-_topk_lib = None
+TOPK_LIBRARY = Library("libgq_topk.so", "GQ_TOPK_LIB_PATH", "gq_topk_", TOPK_ABI_VERSION, TOPK_EXPORTS)
+TOPK_LIB_PATH = TOPK_LIBRARY.path
 
 
 def topk_lib():
-    """Load libgq_topk.so; fail loudly if it was not built (as lib())."""
-    global _topk_lib
-    if _topk_lib is None:
-        if not os.path.exists(TOPK_LIB_PATH):
-            raise GQNativeError("libgq_topk.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                                "(there is no CPU fallback)" % TOPK_LIB_PATH)
-        L = ctypes.CDLL(TOPK_LIB_PATH)
-        L.gq_topk_last_error.restype = ctypes.c_char_p
-        L.gq_topk_abi_version.restype = ctypes.c_int
-        for name in TOPK_EXPORTS:
-            getattr(L, name)
-        if L.gq_topk_abi_version() != TOPK_ABI_VERSION:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
-                                % (TOPK_LIB_PATH, L.gq_topk_abi_version(), TOPK_ABI_VERSION))
-        _topk_lib = L
-    return _topk_lib
-
-
-def _check_topk(rc, what):
-    CALLS[0] += 1
-    if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, topk_lib().gq_topk_last_error().decode()))
+    return TOPK_LIBRARY.handle or _load(TOPK_LIBRARY)
 
 
 class _TopKBatchStruct(ctypes.Structure):     # gq_topk_batch (include/gq_topk.h)
@@ -639,34 +664,16 @@ class _TopKBatchStruct(ctypes.Structure):     # gq_topk_batch (include/gq_topk.h
                 ("counts", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
-class TopKBatch(object):
+class TopKBatch(_ItemBatch):
     """The multi-tensor top-k launches: gq_topk_compress_batched (select + compact, + the dense decoded tensors and the residual)
     and gq_topk_decode_sum_batched.  hist (int32 [nseg * TOPK_HIST_BINS], zero), state (int32 [nseg * 4]) and counts
     (int32 [nitems * 2]) are the caller's scratch; the compress leaves hist zero again."""
 
+    LIBRARY, STRUCT = TOPK_LIBRARY, _TopKBatchStruct
+
     def __init__(self, seg_table, item_seg, nseg, nitems, hist=None, state=None, counts=None):
-        self.L = topk_lib()
-        self.keep = (seg_table, item_seg, hist, state, counts)
-        ptr = lambda t, name: _dev_ptr(t, torch.int32, name).value if t is not None else None
-        self.s = _TopKBatchStruct(ctypes.sizeof(_TopKBatchStruct), int(nseg), int(nitems), _dev_ptr(seg_table, torch.int64, "seg_table").value,
-                                  _dev_ptr(item_seg, torch.int32, "item_seg").value, ptr(hist, "hist"), ptr(state, "state"),
-                                  ptr(counts, "counts"), None, 0, 0)
-        self.ref = ctypes.byref(self.s)
-
-    def set_table(self, seg_table):
-        """As HSQBatch.set_table."""
-        self.keep_table = seg_table
-        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
-
-    def set_dense(self, dense_table, ndense):
-        """As QSGDBatch.set_dense: the compress launch also copies the uncompressed tensors into the wire."""
-        self.keep_dense = dense_table
-        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
-        self.s.ndense = int(ndense) if dense_table is not None else 0
-
-    def part(self, seg_table, item_seg, nseg, nitems):
-        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
-        return TopKBatch(seg_table, item_seg, nseg, nitems)
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems,
+                            (("hist", hist, torch.int32), ("state", state, torch.int32), ("counts", counts, torch.int32)))
 
     def compress(self, wire, out=None, ef_scale=None):
         """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
@@ -674,50 +681,20 @@ class TopKBatch(object):
         rc = self.L.gq_topk_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
                                              ctypes.c_float(_NAN if ef_scale is None else ef_scale),
                                              _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check_topk(rc, "gq_topk_compress_batched")
-
-    def decode(self, gathered, R, out, plain=False):
-        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
-        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
-        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
-        rc = self.L.gq_topk_decode_sum_batched(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride),
-                                               ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
-                                               _stream())
-        _check_topk(rc, "gq_topk_decode_sum_batched")
+        _check(rc, "gq_topk_compress_batched", TOPK_LIBRARY)
 
 
 # ---- signSGD on a 2-bit wire: libgq_sign.so (include/gq_sign.h) -----------------------------------------------------------
-SIGN_LIB_PATH = os.environ.get("GQ_SIGN_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_sign.so")
 SIGN_ABI_VERSION = 1
 SIGN_EXPORTS = ["gq_sign_abi_version", "gq_sign_last_error", "gq_sign_compress_batched", "gq_sign_decode_sum_batched"]
 SIGN_ITEM_BYTES = 4096      # GQ_SIGN_ITEM_BYTES: wire bytes (16384 elements) per item
 
-_sign_lib = None
+SIGN_LIBRARY = Library("libgq_sign.so", "GQ_SIGN_LIB_PATH", "gq_sign_", SIGN_ABI_VERSION, SIGN_EXPORTS)
+SIGN_LIB_PATH = SIGN_LIBRARY.path
 
 
 def sign_lib():
-    """Load libgq_sign.so; fail loudly if it was not built (as lib())."""
-    global _sign_lib
-    if _sign_lib is None:
-        if not os.path.exists(SIGN_LIB_PATH):
-            raise GQNativeError("libgq_sign.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                                "(there is no CPU fallback)" % SIGN_LIB_PATH)
-        L = ctypes.CDLL(SIGN_LIB_PATH)
-        L.gq_sign_last_error.restype = ctypes.c_char_p
-        L.gq_sign_abi_version.restype = ctypes.c_int
-        for name in SIGN_EXPORTS:
-            getattr(L, name)
-        if L.gq_sign_abi_version() != SIGN_ABI_VERSION:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
-                                % (SIGN_LIB_PATH, L.gq_sign_abi_version(), SIGN_ABI_VERSION))
-        _sign_lib = L
-    return _sign_lib
-
-
-def _check_sign(rc, what):
-    CALLS[0] += 1
-    if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, sign_lib().gq_sign_last_error().decode()))
+    return SIGN_LIBRARY.handle or _load(SIGN_LIBRARY)
 
 
 class _SignBatchStruct(ctypes.Structure):     # gq_sign_batch (include/gq_sign.h)
@@ -726,31 +703,11 @@ class _SignBatchStruct(ctypes.Structure):     # gq_sign_batch (include/gq_sign.h
                 ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
-class SignBatch(object):
+class SignBatch(_ItemBatch):
     """The multi-tensor sign launches: gq_sign_compress_batched (2-bit codes, + the dense signs and the residual) and
     gq_sign_decode_sum_batched.  No scratch: both are one launch over the segment table."""
 
-    def __init__(self, seg_table, item_seg, nseg, nitems):
-        self.L = sign_lib()
-        self.keep = (seg_table, item_seg)
-        self.s = _SignBatchStruct(ctypes.sizeof(_SignBatchStruct), int(nseg), int(nitems), _dev_ptr(seg_table, torch.int64, "seg_table").value,
-                                  _dev_ptr(item_seg, torch.int32, "item_seg").value, None, 0, 0)
-        self.ref = ctypes.byref(self.s)
-
-    def set_table(self, seg_table):
-        """As HSQBatch.set_table."""
-        self.keep_table = seg_table
-        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
-
-    def set_dense(self, dense_table, ndense):
-        """As QSGDBatch.set_dense: the compress launch also copies the uncompressed tensors into the wire."""
-        self.keep_dense = dense_table
-        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
-        self.s.ndense = int(ndense) if dense_table is not None else 0
-
-    def part(self, seg_table, item_seg, nseg, nitems):
-        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
-        return SignBatch(seg_table, item_seg, nseg, nitems)
+    LIBRARY, STRUCT = SIGN_LIBRARY, _SignBatchStruct
 
     def compress(self, wire, out=None, ef_scale=None):
         """out: the dense sign(w) (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
@@ -758,49 +715,19 @@ class SignBatch(object):
         rc = self.L.gq_sign_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
                                              ctypes.c_float(_NAN if ef_scale is None else ef_scale),
                                              _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check_sign(rc, "gq_sign_compress_batched")
-
-    def decode(self, gathered, R, out, plain=False):
-        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
-        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
-        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
-        rc = self.L.gq_sign_decode_sum_batched(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride),
-                                               ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
-                                               _stream())
-        _check_sign(rc, "gq_sign_decode_sum_batched")
+        _check(rc, "gq_sign_compress_batched", SIGN_LIBRARY)
 
 
 # ---- the ProbabilisticVectorCompressor's multi-tensor encode: libgq_pvq.so (include/gq_pvq.h) ------------------------------
-PVQ_LIB_PATH = os.environ.get("GQ_PVQ_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_pvq.so")
 PVQ_ABI_VERSION = 1
 PVQ_EXPORTS = ["gq_pvq_abi_version", "gq_pvq_last_error", "gq_pvq_batched_serves", "gq_pvq_encode_batched"]
 
-_pvq_lib = None
+PVQ_LIBRARY = Library("libgq_pvq.so", "GQ_PVQ_LIB_PATH", "gq_pvq_", PVQ_ABI_VERSION, PVQ_EXPORTS)
+PVQ_LIB_PATH = PVQ_LIBRARY.path
 
 
 def pvq_lib():
-    """Load libgq_pvq.so; fail loudly if it was not built (as lib())."""
-    global _pvq_lib
-    if _pvq_lib is None:
-        if not os.path.exists(PVQ_LIB_PATH):
-            raise GQNativeError("libgq_pvq.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                                "(there is no CPU fallback)" % PVQ_LIB_PATH)
-        L = ctypes.CDLL(PVQ_LIB_PATH)
-        L.gq_pvq_last_error.restype = ctypes.c_char_p
-        L.gq_pvq_abi_version.restype = ctypes.c_int
-        for name in PVQ_EXPORTS:
-            getattr(L, name)
-        if L.gq_pvq_abi_version() != PVQ_ABI_VERSION:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
-                                % (PVQ_LIB_PATH, L.gq_pvq_abi_version(), PVQ_ABI_VERSION))
-        _pvq_lib = L
-    return _pvq_lib
-
-
-def _check_pvq(rc, what):
-    CALLS[0] += 1
-    if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, pvq_lib().gq_pvq_last_error().decode()))
+    return PVQ_LIBRARY.handle or _load(PVQ_LIBRARY)
 
 
 def pvq_batched_serves(d, K, code_dtype):
@@ -836,41 +763,20 @@ class PVQBatch(HSQBatch):
         rp = _dev_ptr(r_flat, torch.float32, "r_flat") if r_flat is not None else ctypes.c_void_p(0)
         rc = self.PL.gq_pvq_encode_batched(self.pref, self._wire(wire), ctypes.c_int(random_mode), ctypes.c_uint64(seed & (2 ** 64 - 1)), rp,
                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale), _stream())
-        _check_pvq(rc, "gq_pvq_encode_batched")
+        _check(rc, "gq_pvq_encode_batched", PVQ_LIBRARY)
 
 
 # ---- the ResidualCompressor's own launches: libgq_rq.so (include/gq_rq.h) ---------------------------------------------------
-RQ_LIB_PATH = os.environ.get("GQ_RQ_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_rq.so")
 RQ_ABI_VERSION = 1
 RQ_EXPORTS = ["gq_rq_abi_version", "gq_rq_last_error", "gq_rq_batched_serves", "gq_rq_encode2_batched", "gq_rq_decode_sum_batched"]
 RQ_MEAN, RQ_PLAIN, RQ_ERROR = 0, 1, 2      # GQ_RQ_* of include/gq_rq.h
 
-_rq_lib = None
+RQ_LIBRARY = Library("libgq_rq.so", "GQ_RQ_LIB_PATH", "gq_rq_", RQ_ABI_VERSION, RQ_EXPORTS)
+RQ_LIB_PATH = RQ_LIBRARY.path
 
 
 def rq_lib():
-    """Load libgq_rq.so; fail loudly if it was not built (as lib())."""
-    global _rq_lib
-    if _rq_lib is None:
-        if not os.path.exists(RQ_LIB_PATH):
-            raise GQNativeError("libgq_rq.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                                "(there is no CPU fallback)" % RQ_LIB_PATH)
-        L = ctypes.CDLL(RQ_LIB_PATH)
-        L.gq_rq_last_error.restype = ctypes.c_char_p
-        L.gq_rq_abi_version.restype = ctypes.c_int
-        for name in RQ_EXPORTS:
-            getattr(L, name)
-        if L.gq_rq_abi_version() != RQ_ABI_VERSION:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
-                                % (RQ_LIB_PATH, L.gq_rq_abi_version(), RQ_ABI_VERSION))
-        _rq_lib = L
-    return _rq_lib
-
-
-def _check_rq(rc, what):
-    CALLS[0] += 1
-    if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, rq_lib().gq_rq_last_error().decode()))
+    return RQ_LIBRARY.handle or _load(RQ_LIBRARY)
 
 
 def rq_batched_serves(d, K, code_dtype):
@@ -926,7 +832,7 @@ class RQBatch(object):
         rp = _dev_ptr(r_flat, torch.float32, "r_flat") if r_flat is not None else ctypes.c_void_p(0)
         rc = self.RL.gq_rq_encode2_batched(self.ref, self.b1._wire(wire), ctypes.c_int(random_mode), ctypes.c_uint64(seed & (2 ** 64 - 1)), rp,
                                            _stream())
-        _check_rq(rc, "gq_rq_encode2_batched")
+        _check(rc, "gq_rq_encode2_batched", RQ_LIBRARY)
 
     def decode(self, gathered, R, out, plain=False, mode=None):
         """Mean of the R payloads, each (0 + d1) + d2 (plain: the decompress of ONE payload).  mode = RQ_ERROR (one payload):
@@ -938,42 +844,21 @@ class RQBatch(object):
         op = _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0)
         rc = self.RL.gq_rq_decode_sum_batched(self.ref, self.b1._wire(gathered), ctypes.c_int64(stride), ctypes.c_int(R), op,
                                               ctypes.c_int(mode), _stream())
-        _check_rq(rc, "gq_rq_decode_sum_batched")
+        _check(rc, "gq_rq_decode_sum_batched", RQ_LIBRARY)
 
 
 # ---- Maurey sparsification on a sparse wire: libgq_maurey.so (include/gq_maurey.h) ------------------------------------------
-MAUREY_LIB_PATH = os.environ.get("GQ_MAUREY_LIB_PATH") or os.path.join(_PKG_DIR, "libgq_maurey.so")
 MAUREY_ABI_VERSION = 1
 MAUREY_EXPORTS = ["gq_maurey_abi_version", "gq_maurey_last_error", "gq_maurey_compress_batched", "gq_maurey_decode_sum_batched"]
 MAUREY_CHUNK = 4096         # GQ_MAUREY_CHUNK: elements per item
 MAUREY_HEADER_BYTES = 16    # GQ_MAUREY_HEADER_BYTES: scale + 12 zero bytes in front of a section's words
 
-_maurey_lib = None
+MAUREY_LIBRARY = Library("libgq_maurey.so", "GQ_MAUREY_LIB_PATH", "gq_maurey_", MAUREY_ABI_VERSION, MAUREY_EXPORTS)
+MAUREY_LIB_PATH = MAUREY_LIBRARY.path
 
 
 def maurey_lib():
-    """Load libgq_maurey.so; fail loudly if it was not built (as lib())."""
-    global _maurey_lib
-    if _maurey_lib is None:
-        if not os.path.exists(MAUREY_LIB_PATH):
-            raise GQNativeError("libgq_maurey.so not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                                "(there is no CPU fallback)" % MAUREY_LIB_PATH)
-        L = ctypes.CDLL(MAUREY_LIB_PATH)
-        L.gq_maurey_last_error.restype = ctypes.c_char_p
-        L.gq_maurey_abi_version.restype = ctypes.c_int
-        for name in MAUREY_EXPORTS:
-            getattr(L, name)
-        if L.gq_maurey_abi_version() != MAUREY_ABI_VERSION:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it"
-                                % (MAUREY_LIB_PATH, L.gq_maurey_abi_version(), MAUREY_ABI_VERSION))
-        _maurey_lib = L
-    return _maurey_lib
-
-
-def _check_maurey(rc, what):
-    CALLS[0] += 1
-    if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, maurey_lib().gq_maurey_last_error().decode()))
+    return MAUREY_LIBRARY.handle or _load(MAUREY_LIBRARY)
 
 
 class _MaureyBatchStruct(ctypes.Structure):   # gq_maurey_batch (include/gq_maurey.h)
@@ -983,36 +868,18 @@ class _MaureyBatchStruct(ctypes.Structure):   # gq_maurey_batch (include/gq_maur
                 ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
-class MaureyBatch(object):
+class MaureyBatch(_ItemBatch):
     """The multi-tensor Maurey launches: gq_maurey_compress_batched (the sampler's six launches, + the dense decoded tensors and
     the residual) and gq_maurey_decode_sum_batched.  sums (float64 [nitems * 4]), totals (float64 [nseg]), counts
     (int32 [nitems * 3]), draw_item (int32 [ndraws]) and bucket (float32 [ndraws]) are the caller's scratch; nothing in them
     has to be zero (include/gq_maurey.h)."""
 
+    LIBRARY, STRUCT = MAUREY_LIBRARY, _MaureyBatchStruct
+
     def __init__(self, seg_table, item_seg, nseg, nitems, ndraws=0, sums=None, totals=None, counts=None, draw_item=None, bucket=None):
-        self.L = maurey_lib()
-        self.keep = (seg_table, item_seg, sums, totals, counts, draw_item, bucket)
-        ptr = lambda t, dt, name: _dev_ptr(t, dt, name).value if t is not None else None
-        self.s = _MaureyBatchStruct(ctypes.sizeof(_MaureyBatchStruct), int(nseg), int(nitems), int(ndraws),
-                                    _dev_ptr(seg_table, torch.int64, "seg_table").value, _dev_ptr(item_seg, torch.int32, "item_seg").value,
-                                    ptr(sums, torch.float64, "sums"), ptr(totals, torch.float64, "totals"), ptr(counts, torch.int32, "counts"),
-                                    ptr(draw_item, torch.int32, "draw_item"), ptr(bucket, torch.float32, "bucket"), None, 0, 0)
-        self.ref = ctypes.byref(self.s)
-
-    def set_table(self, seg_table):
-        """As HSQBatch.set_table."""
-        self.keep_table = seg_table
-        self.s.seg_table = _dev_ptr(seg_table, torch.int64, "seg_table").value
-
-    def set_dense(self, dense_table, ndense):
-        """As QSGDBatch.set_dense: the compress's last launch also copies the uncompressed tensors into the wire."""
-        self.keep_dense = dense_table
-        self.s.dense_table = _dev_ptr(dense_table, torch.int64, "dense_table").value if dense_table is not None else None
-        self.s.ndense = int(ndense) if dense_table is not None else 0
-
-    def part(self, seg_table, item_seg, nseg, nitems):
-        """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
-        return MaureyBatch(seg_table, item_seg, nseg, nitems)
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems,
+                            (("sums", sums, torch.float64), ("totals", totals, torch.float64), ("counts", counts, torch.int32),
+                             ("draw_item", draw_item, torch.int32), ("bucket", bucket, torch.float32)), ndraws=int(ndraws))
 
     def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
         """random_mode: RANDOM_GIVEN (r: float32 [ndraws], tensor s reads r[first draw + j]), RANDOM_DEVICE (seed) or
@@ -1025,13 +892,4 @@ class MaureyBatch(object):
                                                ctypes.c_uint64(seed & (2 ** 64 - 1)),
                                                ctypes.c_float(_NAN if ef_scale is None else ef_scale),
                                                _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check_maurey(rc, "gq_maurey_compress_batched")
-
-    def decode(self, gathered, R, out, plain=False):
-        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
-        assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
-        stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
-        rc = self.L.gq_maurey_decode_sum_batched(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride),
-                                                 ctypes.c_int(R), _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0),
-                                                 _stream())
-        _check_maurey(rc, "gq_maurey_decode_sum_batched")
+        _check(rc, "gq_maurey_compress_batched", MAUREY_LIBRARY)
