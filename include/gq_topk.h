@@ -13,6 +13,7 @@
  *     decoded  = v * (kept ? 1 : 0)                                      (v * 0 = copysign(0, v), or NaN for +-inf / NaN)
  * Wire section of one tensor (at a 16-byte aligned offset of ONE user's wire): k x uint32 index, ascending, then k x f32
  * value -- 8k bytes, no header.  The bytes depend on the input alone (no draws, no dependence on workgroup scheduling).
+ * A compress writes the tensors' sections and the dense copies of dense_table and no other byte of the wire.
  */
 #ifndef GQ_TOPK_H
 #define GQ_TOPK_H
