@@ -106,9 +106,10 @@ __device__ __forceinline__ float level_to_norm<float>(float l, float, float, flo
 
 // a / b for many a and ONE b, correctly rounded, in three operations: y = RN(1/b) is computed once (a true division);
 // q0 = RN(a y) is within an ulp of the quotient, r = a - q0 b is exact in one fma, RN(q0 + r y) is the correctly
-// rounded quotient (Markstein's correction step).  Valid while nothing on the way is subnormal: the caller checks
-// 2^-80 <= b <= 2^20 and 2^-102 <= a <= b (then a/b >= 2^-122, and r, a multiple of 2^-47 ulp-units of a, is
-// representable); a == 0 would be fine too but is not worth a test.  Checked against `a / b` on 5.9e9 (a, b) pairs
+// rounded quotient (Markstein's correction step).  Valid while nothing on the way is subnormal: 2^-80 <= b <= 2^20 and
+// 2^-102 <= a <= b (then a/b >= 2^-122, and r, a multiple of 2^-47 ulp-units of a, is representable); a == 0 would be fine too
+// but is not worth a test.  The QSGD caller passes b = norm / s with s <= 2^16 and tests the NORM (quotient_window,
+// qsgd_batched.hip): 2^-64 <= norm <= 2^20, so that b >= 2^-80.  Checked against `a / b` on 5.9e9 (a, b) pairs
 // on the CPU (every mantissa of b; b with the 16 highest mantissas against every mantissa of a) and on the GPU by
 // the kernel-vs-oracle tests.  b == 0 with a == 0 gives 0 * inf = NaN like 0 / 0.
 __device__ __forceinline__ float shared_quotient(float a, float b, float y) {

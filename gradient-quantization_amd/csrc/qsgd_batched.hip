@@ -67,7 +67,7 @@ __device__ __forceinline__ unsigned qsgd_code(float v, float norm_s, float y_s, 
     return l | (sgn << (bits - 1));
 }
 // the operand window of the FAST form for a bucket norm and the smallest |v| of the lane's elements: shared_quotient needs
-// 2^-80 <= norm / s <= 2^20 (s <= 2^16) and every |v| >= 2^-102 (gq_common.hpp).  A lane that holds an exact zero next to non-zero
+// 2^-80 <= norm / s <= 2^20 (s <= 2^16: hence the test of the norm at 2^-64) and every |v| >= 2^-102 (gq_common.hpp).  A lane that holds an exact zero next to non-zero
 // elements takes the division: rare outside all-zero buckets, whose norm is outside the window anyway.
 __device__ __forceinline__ bool quotient_window(float norm, float min_abs) {
     return norm >= 0x1p-64f && norm <= 0x1p20f && min_abs >= 0x1p-102f;
@@ -417,6 +417,7 @@ __global__ __launch_bounds__(QB_THREADS) void qsgd_decode_sum_batched_kernel(
     const float s = (float)(1 << n_bit);
     const MeanDiv md = mean_div_of(R, !plain);   // the aggregate of R users (ps_quantizer.py:48)
     const unsigned lmask = (1u << (bits - 1)) - 1u;
+    const bool words = ((reinterpret_cast<uintptr_t>(gathered) | (uintptr_t)user_stride) & 3) == 0;   // the norms are aligned f32 words
     for (int64_t b = (int64_t)blockIdx.x * (QB_THREADS / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); b < nbuckets; b += nw) {
         const int seg = __builtin_amdgcn_readfirstlane(bucket_seg[b]);
         const int64_t *rec = seg_table + 8 * (int64_t)seg;
@@ -427,7 +428,13 @@ __global__ __launch_bounds__(QB_THREADS) void qsgd_decode_sum_batched_kernel(
             float a0 = 0.0f, a1 = 0.0f;
             for (int r = 0; r < R; ++r) {
                 const uint8_t *p = gathered + (int64_t)r * user_stride;
-                const float norm = reinterpret_cast<const float *>(p + rec[3])[lb];
+                float norm;
+                if (words) {
+                    norm = reinterpret_cast<const float *>(p + rec[3])[lb];
+                } else {   // (the load above is the same for the whole wave: a scalar load, which drops the low two address bits)
+                    const uint8_t *q = p + rec[3] + 4 * lb;
+                    norm = __uint_as_float((unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24));
+                }
                 unsigned c0, c1;
                 if (bits == 4) {
                     const unsigned byte = p[rec[4] + ((lb * d + e) >> 1)];
@@ -627,24 +634,28 @@ __global__ __launch_bounds__(QB_THREADS) void qsgd_decode_sum_batched4_r_kernel(
         it.out_off = rec[5] + it.lb * it.d + 8 * c0;
         return it;
     };
-    unsigned w[R][W];
+    unsigned w[R][W] = {};
     float nm[R];
     auto request = [&](const Item &it, unsigned guard, int r) {
         const uint64_t base = wire0 + (uint64_t)r * (uint64_t)user_stride;
-        // a lane without a unit in this bucket (8 * c0 >= d) reads the bucket's first word instead of one past its codes
-        const unsigned co = (8 * c0 < it.d ? it.code_off : it.code_off - (unsigned)BITS * (unsigned)c0) + guard;
-        if constexpr (BITS == 4) {
-            w[r][0] = *reinterpret_cast<gword *>(reinterpret_cast<gbyte *>(base) + co);
-        } else if constexpr (BITS == 8) {
-            const uv2 v = *reinterpret_cast<gword2 *>(reinterpret_cast<gbyte *>(base) + co);
-            w[r][0] = v[0];
-            w[r][1] = v[1];
-        } else {
-            const uv4 v = *reinterpret_cast<gword4 *>(reinterpret_cast<gbyte *>(base) + co);
-            w[r][0] = v[0];
-            w[r][1] = v[1];
-            w[r][2] = v[2];
-            w[r][3] = v[3];
+        // only a lane with a WHOLE unit in this bucket fetches one (include/gq_hsq.h: nothing behind a bucket's codes is read); what
+        // the others keep in w[r] is never stored: lanes past the bucket store nothing, widths that are no multiple of 8 are
+        // decoded by the pair walk from its own loads
+        const unsigned co = it.code_off + guard;
+        if (8 * c0 + 8 <= it.d) {
+            if constexpr (BITS == 4) {
+                w[r][0] = *reinterpret_cast<gword *>(reinterpret_cast<gbyte *>(base) + co);
+            } else if constexpr (BITS == 8) {
+                const uv2 v = *reinterpret_cast<gword2 *>(reinterpret_cast<gbyte *>(base) + co);
+                w[r][0] = v[0];
+                w[r][1] = v[1];
+            } else {
+                const uv4 v = *reinterpret_cast<gword4 *>(reinterpret_cast<gbyte *>(base) + co);
+                w[r][0] = v[0];
+                w[r][1] = v[1];
+                w[r][2] = v[2];
+                w[r][3] = v[3];
+            }
         }
         nm[r] = *reinterpret_cast<gfloat *>(reinterpret_cast<gbyte *>(base) + (it.norm_off + guard));
     };

@@ -371,6 +371,11 @@ int gq_qsgd_decode_sum(const float *norm, const uint8_t *signs, const void *leve
  * bits = gq_qsgd_code_bits(n_bit, random_mode): 4 (two codes per byte, element 2i in the low nibble)
  * when the top level is <= 7, 8 when it is <= 127, 16 (little-endian) when it is <= 32767, 0 = no packed format.
  * A zero bucket is written as level 0 (the reference's NaN level also decodes to 0).
+ * A codes section that is READ (gq_qsgd_decode_sum_batched, gq_qsgd_decode_sum_batched_tail) needs NO readable byte behind it,
+ * unlike a GQ_LEVELS_PACKED6 section: the decode kernels fetch a bucket's codes as whole units of 8 (4, 8 or 16 bytes) only where
+ * the bucket holds the whole unit, and the rest of a bucket whose width is no multiple of 8 -- at most 6 codes: 3, 6 or 12
+ * bytes -- a pair of codes at a time.  A wire may end with its last bucket's last code; the compress writes exactly
+ * nbuckets * d * bits / 8 bytes per section and 4 bytes per norm.
  *
  * wide == 0: the unit of work is a bucket; buckets are numbered across tensors: item_seg int32[nitems] names the
  *   tensor of each bucket; seg_table int64[nseg][8] = { grad pointer (8-byte aligned), d (even, <= 65536), first
@@ -388,6 +393,9 @@ int gq_qsgd_decode_sum(const float *norm, const uint8_t *signs, const void *leve
  * ef_scale: NaN = none; otherwise error feedback in the same pass (ps_quantizer.py:35-39): the bucket is read as
  *   v = grad + ef_scale*error, v is written back over grad and error = v - decode(code) over error.
  * plain: as gq_hsq_decode_sum_batched.
+ * Alignment of the decode: the bucketed form takes any even `gathered` and user_stride_bytes and an `out` that is 8-byte aligned;
+ * alignment only picks the kernel, the results are the same.  Wide buckets: `gathered` and user_stride_bytes multiples of 4, `out`
+ * of 16, GQ_ERR_INVALID_ARG otherwise.
  */
 #define GQ_QSGD_WIDE_CHUNK 1024
 typedef struct gq_qsgd_batch {

@@ -908,9 +908,9 @@ def test_batched_qsgd_compress_divides_like_the_reference_at_every_scale(span, o
 @pytest.mark.parametrize("d,n_bit", [(128, 2), (128, 1), (32, 2), (8, 4), (256, 6), (512, 2), (64, 8), (16, 5), (2048, 2), (24, 2)])
 def test_batched_qsgd_shared_quotient_equals_the_division_over_the_exponent_range(d, n_bit, oracle):
     """Round 6: |v| / norm comes from ONE reciprocal per bucket and Markstein's correction inside the operand window
-    (2^-80 <= norm <= 2^20, every non-zero |v| of the lane >= 2^-102) and from the true division outside it
-    (qsgd_batched.hip: qsgd_code<FAST>, quotient_window).  Buckets with norms from 2^-140 to 2^60 -- the window's two ends to the
-    ulp among them --, elements up to 2^-70 below their bucket's norm, exact zeros, zero buckets, NaN: the wire's
+    (2^-64 <= norm <= 2^20 -- norm / s >= 2^-80 --, every |v| of the lane >= 2^-102) and from the true division outside it
+    (qsgd_batched.hip: qsgd_code<FAST>, quotient_window).  Buckets with norms from 2^-140 to 2^60 -- 2^-80 and the window's upper
+    end to the ulp among them; the lower end, 2^-64, to the ulp: tests/test_gpu_qsgd_contract.py --, elements up to 2^-70 below their bucket's norm, exact zeros, zero buckets, NaN: the wire's
     decode equals the oracle's decompress(compress(g)) (qsgd_compressor.py:49-53,66-71) bit for bit, NaN for NaN."""
     from gq_amd.compressors import QSGDCompressor
     from gq_amd.quantizers import QSGDCodec
