@@ -11,6 +11,7 @@
 // (hsq_encode_pf.hip).
 #include "hsq_encode_common.hpp"
 #include "hsq_levels_common.hpp"
+#include "hsq_decode_common.hpp"
 #include <type_traits>
 
 namespace gq {
@@ -30,7 +31,6 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_levels_batched_kernel(
     uint64_t seed, const float *__restrict__ r_flat, uint8_t *__restrict__ wire, const int64_t *__restrict__ dense_table, int ndense) {
     resolve_seed(random_mode, seed);
     copy_dense_segments(dense_table, ndense, wire);
-    const float s = (float)(1 << n_bit), smax = s - 1.0f;
     const int64_t total4 = ntiles * 16;
     const int64_t stride = (int64_t)gridDim.x * BT_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x; i < total4; i += stride) {
@@ -46,9 +46,8 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_levels_batched_kernel(
             lbub[0] = lb;
             lbub[1] = ub;
         }
-        const float range = ub - lb;
-        const bool flat = (lb - ub) == 0.0f;
-        const uint64_t sd = random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, lb, ub) : seed;
+        const LevelQuant lq(lb, ub, n_bit, random_mode, r_flat,
+                            random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, lb, ub) : seed);
         const f32x4 uu = *reinterpret_cast<const f32x4 *>(u_flat + 4 * i);
         typename std::conditional<std::is_same<LevelT, Packed6>::value, int, LevelT>::type out[4];   // Packed6: past-the-end slots stay 0
 #pragma unroll
@@ -57,18 +56,7 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_levels_batched_kernel(
                 out[e] = uu[e];
                 continue;
             }
-            int l = 0;
-            if (!flat) {
-                const float q = (uu[e] - lb) / range;
-                const float x = fabsf(q) * s;
-                const float c = fminf(fmaxf(x, 0.0f), smax);
-                l = (x != x) ? INT32_MIN : (int)c;   // clamp(NaN) stays NaN and NaN -> int32 is INT_MIN in the reference (x86)
-                if (random_mode != GQ_RANDOM_OFF) {   // GIVEN: the reference's draws, laid out like u_flat
-                    const float prob = x - (float)l;
-                    const float rr = random_mode == GQ_RANDOM_GIVEN ? r_flat[4 * i + e] : uniform01(sd, (uint64_t)(4 * i + e));
-                    l += (prob > rr) ? 1 : 0;
-                }
-            }
+            const int l = lq.level(uu[e], 4 * i + e);   // GIVEN: the reference's draws, laid out like u_flat
             if constexpr (std::is_same<LevelT, Packed6>::value)
                 out[e] = local + e < m ? l : 0;
             else
@@ -95,20 +83,18 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_levels_batched_kernel(
 //     error = grad - codebook[code] * (l*(ub-lb)/2^n_bit + lb)
 // into the error buffer named by seg_table[seg][7] (skipped when 0).  `grad` is what the EF encode
 // left there (grad + scale*error_old).  One thread per (padded subvector, quarter); the four
-// threads of a subvector compute the same level, quarter 0 stores it.
-template <bool PACKED6>
+// threads of a subvector compute the same level, quarter 0 stores it.  Packed 6-bit levels
+// (GQ_LEVELS_PACKED6) only: byte and 16-bit levels go a wave per tile (hsq_levels_ef_tile_kernel).
 __global__ __launch_bounds__(BT_THREADS) void hsq_levels_ef_batched_kernel(
     const int64_t *__restrict__ seg_table, const int32_t *__restrict__ tile_seg, int64_t ntiles,
     const float *__restrict__ u_flat, const unsigned *__restrict__ seg_minmax, int n_bit, int random_mode,
     uint64_t seed, const float *__restrict__ r_flat, const float *__restrict__ cb, int K, uint8_t *__restrict__ wire, const int64_t *__restrict__ dense_table, int ndense) {
     resolve_seed(random_mode, seed);
     copy_dense_segments(dense_table, ndense, wire);
-    // rows 20 floats apart: an odd number of 16-byte units spreads the random-row gathers over the banks
-    __shared__ __attribute__((aligned(16))) float s_cb[256 * 20];
-    for (int i = threadIdx.x; i < K * 16 / 4; i += BT_THREADS)   // (K <= 256 rows; codes stay below K)
-        *reinterpret_cast<f32x4 *>(s_cb + (i >> 2) * 20 + 4 * (i & 3)) = reinterpret_cast<const f32x4 *>(cb)[i];
+    __shared__ __attribute__((aligned(16))) float s_cb[256 * cb_row_stride(16)];
+    stage_cb_rows<16, BT_THREADS>(s_cb, cb, K);
     __syncthreads();
-    const float s = (float)(1 << n_bit), smax = s - 1.0f;
+    const float inv_s = 1.0f / (float)(1 << n_bit);
     const int64_t total = ntiles * 64 * 4;
     const int64_t stride = (int64_t)gridDim.x * BT_THREADS;
     for (int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x; i < total; i += stride) {
@@ -120,44 +106,28 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_levels_ef_batched_kernel(
         const int64_t local = (tile - rec[2]) * 64 + (g & 63);
         if (local >= rec[1]) continue;
         const float lb = order_unmap_f(seg_minmax[2 * seg]), ub = order_unmap_f(seg_minmax[2 * seg + 1]);
-        const float range = ub - lb;
-        int l = 0;
-        if ((lb - ub) != 0.0f) {
-            const float x = fabsf((u_flat[g] - lb) / range) * s;
-            const float c = fminf(fmaxf(x, 0.0f), smax);
-            l = (x != x) ? INT32_MIN : (int)c;   // clamp(NaN) stays NaN and NaN -> int32 is INT_MIN in the reference (x86)
-            if (random_mode != GQ_RANDOM_OFF) {   // GIVEN: the reference's draws, laid out like u_flat
-                const float prob = x - (float)l;
-                const float rr = random_mode == GQ_RANDOM_GIVEN ? r_flat[g] : uniform01(random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, lb, ub) : seed, (uint64_t)g);
-                l += (prob > rr) ? 1 : 0;
-            }
+        const LevelQuant lq(lb, ub, n_bit, random_mode, r_flat,
+                            random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, lb, ub) : seed);
+        const int l = lq.level(u_flat[g], g);   // GIVEN: the reference's draws, laid out like u_flat
+        if (q == 0 && local == 0) {
+            float *lbub = reinterpret_cast<float *>(wire + rec[5]);
+            lbub[0] = lb;
+            lbub[1] = ub;
         }
-        if (q == 0) {
-            if constexpr (!PACKED6) wire[rec[4] + local] = (uint8_t)l;
-            if (local == 0) {
-                float *lbub = reinterpret_cast<float *>(wire + rec[5]);
-                lbub[0] = lb;
-                lbub[1] = ub;
-            }
-        }
-        if constexpr (PACKED6) {
-            // the four subvectors of a group sit in 16 consecutive lanes (4 quarters each; groups never straddle a
-            // tile); the group's first lane collects their levels.  Lanes of subvectors past the tensor's end have left
-            // the loop (`continue` above), so their levels are read as 0 through the ballot.
-            const int lane = threadIdx.x & 63, base = lane & ~15;
-            const int l1 = __shfl(l, base + 4, 64), l2 = __shfl(l, base + 8, 64), l3 = __shfl(l, base + 12, 64);
-            const int64_t m = rec[1];
-            if ((lane & 15) == 0)
-                store_packed6(wire + rec[4] + 3 * (local >> 2), l, local + 1 < m ? l1 : 0, local + 2 < m ? l2 : 0,
-                              local + 3 < m ? l3 : 0);
-        }
+        // the four subvectors of a group sit in 16 consecutive lanes (4 quarters each; groups never straddle a
+        // tile); the group's first lane collects their levels.  Lanes of subvectors past the tensor's end have left
+        // the loop (`continue` above), so their levels are read as 0 through the ballot.
+        const int lane = threadIdx.x & 63, base = lane & ~15;
+        const int l1 = __shfl(l, base + 4, 64), l2 = __shfl(l, base + 8, 64), l3 = __shfl(l, base + 12, 64);
+        const int64_t m = rec[1];
+        if ((lane & 15) == 0)
+            store_packed6(wire + rec[4] + 3 * (local >> 2), l, local + 1 < m ? l1 : 0, local + 2 < m ? l2 : 0,
+                          local + 3 < m ? l3 : 0);
         float *err = reinterpret_cast<float *>(rec[7]);
         if (!err) continue;
-        float n = (float)l * range;   // prob_scalar:31-32, unfused
-        n = n / s;
-        n = n + lb;
+        const float n = level_to_norm<int>(l, lb, lq.range, inv_s);
         const int code = wire[rec[3] + local];
-        const f32x4 c = *reinterpret_cast<const f32x4 *>(s_cb + code * 20 + 4 * q);
+        const f32x4 c = *reinterpret_cast<const f32x4 *>(s_cb + code * cb_row_stride(16) + 4 * q);
         const f32x4 v = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(rec[0]) + local * 16 + 4 * q);
         f32x4 e;
         e[0] = v[0] - c[0] * n;
@@ -173,12 +143,10 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_decode_sum_batched_kernel(
     const int64_t *__restrict__ seg_table, const int32_t *__restrict__ tile_seg, int64_t ntiles,
     const uint8_t *__restrict__ gathered, int64_t user_stride, int R, const float *__restrict__ cb, int K, int n_bit,
     float *__restrict__ out, int plain) {
-    // rows 20 floats apart: an odd number of 16-byte units spreads the random-row gathers over the banks
-    __shared__ __attribute__((aligned(16))) float s_cb[256 * 20];
-    for (int i = threadIdx.x; i < K * 16 / 4; i += BT_THREADS)   // (K <= 256 rows; codes stay below K)
-        *reinterpret_cast<f32x4 *>(s_cb + (i >> 2) * 20 + 4 * (i & 3)) = reinterpret_cast<const f32x4 *>(cb)[i];
+    __shared__ __attribute__((aligned(16))) float s_cb[256 * cb_row_stride(16)];
+    stage_cb_rows<16, BT_THREADS>(s_cb, cb, K);
     __syncthreads();
-    const float s = (float)(1 << n_bit);
+    const float inv_s = 1.0f / (float)(1 << n_bit);
     const MeanDiv md = mean_div_of(R, !plain);   // the aggregate of R users (ps_quantizer.py:48) unless the caller asked for the plain decode
     const int64_t total = ntiles * 64 * 4;
     const int64_t stride = (int64_t)gridDim.x * BT_THREADS;
@@ -196,10 +164,8 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_decode_sum_batched_kernel(
             const int code = p[rec[3] + local];
             const float *lbub = reinterpret_cast<const float *>(p + rec[5]);
             const float lb = lbub[0], range = lbub[1] - lb;
-            float n = (float)p[rec[4] + local] * range;   // prob_scalar:31-32, unfused
-            n = n / s;
-            n = n + lb;
-            const f32x4 c = *reinterpret_cast<const f32x4 *>(s_cb + code * 20 + 4 * q);
+            const float n = level_to_norm<uint8_t>(p[rec[4] + local], lb, range, inv_s);
+            const f32x4 c = *reinterpret_cast<const f32x4 *>(s_cb + code * cb_row_stride(16) + 4 * q);
             f32x4 dec;
             dec[0] = c[0] * n;
             dec[1] = c[1] * n;
@@ -226,61 +192,8 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_decode_sum_batched_kernel(
 
 // The d = 16 / K = 256 multi-tensor decode-mean is built like the per-tensor one (hsq_decode.hip,
 // hsq_decode_sum_d16u8_r_kernel): a thread produces one quarter of FOUR consecutive padded subvectors (they share a
-// tile, hence a tensor); the codebook is staged four times (row r, copy c at byte r*256 + c*64) and the four 4-lane
-// teams of every ds_read_b128 lane group read copies 0..3.  Helpers first, the kernels below.
-
-// LDS byte address of a codebook row for this lane: [0, 0, code_k, lane_const] by one v_perm_b32
-template <int K4>
-__device__ __forceinline__ unsigned bt4_row_addr(unsigned c4, unsigned lane_const) {
-    return __builtin_amdgcn_perm(c4, lane_const, 0x0c0c0000u | ((4u + K4) << 8));
-}
-
-typedef const f32x4 __attribute__((address_space(3))) bt4_lds_f32x4;
-template <bool FIRST, bool PACKED6, bool ABS0 = false, bool FMA = false>   // ABS0: the image starts at LDS address 0; FMA: opt-in fused accumulation (see dec16_payload)
-__device__ __forceinline__ void bt4_payload(f32x4 (&acc)[4], unsigned c4, unsigned l4, float lb, float ub, float inv_s, int q,
-                                            const char *cb_bytes, unsigned lane_const) {
-    const float range = ub - lb;
-    // lane q of a team works out the norm of subvector q; the team shares them by quad-permute DPP moves
-    const unsigned lq = PACKED6 ? ((l4 >> (6 * q)) & 63u) : ((l4 >> (8 * q)) & 255u);
-    float n_own = (float)lq * range;   // prob_scalar:31-32, unfused
-    n_own = n_own * inv_s;                                   // == / 2^n_bit exactly
-    n_own = n_own + lb;
-    const int n_bits = __builtin_bit_cast(int, n_own);
-    const float n_team[4] = {
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0x00, 0xF, 0xF, true)),
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0x55, 0xF, 0xF, true)),
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0xAA, 0xF, 0xF, true)),
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0xFF, 0xF, 0xF, true))};
-    const unsigned a[4] = {bt4_row_addr<0>(c4, lane_const), bt4_row_addr<1>(c4, lane_const), bt4_row_addr<2>(c4, lane_const),
-                           bt4_row_addr<3>(c4, lane_const)};
-    if constexpr (FMA && !FIRST) {      // one v_fmac_f32_dpp per element: the team's norms are read across the quad by the multiply-add itself
-        const float n_rdy = quad_norm_ready(n_own);
-        const f32x4 c0 = ABS0 ? *reinterpret_cast<bt4_lds_f32x4 *>((uintptr_t)a[0]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[0]);
-        const f32x4 c1 = ABS0 ? *reinterpret_cast<bt4_lds_f32x4 *>((uintptr_t)a[1]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[1]);
-        const f32x4 c2 = ABS0 ? *reinterpret_cast<bt4_lds_f32x4 *>((uintptr_t)a[2]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[2]);
-        const f32x4 c3 = ABS0 ? *reinterpret_cast<bt4_lds_f32x4 *>((uintptr_t)a[3]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[3]);
-        acc[0] = fmac_quad4<0>(acc[0], n_rdy, c0);
-        acc[1] = fmac_quad4<1>(acc[1], n_rdy, c1);
-        acc[2] = fmac_quad4<2>(acc[2], n_rdy, c2);
-        acc[3] = fmac_quad4<3>(acc[3], n_rdy, c3);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float n = n_team[k];
-        const f32x4 c = ABS0 ? *reinterpret_cast<bt4_lds_f32x4 *>((uintptr_t)a[k])
-                             : *reinterpret_cast<const f32x4 *>(cb_bytes + a[k]);
-        const f32x4 n4 = {n, n, n, n};
-        const f32x4 dec = c * n4;
-        if constexpr (FIRST) {
-            acc[k] = dec;
-        } else {
-            acc[k] = acc[k] + dec;
-        }
-    }
-}
-
-// The same for a compile-time payload count R <= BT4_RMAX, software-pipelined across a wave's tiles like
+// tile, hence a tensor), on the four-copy codebook image, one payload at a time by dec16_payload (hsq_decode_common.hpp).
+// A compile-time payload count R <= BT4_RMAX, software-pipelined across a wave's tiles like
 // hsq_decode_sum_d16u8_r_kernel (hsq_decode.hip): a wave's 64 items are exactly one tile, so the segment record of a tile
 // is wave-uniform -- it is fetched by scalar loads two tiles ahead, the (code, level) words and (lb, ub) of the NEXT tile
 // are re-requested into the registers of the payload just consumed, and the stores of a tile drain under the next
@@ -327,7 +240,7 @@ void hsq_decode_sum_batched4_r_kernel(
     const int64_t *__restrict__ seg_table, const int32_t *__restrict__ tile_seg, int64_t ntiles,
     const uint8_t *__restrict__ gathered, int64_t user_stride, const float *__restrict__ cb, int K, int n_bit,
     float *__restrict__ out, int plain, const StepTail tail) {
-    extern __shared__ __attribute__((aligned(16))) float s_cb4[];   // [256][4 copies][16] at LDS address 0 (bt4_payload<.., ABS0>)
+    extern __shared__ __attribute__((aligned(16))) float s_cb4[];   // [256][4 copies][16] at LDS address 0 (dec16_payload<.., ABS0>)
     step_tail_run(tail);
     constexpr int THREADS = bt4r_threads(R);
     const float inv_s = 1.0f / (float)(1 << n_bit);
@@ -383,19 +296,9 @@ void hsq_decode_sum_batched4_r_kernel(
         for (int r = 0; r < R; ++r) request_lbub(cur, r);
     }
     {
-        constexpr int STAGE = (256 * 16 + THREADS - 1) / THREADS;
-        f32x4 stage[STAGE];
-#pragma unroll
-        for (int n = 0; n < STAGE; ++n) {
-            const int e = threadIdx.x + n * THREADS;   // (row, copy, quarter)
-            if (e < K * 16) stage[n] = *reinterpret_cast<const f32x4 *>(cb + (e >> 4) * 16 + 4 * (e & 3));
-        }
-#pragma unroll
-        for (int n = 0; n < STAGE; ++n) {
-            const int e = threadIdx.x + n * THREADS;
-            const int row = e >> 4, c = (e >> 2) & 3, qq = e & 3;
-            if (e < K * 16) *reinterpret_cast<f32x4 *>(s_cb4 + row * 64 + c * 16 + 4 * qq) = stage[n];
-        }
+        Cb4Stage<THREADS> stage;
+        stage.load(cb, K);
+        stage.store(s_cb4, K);
     }
     __syncthreads();
     if (!active) return;
@@ -408,9 +311,9 @@ void hsq_decode_sum_batched4_r_kernel(
         for (int r = 0; r < R; ++r) {
             const unsigned c4 = team_word(cw[r >> 2], r & 3), l4 = team_word(lw[r >> 2], r & 3);
             if (r == 0)
-                bt4_payload<true, PACKED6, true>(acc, c4, l4, lb[r], ub[r], inv_s, q, cb_bytes, lane_const);
+                dec16_payload<true, PACKED6, true>(acc, c4, l4, lb[r], ub[r] - lb[r], inv_s, q, cb_bytes, lane_const);
             else
-                bt4_payload<false, PACKED6, true, FMA>(acc, c4, l4, lb[r], ub[r], inv_s, q, cb_bytes, lane_const);
+                dec16_payload<false, PACKED6, true, FMA>(acc, c4, l4, lb[r], ub[r] - lb[r], inv_s, q, cb_bytes, lane_const);
             // keep each re-request behind the payload it replaces (hoisted to the top of the trip, the new words were
             // spilled until their registers came free): the lane offset is made to "depend" on the payload's last sum.
             // No instruction; a sched_barrier or a volatile asm counts as a store and turns the scalar (lb, ub) loads into vector loads
@@ -515,19 +418,9 @@ void hsq_decode_sum_batched4_rc_kernel(
         for (int jj = 0; jj < C; ++jj) request(cur, gl, 0, jj);
     }
     {
-        constexpr int STAGE = (256 * 16 + THREADS - 1) / THREADS;
-        f32x4 stage[STAGE];
-#pragma unroll
-        for (int n = 0; n < STAGE; ++n) {
-            const int e = threadIdx.x + n * THREADS;
-            if (e < K * 16) stage[n] = *reinterpret_cast<const f32x4 *>(cb + (e >> 4) * 16 + 4 * (e & 3));
-        }
-#pragma unroll
-        for (int n = 0; n < STAGE; ++n) {
-            const int e = threadIdx.x + n * THREADS;
-            const int row = e >> 4, c = (e >> 2) & 3, qq = e & 3;
-            if (e < K * 16) *reinterpret_cast<f32x4 *>(s_cb4 + row * 64 + c * 16 + 4 * qq) = stage[n];
-        }
+        Cb4Stage<THREADS> stage;
+        stage.load(cb, K);
+        stage.store(s_cb4, K);
     }
     __syncthreads();
     if (!active) return;
@@ -544,7 +437,7 @@ void hsq_decode_sum_batched4_rc_kernel(
                 const int r = chunk * C + jj;
                 if (r < R) {
                     const float *lbub = reinterpret_cast<const float *>(gathered + (int64_t)r * user_stride + (int64_t)cur.lbub_off);
-                    bt4_payload<false, PACKED6, true>(acc, c4[jj], l4[jj], lbub[0], lbub[1], inv_s, q, cb_bytes, lane_const);
+                    dec16_payload<false, PACKED6, true>(acc, c4[jj], l4[jj], lbub[0], lbub[1] - lbub[0], inv_s, q, cb_bytes, lane_const);
                 }
                 if (last)
                     request(nxt, gl_nxt, 0, jj);
@@ -626,70 +519,6 @@ static void launch_bt4_fixed_r(int R, const int64_t *seg_table, const int32_t *t
     }
 }
 
-// Error-feedback level kernel for the other prefilter sub-dimensions (D = 8, 32): as
-// hsq_levels_ef_batched_kernel, one thread per (padded subvector, 4-float unit).
-template <int D>
-__global__ __launch_bounds__(BT_THREADS) void hsq_levels_ef_batched_d_kernel(
-    const int64_t *__restrict__ seg_table, const int32_t *__restrict__ tile_seg, int64_t ntiles,
-    const float *__restrict__ u_flat, const unsigned *__restrict__ seg_minmax, int n_bit, int random_mode,
-    uint64_t seed, const float *__restrict__ r_flat, const float *__restrict__ cb, int K, uint8_t *__restrict__ wire, const int64_t *__restrict__ dense_table, int ndense) {
-    resolve_seed(random_mode, seed);
-    copy_dense_segments(dense_table, ndense, wire);
-    constexpr int UPS = D / 4;
-    constexpr int RS = ((D / 4) & 1) ? D : D + 4;
-    __shared__ __attribute__((aligned(16))) float s_cb[256 * RS];
-    for (int i = threadIdx.x; i < K * UPS; i += BT_THREADS)   // (K <= 256 rows; codes stay below K)
-        *reinterpret_cast<f32x4 *>(s_cb + (i / UPS) * RS + 4 * (i % UPS)) = reinterpret_cast<const f32x4 *>(cb)[i];
-    __syncthreads();
-    const float s = (float)(1 << n_bit), smax = s - 1.0f;
-    const int64_t total = ntiles * 64 * UPS;
-    const int64_t stride = (int64_t)gridDim.x * BT_THREADS;
-    for (int64_t i = (int64_t)blockIdx.x * BT_THREADS + threadIdx.x; i < total; i += stride) {
-        const int64_t g = i / UPS;
-        const int q = (int)(i % UPS);
-        const int64_t tile = g >> 6;
-        const int seg = tile_seg[tile];
-        const int64_t *rec = seg_table + 8 * (int64_t)seg;
-        const int64_t local = (tile - rec[2]) * 64 + (g & 63);
-        if (local >= rec[1]) continue;
-        const float lb = order_unmap_f(seg_minmax[2 * seg]), ub = order_unmap_f(seg_minmax[2 * seg + 1]);
-        const float range = ub - lb;
-        int l = 0;
-        if ((lb - ub) != 0.0f) {
-            const float x = fabsf((u_flat[g] - lb) / range) * s;
-            const float c = fminf(fmaxf(x, 0.0f), smax);
-            l = (x != x) ? INT32_MIN : (int)c;   // clamp(NaN) stays NaN and NaN -> int32 is INT_MIN in the reference (x86)
-            if (random_mode != GQ_RANDOM_OFF) {   // GIVEN: the reference's draws, laid out like u_flat
-                const float prob = x - (float)l;
-                const float rr = random_mode == GQ_RANDOM_GIVEN ? r_flat[g] : uniform01(random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, lb, ub) : seed, (uint64_t)g);
-                l += (prob > rr) ? 1 : 0;
-            }
-        }
-        if (q == 0) {
-            wire[rec[4] + local] = (uint8_t)l;
-            if (local == 0) {
-                float *lbub = reinterpret_cast<float *>(wire + rec[5]);
-                lbub[0] = lb;
-                lbub[1] = ub;
-            }
-        }
-        float *err = reinterpret_cast<float *>(rec[7]);
-        if (!err) continue;
-        float n = (float)l * range;   // prob_scalar:31-32, unfused
-        n = n / s;
-        n = n + lb;
-        const int code = wire[rec[3] + local];
-        const f32x4 c = *reinterpret_cast<const f32x4 *>(s_cb + code * RS + 4 * q);
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(reinterpret_cast<const float *>(rec[0]) + local * D + 4 * q);
-        f32x4 e;
-        e[0] = v[0] - c[0] * n;
-        e[1] = v[1] - c[1] * n;
-        e[2] = v[2] - c[2] * n;
-        e[3] = v[3] - c[3] * n;
-        *reinterpret_cast<f32x4 *>(err + local * D + 4 * q) = e;
-    }
-}
-
 // decode-mean over a segment table for K = 256 and D = 8 / 16 / 32 with byte or 16-bit levels (main.py:90-92's own defaults
 // -- c_dim 32, n_bit 8, stochastic rounding -- reach level 256: the levels travel as int16): a WAVE per tile of 64 padded
 // subvectors.  Round 4 ran one thread per (subvector, 16-byte unit) -- every thread fetched its tensor's record, the
@@ -707,9 +536,6 @@ constexpr int DT_RB = 4;    // ... of which this many are read back from LDS tog
 // gq_step_tail.ticket of gq_hsq_levels_decode_batched: (1 + GQ_TICKET_SHARDS) counters GQ_TICKET_STRIDE words apart (include/gq_hsq.h: GQ_TICKET_WORDS)
 #define GQ_TICKET_SHARDS 16
 #define GQ_TICKET_STRIDE 32
-#ifndef GQ_EF_LEVELS_TILE
-#define GQ_EF_LEVELS_TILE 1   // 0: round 4's one-thread-per-unit error-feedback level kernels (A/B builds)
-#endif
 // RB: payloads whose loads go out together (4 for R >= 4, 2 for R = 2 / 3); 0: the one-by-one loops alone (fewer registers:
 // R = 1 ran 3-8 % slower with the batch code merely present).
 template <int D, typename LevelT, int RB>
@@ -720,11 +546,10 @@ __global__ __launch_bounds__(DT_THREADS) void hsq_decode_sum_batched_tile_kernel
     step_tail_run(tail);
     constexpr int DT_RBK = RB > 0 ? RB : 1;
     constexpr int UPS = D / 4;                               // 16-byte units per subvector = passes per tile
-    constexpr int RS = ((D / 4) & 1) ? D : D + 4;            // LDS row stride in floats: an odd number of 16-byte units
+    constexpr int RS = cb_row_stride(D);                     // LDS row stride in floats: an odd number of 16-byte units
     __shared__ __attribute__((aligned(16))) float s_cb[256 * RS];
     __shared__ __attribute__((aligned(8))) unsigned s_pair[DT_WAVES * DT_RCH * 64 * 2];   // { code, bits of the norm } per (wave, payload of the chunk, subvector)
-    for (int i = threadIdx.x; i < K * UPS; i += DT_THREADS)   // (K <= 256 rows; codes stay below K)
-        *reinterpret_cast<f32x4 *>(s_cb + (i / UPS) * RS + 4 * (i % UPS)) = reinterpret_cast<const f32x4 *>(cb)[i];
+    stage_cb_rows<D, DT_THREADS>(s_cb, cb, K);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const float inv_s = 1.0f / (float)(1 << n_bit);
@@ -769,22 +594,20 @@ __global__ __launch_bounds__(DT_THREADS) void hsq_decode_sum_batched_tile_kernel
             int rb = 0;
             for (; RB > 0 && rb + DT_RBK <= nr; rb += DT_RBK) {
                 unsigned code_[DT_RBK];
-                float lvl_[DT_RBK], lb_[DT_RBK], ub_[DT_RBK];
+                LevelT lvl_[DT_RBK];
+                float lb_[DT_RBK], ub_[DT_RBK];
 #pragma unroll
                 for (int k = 0; k < DT_RBK; ++k) {
                     const uint8_t *p = gathered + (int64_t)(r0 + rb + k) * user_stride;
                     const float *lbub = reinterpret_cast<const float *>(p + lbub_off);
                     lb_[k] = lbub[0];
                     ub_[k] = lbub[1];
-                    lvl_[k] = (float)reinterpret_cast<const LevelT *>(p + level_off)[sv0 + lsv];
+                    lvl_[k] = reinterpret_cast<const LevelT *>(p + level_off)[sv0 + lsv];
                     code_[k] = p[code_off + lsv];
                 }
 #pragma unroll
                 for (int k = 0; k < DT_RBK; ++k) {
-                    const float lb = lb_[k], range = ub_[k] - lb;
-                    float n = lvl_[k] * range;   // prob_scalar:31-32, unfused
-                    n = n * inv_s;               // == / 2^n_bit exactly
-                    n = n + lb;
+                    const float n = level_to_norm<LevelT>(lvl_[k], lb_[k], ub_[k] - lb_[k], inv_s);
                     *reinterpret_cast<uint2 *>(pairs + ((rb + k) * 64 + lane) * 2) = make_uint2(code_[k], __float_as_uint(n));
                 }
             }
@@ -792,9 +615,7 @@ __global__ __launch_bounds__(DT_THREADS) void hsq_decode_sum_batched_tile_kernel
                 const uint8_t *p = gathered + (int64_t)(r0 + rb) * user_stride;
                 const float *lbub = reinterpret_cast<const float *>(p + lbub_off);
                 const float lb = lbub[0], range = lbub[1] - lb;
-                float n = (float)reinterpret_cast<const LevelT *>(p + level_off)[sv0 + lsv] * range;
-                n = n * inv_s;
-                n = n + lb;
+                const float n = level_to_norm<LevelT>(reinterpret_cast<const LevelT *>(p + level_off)[sv0 + lsv], lb, range, inv_s);
                 const unsigned code = p[code_off + lsv];
                 *reinterpret_cast<uint2 *>(pairs + (rb * 64 + lane) * 2) = make_uint2(code, __float_as_uint(n));
             }
@@ -889,14 +710,13 @@ __global__ __launch_bounds__(DT_THREADS) void hsq_levels_ef_tile_kernel(
     }
     const MeanDiv md = mean_div_of(1, !plain);
     constexpr int UPS = D / 4;
-    constexpr int RS = ((D / 4) & 1) ? D : D + 4;
+    constexpr int RS = cb_row_stride(D);
     __shared__ __attribute__((aligned(16))) float s_cb[256 * RS];
     __shared__ __attribute__((aligned(8))) unsigned s_pair[DT_WAVES * 64 * 2];   // { code, bits of the norm } per (wave, subvector)
-    for (int i = threadIdx.x; i < K * UPS; i += DT_THREADS)   // (K <= 256 rows; codes stay below K)
-        *reinterpret_cast<f32x4 *>(s_cb + (i / UPS) * RS + 4 * (i % UPS)) = reinterpret_cast<const f32x4 *>(cb)[i];
+    stage_cb_rows<D, DT_THREADS>(s_cb, cb, K);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const float s = (float)(1 << n_bit);
+    const float inv_s = 1.0f / (float)(1 << n_bit);
     auto uniform64 = [](int64_t v) {
         const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(uint64_t)v);
         const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((uint64_t)v >> 32));
@@ -954,10 +774,7 @@ __global__ __launch_bounds__(DT_THREADS) void hsq_levels_ef_tile_kernel(
             }
         }
         if (!OUT && !err) continue;                        // (wave-uniform: a tensor without an error buffer gets its levels only)
-        const float range = ub - lb;
-        float n = (float)l * range;   // prob_scalar:31-32, unfused
-        n = n / s;
-        n = n + lb;
+        const float n = level_to_norm<int>(l, lb, lq.range, inv_s);
         *reinterpret_cast<uint2 *>(pairs + lane * 2) = make_uint2(code, __float_as_uint(n));
         __builtin_amdgcn_wave_barrier();   // (written and read by this wave only: LDS operations of a wave stay in order)
         const float *const grad = reinterpret_cast<const float *>(r_grad) + sv0 * D;
@@ -1069,12 +886,7 @@ __global__ __launch_bounds__(BT_THREADS) void hsq_decode_sum_batched_any_kernel(
                 const uint8_t *p = gathered + (int64_t)r * user_stride;
                 const float *lbub = reinterpret_cast<const float *>(p + rec[5]);
                 const float lb = lbub[0], range = lbub[1] - lb;
-                float n = (float)reinterpret_cast<const LevelT *>(p + rec[4])[local];
-                if constexpr (!std::is_same<LevelT, float>::value) {
-                    n = n * range;   // prob_scalar:31-32, unfused
-                    n = n * inv_s;
-                    n = n + lb;
-                }
+                const float n = level_to_norm<LevelT>(reinterpret_cast<const LevelT *>(p + rec[4])[local], lb, range, inv_s);   // (f32 norms travel as they are)
                 const int64_t code = (int64_t)reinterpret_cast<const CodeT *>(p + rec[3])[local];
                 const vec_t c = *reinterpret_cast<const vec_t *>(cbp + code * d + VEC * q);
                 const vec_t dec = c * n;
@@ -1183,14 +995,11 @@ GQ_INTERNAL int gqi_hsq_levels_batched_d16(const int64_t *seg_table, const int32
     const dim3 block(gq::BT_THREADS);
     hipStream_t st = gq::as_stream(stream);
     if (ef_codebook && packed6)
-        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_kernel<true>, dim3((unsigned)gq::bt_grid(ntiles * 256)), block, 0, st,
+        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_kernel, dim3((unsigned)gq::bt_grid(ntiles * 256)), block, 0, st,
                            seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, ef_codebook, K, wire, dense_table, ndense);
-    else if (ef_codebook && GQ_EF_LEVELS_TILE)
+    else if (ef_codebook)
         gq::launch_levels_ef_tile<16, uint8_t>(seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, ef_codebook, K, wire,
                                                dense_table, ndense, st);
-    else if (ef_codebook)
-        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_kernel<false>, dim3((unsigned)gq::bt_grid(ntiles * 256)), block, 0, st,
-                           seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, ef_codebook, K, wire, dense_table, ndense);
     else if (packed6)
         hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<gq::Packed6>, dim3((unsigned)gq::bt_grid(ntiles * 16)), block, 0, st,
                            seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, wire, dense_table, ndense);
@@ -1298,21 +1107,12 @@ GQ_INTERNAL int gqi_hsq_levels_batched_ef_d(const int64_t *seg_table, const int3
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_hsq_levels_batched: GQ_RANDOM_GIVEN needs r_flat");
     if (((int64_t)1 << n_bit) - (random_mode == GQ_RANDOM_OFF ? 1 : 0) > 255)
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_hsq_levels_batched: levels do not fit uint8");
-    if (GQ_EF_LEVELS_TILE && (d == 8 || d == 32)) {
-        if (d == 8)
-            gq::launch_levels_ef_tile<8, uint8_t>(seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, codebook, K, wire,
-                                                  dense_table, ndense, gq::as_stream(stream));
-        else
-            gq::launch_levels_ef_tile<32, uint8_t>(seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, codebook, K, wire,
-                                                   dense_table, ndense, gq::as_stream(stream));
-    } else if (d == 8) {
-        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_d_kernel<8>, dim3((unsigned)gq::bt_grid(ntiles * 64 * 2)),
-                           dim3(gq::BT_THREADS), 0, gq::as_stream(stream), seg_table, tile_seg, ntiles, u_flat, seg_minmax,
-                           n_bit, random_mode, seed, r_flat, codebook, K, wire, dense_table, ndense);
+    if (d == 8) {
+        gq::launch_levels_ef_tile<8, uint8_t>(seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, codebook, K, wire,
+                                              dense_table, ndense, gq::as_stream(stream));
     } else if (d == 32) {
-        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_d_kernel<32>, dim3((unsigned)gq::bt_grid(ntiles * 64 * 8)),
-                           dim3(gq::BT_THREADS), 0, gq::as_stream(stream), seg_table, tile_seg, ntiles, u_flat, seg_minmax,
-                           n_bit, random_mode, seed, r_flat, codebook, K, wire, dense_table, ndense);
+        gq::launch_levels_ef_tile<32, uint8_t>(seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, codebook, K, wire,
+                                               dense_table, ndense, gq::as_stream(stream));
     } else {
         return gq::fail(GQ_ERR_UNSUPPORTED, "gq_hsq_levels_batched: the fused error-feedback form serves d = 8, 16 or 32 (K = 256)");
     }

@@ -10,17 +10,14 @@
 #include "gq_common.hpp"
 #include "hsq_encode_common.hpp"
 #include "hsq_levels_common.hpp"
+#include "hsq_decode_common.hpp"
 #include <type_traits>
 
 namespace gq {
 
 constexpr int DEC_THREADS = 256;
 
-// LDS row stride (floats) of a staged codebook.  Rows of d floats laid end to end start on very few
-// bank positions (d = 16: 64 B rows, the 128 B bank window has TWO), and a gather of 16 random rows
-// per ds_read_b128 then serialises ~8 ways (PMC: 16 conflict cycles per LDS instruction, LDS stalled 61 %
-// of an R = 8 decode).  An odd number of 16-byte units per row spreads the row starts over all positions.
-__host__ __device__ inline int cb_row_stride(int d) { return ((d >> 2) & 1) ? d : d + 4; }
+// (cb_row_stride, the LDS row stride of a staged codebook, is in hsq_decode_common.hpp)
 
 // (level_to_norm -- probabilistic_scalar_compressor.py:31-32 -- is in gq_common.hpp: libgq_rq.so evaluates it too)
 
@@ -81,10 +78,8 @@ __global__ __launch_bounds__(DEC_THREADS) void hsq_decode_sum_v4_kernel(
 // rate (PMC: 16 conflict cycles per ds_read_b128; R = 8 took 69-80 us for 100 MB).  Here
 //  * one thread produces the same quarter (4 floats) of FOUR consecutive subvectors: two dword loads
 //    per payload bring its 4 codes and 4 levels;
-//  * the codebook is staged FOUR times, row r copy c at byte r*256 + c*64.  A ds_read_b128 is served in
-//    four fixed groups of 16 lanes (MI355X_MICROARCH.md, LDS): the four 4-lane teams of a group
-//    (one subvector each, 64 contiguous bytes) read copies 0..3, so every group covers the 64 banks
-//    exactly once whatever the codes are: conflict-free, 256 B/clk;
+//  * the codebook is staged FOUR times, row r copy c at byte r*256 + c*64, so that every ds_read_b128 lane group covers
+//    the 64 banks exactly once whatever the codes are (hsq_decode_common.hpp: stage_cb4, dec16_payload);
 //  * packed f32 multiplies / adds (separate roundings, as the reference).
 // Same arithmetic and summation order as the kernels above.
 constexpr int DEC16_THREADS = 1024;
@@ -97,60 +92,6 @@ constexpr int DEC16_LBUB = 64;
 #endif
 constexpr int DEC16_CHUNK = GQ_DEC16_CHUNK;   // payloads whose words are requested together
 
-// LDS byte address of a codebook row for this lane: code * 256 + (copy * 64 + quarter * 16), built by ONE v_perm_b32
-// from byte k of the packed codes and the lane's constant (< 256): [0, 0, code_k, lane_const].
-template <int K4>
-__device__ __forceinline__ unsigned row_addr(unsigned c4, unsigned lane_const) {
-    return __builtin_amdgcn_perm(c4, lane_const, 0x0c0c0000u | ((4u + K4) << 8));
-}
-
-// One payload's contribution to the four subvectors of a team (see the kernel): norms by lane q, shared through
-// quad-permute DPP moves; probabilistic_scalar_compressor.py:31-32 unfused, nearest_neighbor_compressor.py:88.
-// ABS0: the codebook image starts at LDS address 0 (a kernel whose only LDS is its dynamic array) and the v_perm_b32
-// result IS the address; through a pointer the compiler adds the array's link-time base (0) to every row address.
-typedef const f32x4 __attribute__((address_space(3))) lds_f32x4;
-// FMA (opt-in, GQ_AGGREGATE_FMA in n_bit; payloads after the first): acc = fma(c, n, acc) instead of the reference's
-// separately rounded product and sum -- half the operations per payload, within 1e-6 relative L2 of the exact mean
-// (north_star grants 1e-5 on the decoded aggregate); never used for a plain decompress, R = 1 or error-feedback round trips.
-template <bool FIRST, bool PACKED6, bool ABS0 = false, bool FMA = false>
-__device__ __forceinline__ void dec16_payload(f32x4 (&acc)[4], unsigned c4, unsigned l4, float lb, float range, float inv_s,
-                                              int q, const char *cb_bytes, unsigned lane_const) {
-    const float n_own = level_to_norm<unsigned>(PACKED6 ? ((l4 >> (6 * q)) & 63u) : ((l4 >> (8 * q)) & 255u), lb, range, inv_s);
-    const int n_bits = __builtin_bit_cast(int, n_own);
-    const float n_team[4] = {   // quad_perm [k,k,k,k]: lane k of the team broadcasts
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0x00, 0xF, 0xF, true)),
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0x55, 0xF, 0xF, true)),
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0xAA, 0xF, 0xF, true)),
-        __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(n_bits, 0xFF, 0xF, 0xF, true))};
-    const unsigned a[4] = {row_addr<0>(c4, lane_const), row_addr<1>(c4, lane_const), row_addr<2>(c4, lane_const),
-                           row_addr<3>(c4, lane_const)};
-    if constexpr (FMA && !FIRST) {      // one v_fmac_f32_dpp per element: the team's norms are read across the quad by the multiply-add itself
-        const float n_rdy = quad_norm_ready(n_own);
-        const f32x4 c0 = ABS0 ? *reinterpret_cast<lds_f32x4 *>((uintptr_t)a[0]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[0]);
-        const f32x4 c1 = ABS0 ? *reinterpret_cast<lds_f32x4 *>((uintptr_t)a[1]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[1]);
-        const f32x4 c2 = ABS0 ? *reinterpret_cast<lds_f32x4 *>((uintptr_t)a[2]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[2]);
-        const f32x4 c3 = ABS0 ? *reinterpret_cast<lds_f32x4 *>((uintptr_t)a[3]) : *reinterpret_cast<const f32x4 *>(cb_bytes + a[3]);
-        acc[0] = fmac_quad4<0>(acc[0], n_rdy, c0);
-        acc[1] = fmac_quad4<1>(acc[1], n_rdy, c1);
-        acc[2] = fmac_quad4<2>(acc[2], n_rdy, c2);
-        acc[3] = fmac_quad4<3>(acc[3], n_rdy, c3);
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float n = n_team[k];
-        const f32x4 c = ABS0 ? *reinterpret_cast<lds_f32x4 *>((uintptr_t)a[k])
-                             : *reinterpret_cast<const f32x4 *>(cb_bytes + a[k]);
-        const f32x4 n4 = {n, n, n, n};
-        const f32x4 dec = c * n4;
-        if constexpr (FIRST) {
-            acc[k] = dec;
-        } else {
-            acc[k] = acc[k] + dec;
-        }
-    }
-}
-
 // Payloads are taken DEC16_CHUNK at a time: the 2 x DEC16_CHUNK dwords of a chunk are requested back to back and
 // only then consumed.  (Round 2 fetched a payload's two words inside the payload loop: every payload waited out its
 // own round trip to HBM, R of them in a row per item, and the kernel's time was write time PLUS R x 2.1 us --
@@ -162,10 +103,7 @@ void hsq_decode_sum_d16u8_kernel(
     int64_t code_stride, int64_t level_stride, int64_t lbub_stride, const float *__restrict__ cb, int R, int64_t M,
     int K, int n_bit, float *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float s_cb[];   // [K][4 copies][16]
-    for (int i = threadIdx.x; i < K * 16; i += DEC16_THREADS) {   // (row, copy, quarter)
-        const int row = i >> 4, c = (i >> 2) & 3, q = i & 3;
-        *reinterpret_cast<f32x4 *>(s_cb + row * 64 + c * 16 + 4 * q) = *reinterpret_cast<const f32x4 *>(cb + row * 16 + 4 * q);
-    }
+    stage_cb4<DEC16_THREADS>(s_cb, cb, K);
     // (lb, ub - lb) of the first DEC16_LBUB payloads once per workgroup: read per payload as a uniform
     // scalar load, every s_waitcnt lgkmcnt for it also drained the LDS gathers in flight
     __shared__ float2 s_lbub[DEC16_LBUB];
@@ -326,13 +264,8 @@ void hsq_decode_sum_d16u8_r_kernel(
 #pragma unroll
         for (int j = 0; j < NW; ++j) request_group(i, j);
     }
-    constexpr int STAGE = 256 * 16 / DEC16_THREADS;   // K <= 256 rows of four 16-byte quarters
-    f32x4 stage[STAGE];
-#pragma unroll
-    for (int n = 0; n < STAGE; ++n) {
-        const int e = threadIdx.x + n * DEC16_THREADS;   // (row, copy, quarter)
-        if (e < K * 16) stage[n] = *reinterpret_cast<const f32x4 *>(cb + (e >> 4) * 16 + 4 * (e & 3));
-    }
+    Cb4Stage<DEC16_THREADS> stage;
+    stage.load(cb, K);
     float lb[R], range[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -340,12 +273,7 @@ void hsq_decode_sum_d16u8_r_kernel(
         lb[r] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, l)));
         range[r] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, u - l)));
     }
-#pragma unroll
-    for (int n = 0; n < STAGE; ++n) {
-        const int e = threadIdx.x + n * DEC16_THREADS;
-        const int row = e >> 4, c = (e >> 2) & 3, q = e & 3;
-        if (e < K * 16) *reinterpret_cast<f32x4 *>(s_cb + row * 64 + c * 16 + 4 * q) = stage[n];
-    }
+    stage.store(s_cb, K);
     __syncthreads();
     const float inv_s = 1.0f / (float)(1 << (n_bit & 31));
     const MeanDiv md = mean_div_of(R);
@@ -444,10 +372,7 @@ void hsq_decode_sum_d16u8_rc_kernel(
     int n_bit, float *__restrict__ out) {
     constexpr int C = 8;   // payloads per chunk
     extern __shared__ __attribute__((aligned(16))) float s_cb[];   // [K][4 copies][16] at LDS address 0, then (lb, ub - lb) of the R payloads
-    for (int i = threadIdx.x; i < K * 16; i += DEC16_THREADS) {   // (row, copy, quarter)
-        const int row = i >> 4, c = (i >> 2) & 3, q = i & 3;
-        *reinterpret_cast<f32x4 *>(s_cb + row * 64 + c * 16 + 4 * q) = *reinterpret_cast<const f32x4 *>(cb + row * 16 + 4 * q);
-    }
+    stage_cb4<DEC16_THREADS>(s_cb, cb, K);
     float2 *const s_lbub = reinterpret_cast<float2 *>(s_cb + K * 64);
     for (int r = threadIdx.x; r < R; r += DEC16_THREADS) {
         const float lb = lb_ub[r * lbub_stride];
@@ -642,13 +567,8 @@ void hsq_levels_decode_d16u8_kernel(
     }
     const int final_flag = ws_counter(partials)[2];
     const float2 part = reinterpret_cast<const float2 *>(partials)[threadIdx.x];
-    constexpr int STAGE = 256 * 16 / DEC16_THREADS;
-    f32x4 stage[STAGE];
-#pragma unroll
-    for (int n = 0; n < STAGE; ++n) {
-        const int e = threadIdx.x + n * DEC16_THREADS;
-        if (e < K * 16) stage[n] = *reinterpret_cast<const f32x4 *>(cb + (e >> 4) * 16 + 4 * (e & 3));
-    }
+    Cb4Stage<DEC16_THREADS> stage;
+    stage.load(cb, K);
     float *const s_red = s_cb + K * 64;
     {
         float lo = wave_min(part.x), hi = wave_max(part.y);
@@ -658,12 +578,7 @@ void hsq_levels_decode_d16u8_kernel(
             s_red[16 + (threadIdx.x >> 6)] = hi;
         }
     }
-#pragma unroll
-    for (int n = 0; n < STAGE; ++n) {
-        const int e = threadIdx.x + n * DEC16_THREADS;
-        const int row = e >> 4, c = (e >> 2) & 3, qq = e & 3;
-        if (e < K * 16) *reinterpret_cast<f32x4 *>(s_cb + row * 64 + c * 16 + 4 * qq) = stage[n];
-    }
+    stage.store(s_cb, K);
     __syncthreads();
     float lb, ub;
     if (final_flag != 0) {   // the caller's final pair (gq_hsq.h)

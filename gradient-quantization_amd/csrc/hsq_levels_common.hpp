@@ -1,5 +1,9 @@
-// The scalar level quantiser of probabilistic_scalar_compressor.py:12-27 as ONE device function, shared by the level
-// kernel (hsq_levels.hip) and the fused levels + decode kernel (hsq_decode.hip) so that both give the same bits.
+// The scalar level quantiser of probabilistic_scalar_compressor.py:12-27 as ONE device function, so that every kernel that
+// quantises a projection gives the same bits:
+//   hsq_levels.hip    hsq_levels_kernel
+//   hsq_decode.hip    hsq_levels_decode_d16u8_kernel (levels + decode of one payload)
+//   hsq_batched.hip   hsq_levels_batched_kernel, hsq_levels_ef_batched_kernel, hsq_levels_ef_tile_kernel (one LevelQuant per
+//                     item or tile: lb / ub are per tensor; under GQ_RANDOM_DEVICE_KEYED the caller passes keyed_seed())
 // Compile with -ffp-contract=off: sub, IEEE divide, exact * 2^n_bit, truncation are separate roundings like the reference's
 // elementwise ops.
 #pragma once
@@ -10,7 +14,7 @@ namespace gq {
 struct LevelQuant {
     float lb, ub, range, s, smax;
     bool flat;          // lb == ub: prob_scalar:15-16 -> all zeros
-    int random_mode;    // GQ_RANDOM_OFF / GIVEN / DEVICE
+    int random_mode;    // GQ_RANDOM_OFF / GIVEN / anything else: DEVICE, with `seed` as the caller resolved it
     const float *r;     // GIVEN: the caller's draws, indexed like the projections
     uint64_t seed;      // DEVICE: counter-based generator
 
