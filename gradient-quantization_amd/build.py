@@ -24,6 +24,7 @@ LIBS = {
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],      # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean
     os.path.join(HERE, "libgq_maurey.so"): ["maurey.hip"],        # Maurey sparsification: the sampler's six launches and the decode-mean
+    os.path.join(HERE, "libgq_kmeans.so"): ["kmeans.hip"],        # Lloyd k-means for training codebooks (gq_amd.codebook.train_codebook)
 }
 # -ffp-contract=off: the reference's elementwise ops are separately rounded; hipcc's
 # default ("fast") would fuse the decode's mul/add and the level quantiser's sub/div.

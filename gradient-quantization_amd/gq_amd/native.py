@@ -893,3 +893,53 @@ class MaureyBatch(_ItemBatch):
                                                ctypes.c_float(_NAN if ef_scale is None else ef_scale),
                                                _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
         _check(rc, "gq_maurey_compress_batched", MAUREY_LIBRARY)
+
+
+# ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
+KMEANS_ABI_VERSION = 1
+KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]
+KMEANS_EUCLID, KMEANS_ABSDOT = 0, 1     # GQ_KMEANS_EUCLID / GQ_KMEANS_ABSDOT
+KMEANS_GLOBAL_ATOMICS = 0x100           # GQ_KMEANS_GLOBAL_ATOMICS: OR-ed into the metric of kmeans_run (the same bits; for timing)
+KMEANS_METRICS = {"euclid": KMEANS_EUCLID, "absdot": KMEANS_ABSDOT}
+KMEANS_MAX_D, KMEANS_MAX_K, KMEANS_MAX_N = 64, 4096, 1 << 22
+KMEANS_THREADS, KMEANS_BLOCKS_PER_CU = 256, 2
+
+KMEANS_LIBRARY = Library("libgq_kmeans.so", "GQ_KMEANS_LIB_PATH", "gq_kmeans_", KMEANS_ABI_VERSION, KMEANS_EXPORTS,
+                         [("gq_kmeans_workspace_bytes", ctypes.c_size_t)])
+KMEANS_LIB_PATH = KMEANS_LIBRARY.path
+
+
+def kmeans_lib():
+    return KMEANS_LIBRARY.handle or _load(KMEANS_LIBRARY)
+
+
+def kmeans_workspace_bytes(K, d):
+    return int(kmeans_lib().gq_kmeans_workspace_bytes(ctypes.c_int(int(K)), ctypes.c_int(int(d))))
+
+
+def _opt_ptr(t, dtype, name):
+    return _dev_ptr(t, dtype, name) if t is not None else ctypes.c_void_p(0)
+
+
+def kmeans_assign(X, C, metric, labels, signs=None):
+    """One assignment of the points X (float32 [N, d]) to the centroids C (float32 [K, d]): labels int32 [N], signs int8 [N]
+    (optional).  metric: KMEANS_EUCLID or KMEANS_ABSDOT."""
+    (N, d), K = X.shape, C.shape[0]
+    assert C.shape[1] == d and labels.numel() == N and (signs is None or signs.numel() == N)
+    rc = kmeans_lib().gq_kmeans_assign(_dev_ptr(X, torch.float32, "X"), ctypes.c_int64(N), ctypes.c_int(d),
+                                       _dev_ptr(C, torch.float32, "C"), ctypes.c_int(K), ctypes.c_int(metric),
+                                       _dev_ptr(labels, torch.int32, "labels"), _opt_ptr(signs, torch.int8, "signs"), _stream())
+    _check(rc, "gq_kmeans_assign", KMEANS_LIBRARY)
+
+
+def kmeans_run(X, C, metric, iters, labels, counts, workspace, signs=None):
+    """`iters` Lloyd iterations on C in place (include/gq_kmeans.h).  labels int32 [N], signs int8 [N] (optional) and counts
+    int64 [K] are those of the last assignment; workspace: int64, kmeans_workspace_bytes(K, d) bytes, any content."""
+    (N, d), K = X.shape, C.shape[0]
+    assert C.shape[1] == d and labels.numel() == N and counts.numel() == K and (signs is None or signs.numel() == N)
+    assert workspace.numel() * workspace.element_size() >= kmeans_workspace_bytes(K, d), "k-means workspace too small"
+    rc = kmeans_lib().gq_kmeans_run(_dev_ptr(X, torch.float32, "X"), ctypes.c_int64(N), ctypes.c_int(d),
+                                    _dev_ptr(C, torch.float32, "C"), ctypes.c_int(K), ctypes.c_int(metric), ctypes.c_int(iters),
+                                    _dev_ptr(labels, torch.int32, "labels"), _opt_ptr(signs, torch.int8, "signs"),
+                                    _dev_ptr(counts, torch.int64, "counts"), _dev_ptr(workspace, torch.int64, "workspace"), _stream())
+    _check(rc, "gq_kmeans_run", KMEANS_LIBRARY)
