@@ -10,7 +10,7 @@ device memory, through gq_amd.native).
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
     MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
-    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedSign / BatchedMaurey
+    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -1523,16 +1523,19 @@ class BatchedTopK(_ItemGroup):
     def group_key(codec):
         return ()
 
+    OUT_PAD = 1                 # a tensor's views in the output buffer are packed back to back
+    BATCH = native.TopKBatch
+
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
-        # an item is a chunk of elements; a tensor's views in the output buffer are packed back to back
+        # an item is a chunk of elements
         nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
-                                      lambda cd: max(1, -(-cd.numel // native.TOPK_CHUNK)), {4: [codecs[i].k for i in idxs]}, 1)
+                                      lambda cd: max(1, -(-cd.numel // native.TOPK_CHUNK)), {4: [codecs[i].k for i in idxs]}, self.OUT_PAD)
         self.random = False
         # the select's scratch (include/gq_topk.h): the histograms start zero and every compress leaves them zero
         self._hist = torch.zeros(nseg * native.TOPK_HIST_BINS, dtype=torch.int32, device=device)
         self._state = torch.zeros(nseg * 4, dtype=torch.int32, device=device)
         self._counts = torch.zeros(item * 2, dtype=torch.int32, device=device)
-        self._batch = native.TopKBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self._hist, self._state, self._counts)
+        self._batch = self.BATCH(self._dev[:self._table_words], self.item_seg, nseg, item, self._hist, self._state, self._counts)
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False, out=None):
@@ -1549,6 +1552,68 @@ class BatchedTopK(_ItemGroup):
 
 
 TopKCodec.GROUP = BatchedTopK
+
+
+class BatchedDGC(BatchedTopK):
+    """BatchedTopK with momentum correction and momentum factor masking (Deep Gradient Compression; include/gq_dgc.h): a record is
+    gq_dgc_accumulate_batched (u <- m * u + g, also into the group's scratch), the top-k sequence in its error-feedback form at
+    scale 1 over that scratch and v, and gq_dgc_mask_batched (u <- +0 at the indices just sent).  The gradients are read only.
+    The group's own table carries the gradients' addresses, as BatchedTopK's does; the select reads ONE user's state table --
+    scratch, u, v and the layout, built once per set of state buffers and never freed or moved (captured graphs hold its
+    address) -- so nothing but the accumulate launch follows the
+    gradients.  Wire, decode-mean, graph machinery and the plain compress (no state handed in: the two-phase re-compress of the
+    mean, which has no momentum) are BatchedTopK's.
+    encode's `errs` is the state, ([u per tensor], [v per tensor]) of one user, and `ef_scale` the momentum."""
+
+    OUT_PAD = 4                 # 16-byte aligned tensors in the scratch: the accumulate launch stores float4 there
+    BATCH = native.DGCBatch
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        BatchedTopK.__init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense)
+        self._scratch = torch.empty(max(4, self.out_floats), dtype=torch.float32, device=device)
+        self._state_tables = {}
+
+    def _state_table(self, us, vs):
+        """The device table of these state buffers (include/gq_dgc.h: state_table), or None when they cannot be addressed."""
+        key = (tuple(map(_DATA_PTR, us)), tuple(map(_DATA_PTR, vs)))
+        tab = self._state_tables.get(key)
+        if tab is None:
+            dev_index = self.device.index if self.device.index is not None else torch._C._cuda_getDevice()
+            for ts in (us, vs):
+                if (len(ts) != self.nseg or not all(map(_IS_CONTIGUOUS, ts)) or set(map(_DTYPE_OF, ts)) != _F32_ONLY
+                        or set(map(_GET_DEVICE, ts)) != {dev_index} or any(t.numel() != cd.numel for t, cd in zip(ts, self.codecs))):
+                    return None
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("BatchedDGC: a state table is built by an eager record, not under stream capture")
+            host = self._layout.clone()
+            base = self._scratch.data_ptr()
+            for s in range(self.nseg):
+                host[s, 0], host[s, 6], host[s, 7] = base + 4 * self.out_off[s], key[0][s], key[1][s]
+            tab = self._state_tables[key] = (host.view(-1).to(self.device), list(us), list(vs))      # (the buffers stay alive with their table)
+        return tab[0]
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None):
+        """errs = ([u], [v]) of one user, ef_scale = m: one record with momentum correction into that user's wire.  errs None:
+        BatchedTopK.encode (plain top-k).  graph_header, table_current, dense: see BatchedTopK.encode."""
+        if errs is None:
+            return BatchedTopK.encode(self, tensors, wire_user, slot, salt, None, None, draws, graph_header, dense, defer_reset, rng_slot,
+                                      table_current, out)
+        table = self._state_table(*errs)
+        if table is None or not self._choose_header(tensors, slot, self.align, None, dense, graph_header, table_current):
+            return False
+        self._batch.set_state(table)
+        if out is None:
+            out = self._ef_buffer(wire_user.device)
+        self._launch(graph_header, defer_reset, self._batch.record, wire_user, out, float(ef_scale))
+        return True
+
+    def upload(self, tensors, slot, errs=None, dense=None):
+        """(in front of an address-free graph's replay: the graph's launches read the state table of the buffers it was captured
+        with -- the caller keys its graphs by the state buffers' addresses, and a table, once built, stays where it is)"""
+        if errs is not None and (tuple(map(_DATA_PTR, errs[0])), tuple(map(_DATA_PTR, errs[1]))) not in self._state_tables:
+            return False
+        return BatchedTopK.upload(self, tensors, slot, None, dense)
 
 
 class BatchedSign(_ItemGroup):

@@ -166,6 +166,9 @@ def build_parser():
     p.add_argument('--no-cuda', action='store_true', default=False)
     p.add_argument('--ef', action='store_true', default=False)
     p.add_argument('--two-phase', action='store_true', default=False)
+    p.add_argument('--momentum-correction', dest='momentum_correction', type=float, default=None, metavar='M',
+                   help='--quantizer topk only, not with --ef: momentum correction and momentum factor masking (Deep Gradient Compression) '
+                        'with momentum M in the quantizer; the optimizer then runs with momentum 0 (weight decay stays with it)')
     p.add_argument('--seed', type=int, default=1)
     p.add_argument('--train-size', type=int, default=4096, help='synthetic samples per epoch')
     p.add_argument('--log-interval', type=int, default=8, help='iterations between JSON log lines')
@@ -239,11 +242,13 @@ def train(args, log=None):
     num_classes = 10
     model = network_choices[args.network](num_classes=num_classes).to(device)
     quantizer = Quantizer(quantizer_choices[args.quantizer], model.parameters(), args)
-    optimizer = optim.SGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+    # --momentum-correction: the velocity lives in the quantizer (per user, in front of the select); the optimizer adds none
+    opt_momentum = args.momentum if getattr(args, "momentum_correction", None) is None else 0.0
+    optimizer = optim.SGD(model.parameters(), lr=args.lr, momentum=opt_momentum, weight_decay=args.weight_decay)
     # main.py:136-163: the learning-rate steps are NEW optimizers (momentum buffers start over), weight decay 5e-4
     # from then on; none for MNIST; SignSGD has its own constants
     steps = {} if args.dataset == 'mnist' else {51: 0.01, 71: 0.005}
-    momentum = args.momentum
+    momentum = opt_momentum
     if args.quantizer == 'sign':
         steps, momentum = {51: 0.0005, 71: 0.0001}, 0.0
         optimizer = optim.SGD(model.parameters(), lr=1e-3, momentum=0.0, weight_decay=0.1)

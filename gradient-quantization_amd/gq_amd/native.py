@@ -684,6 +684,70 @@ class TopKBatch(_ItemBatch):
         _check(rc, "gq_topk_compress_batched", TOPK_LIBRARY)
 
 
+# ---- momentum correction around the top-k select: libgq_dgc.so (include/gq_dgc.h) --------------------------------------------
+DGC_ABI_VERSION = 1
+DGC_EXPORTS = ["gq_dgc_abi_version", "gq_dgc_last_error", "gq_dgc_accumulate_batched", "gq_dgc_mask_batched"]
+
+DGC_LIBRARY = Library("libgq_dgc.so", "GQ_DGC_LIB_PATH", "gq_dgc_", DGC_ABI_VERSION, DGC_EXPORTS)
+DGC_LIB_PATH = DGC_LIBRARY.path
+
+
+def dgc_lib():
+    return DGC_LIBRARY.handle or _load(DGC_LIBRARY)
+
+
+class _DGCBatchStruct(ctypes.Structure):      # gq_dgc_batch (include/gq_dgc.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("grad_table", ctypes.c_void_p), ("state_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p)]
+
+
+class DGCBatch(TopKBatch):
+    """TopKBatch over the group's own table -- column 0 the gradients, which is also gq_dgc_batch.grad_table: the plain top-k
+    compress (a two-phase re-compress) and the decode-mean -- plus what a record with momentum correction launches: a second
+    gq_topk_batch, `select`, over ONE user's state table (set_state; the same item table and the same scratch: the launches of
+    a stream run one after the other) between gq_dgc_accumulate_batched and gq_dgc_mask_batched."""
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, hist=None, state=None, counts=None):
+        TopKBatch.__init__(self, seg_table, item_seg, nseg, nitems, hist, state, counts)
+        self.DL = dgc_lib()
+        self.select = TopKBatch(seg_table, item_seg, nseg, nitems, hist, state, counts) if hist is not None else None
+        self.d = _DGCBatchStruct(struct_bytes=ctypes.sizeof(_DGCBatchStruct), nseg=int(nseg), nitems=int(nitems),
+                                 grad_table=self.s.seg_table, state_table=None, item_seg=self.s.item_seg)
+        self.dref = ctypes.byref(self.d)
+        self.keep_state = None
+
+    def set_table(self, seg_table):
+        TopKBatch.set_table(self, seg_table)
+        self.d.grad_table = self.s.seg_table
+
+    def set_dense(self, dense_table, ndense):
+        TopKBatch.set_dense(self, dense_table, ndense)
+        if self.select is not None:
+            self.select.set_dense(dense_table, ndense)      # (the select's write launch copies the dense tensors into the wire)
+
+    def set_state(self, state_table):
+        """state_table: int64 [nseg * 8] on the device, one user's (include/gq_dgc.h); None: none (the launches refuse)."""
+        self.keep_state = state_table
+        self.d.state_table = _dev_ptr(state_table, torch.int64, "state_table").value if state_table is not None else None
+        if state_table is not None:
+            self.select.set_table(state_table)
+
+    def accumulate(self, m):
+        rc = self.DL.gq_dgc_accumulate_batched(self.dref, ctypes.c_float(m), _stream())
+        _check(rc, "gq_dgc_accumulate_batched", DGC_LIBRARY)
+
+    def mask(self, wire):
+        rc = self.DL.gq_dgc_mask_batched(self.dref, _dev_ptr(wire, torch.uint8, "wire"), _stream())
+        _check(rc, "gq_dgc_mask_batched", DGC_LIBRARY)
+
+    def record(self, wire, out, m):
+        """One record of the state table's user: accumulate, the select (error feedback at scale 1 over s and v; out: the
+        decoded tensors, which that form needs), mask."""
+        self.accumulate(m)
+        self.select.compress(wire, out, 1.0)
+        self.mask(wire)
+
+
 # ---- signSGD on a 2-bit wire: libgq_sign.so (include/gq_sign.h) -----------------------------------------------------------
 SIGN_ABI_VERSION = 1
 SIGN_EXPORTS = ["gq_sign_abi_version", "gq_sign_last_error", "gq_sign_compress_batched", "gq_sign_decode_sum_batched"]

@@ -46,7 +46,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedHSQ, BatchedMaurey, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
+    BatchedDGC, BatchedHSQ, BatchedMaurey, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
     MaureyCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
@@ -174,6 +174,10 @@ class PSQuantizer(object):
         self.error_feedback = args.ef
         self.two_phase = args.two_phase
         self.process_group = process_group
+        # args.momentum_correction = m (None: off): Deep Gradient Compression's momentum correction and momentum factor masking
+        # around the top-k select (include/gq_dgc.h).  The velocity u and its accumulation v live here, per parameter and user
+        # like param.error: param.dgc_u[user], param.dgc_v[user]; v is the error feedback at scale 1, so --ef is excluded.
+        self.dgc_m = self._momentum_correction(Compressor, args)
         factory = codec_factory or quantizer_codec_factory
         self.aggregate_fma = aggregate_fma(args)     # opt-in fused accumulation of the decode-mean (R >= 2 only)
         self.wire_levels = wire_levels_mode(args, _dist_world(process_group)[0])      # "bytes" | "packed6" (6-bit levels where the configuration allows)
@@ -193,6 +197,9 @@ class PSQuantizer(object):
                 param.error = [torch.zeros_like(param) for _ in range(args.num_users)]
             if self.error_feedback and self.two_phase:
                 param.server_error = torch.zeros_like(param)
+            if self.dgc_m is not None and isinstance(comp, TopKSparsificationCompressor):
+                param.dgc_u = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
+                param.dgc_v = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
         # wire layout of one user: 16-byte aligned sections for the compressed tensors first, then ONE
         # packed region with the raw f32 of all identity-compressed (<= 1000 element) tensors
         self.offsets = [0] * self.num_layers
@@ -219,7 +226,9 @@ class PSQuantizer(object):
         self._step_tail = os.environ.get("GQ_STEP_TAIL", "1") != "0"       # (see _decode_all)
         self._fuse_levels = os.environ.get("GQ_FUSE_LEVELS", "1") != "0"   # (see _can_fuse_levels)
         BatchedQSGD.place_lone_buckets(self.codecs)
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, BatchedTopK, BatchedSign, BatchedMaurey):
+        self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
+        topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -292,6 +301,52 @@ class PSQuantizer(object):
                 if c not in self.cuts:
                     self.cuts.append(c)
         self.cuts.sort()
+
+    @staticmethod
+    def _momentum_correction(Compressor, args, ring=False):
+        """args.momentum_correction as a float, or None when it is absent / None; ValueError where it cannot apply."""
+        m = getattr(args, "momentum_correction", None)
+        if m is None:
+            return None
+        m = float(m)
+        if ring:
+            raise ValueError("momentum_correction is not available in ring mode: a hop compresses the running sum of the users before "
+                             "it, not a gradient")
+        if not (isinstance(Compressor, type) and issubclass(Compressor, TopKSparsificationCompressor)):
+            raise ValueError("momentum_correction needs TopKSparsificationCompressor (--quantizer topk), got %s"
+                             % getattr(Compressor, "__name__", Compressor))
+        if getattr(args, "ef", False):
+            raise ValueError("momentum_correction excludes error feedback (ef): its accumulation v is the error feedback at scale 1")
+        if m != m or abs(m) == float("inf"):
+            raise ValueError("momentum_correction must be a finite number, got %r" % (m,))
+        return m
+
+    def _state_for(self, idxs, user):
+        """What a group's encode takes as `errs`, and its scale: the error buffers and the error-feedback scale, or with momentum
+        correction ([u], [v]) of the user and the momentum."""
+        if self.dgc_m is not None:
+            ps = [self.parameters[i] for i in idxs]
+            return ([p.dgc_u[user] for p in ps], [p.dgc_v[user] for p in ps])
+        return [self.parameters[i].error[user] for i in idxs] if self.error_feedback else None
+
+    def _record_dgc_single(self, i, grad, wire, user):
+        """The per-tensor route of a record with momentum correction: the same three launches over a one-tensor group, for a
+        gradient the multi-tensor path cannot address (the launches read a contiguous float32 copy of it)."""
+        param, codec = self.parameters[i], self.codecs[i]
+        flat = grad.detach().to(torch.float32).contiguous().view(-1)
+        if flat.data_ptr() % 4:
+            flat = flat.clone()
+        grp = self._dgc_single.get(i)
+        if grp is None or grp.device != flat.device:
+            grp = self._dgc_single[i] = BatchedDGC([codec], [0], [0], flat.device, 1, max(16, codec.nbytes))
+        for name in ("dgc_u", "dgc_v"):      # a state buffer somebody replaced by one the launches cannot address
+            t = getattr(param, name)[user]
+            if not (t.is_contiguous() and t.dtype == torch.float32 and t.device == flat.device):
+                getattr(param, name)[user] = t.to(device=flat.device, dtype=torch.float32).contiguous()
+        off = self.offsets[i]
+        if not grp.encode([flat], TopKCodec._at(wire, off), 0, 0, ([param.dgc_u[user]], [param.dgc_v[user]]), self.dgc_m):
+            raise native.GQNativeError("momentum correction: the gradient of parameter %d must be a float tensor on the current HIP "
+                                       "device (there is no CPU path)" % i)
 
     # ---- buffers -------------------------------------------------------------------------
     def _ensure_wire(self, device, slots):
@@ -419,7 +474,7 @@ class PSQuantizer(object):
         """Can _replay_known_step ever apply to this quantizer?  (False: decided for good; None: not yet -- the groups are built by
         the first record.)"""
         if (_HOST is None or not hasattr(_HOST, "scan_key") or not self.use_graphs or not self._fuse_steps or self.error_feedback
-                or self.two_phase or self._draw_total or self.capacity != 1 or not self._groups):
+                or self.dgc_m is not None or self.two_phase or self._draw_total or self.capacity != 1 or not self._groups):
             self._fast_ok = False
             return False
         if self._wire is None or not self._whole_step_ok(_dist_world(self.process_group)[0], 0) or not self._graphable():
@@ -489,6 +544,10 @@ class PSQuantizer(object):
             if self.error_feedback:     # the residual buffers' addresses are in the header too (a per-tensor step replaces them)
                 graph_key += (scale, tuple(p.error[user].data_ptr() for p in self.parameters))
                 generic_key += (scale,)
+            if self.dgc_m is not None:      # the state buffers' addresses are in the select's table, which a graph holds by address
+                state = tuple(t.data_ptr() for p in self.parameters if hasattr(p, "dgc_u") for t in (p.dgc_u[user], p.dgc_v[user]))
+                graph_key += (state,)
+                generic_key += (state,)
             plain_f32 = scan[2] if scan is not None else (all(map(_IS_CONTIGUOUS, all_grads)) and set(map(_DTYPE_OF, all_grads)) == _F32_ONLY)
             ent = self._rec_graphs.get(graph_key) if plain_f32 else None
             tied = ent is not None and ent[1] is not None
@@ -534,7 +593,9 @@ class PSQuantizer(object):
                 continue
             codec, off = self.codecs[i], self.offsets[i]
             grad = param.grad.data
-            if self.error_feedback:
+            if self.dgc_m is not None and isinstance(codec, TopKCodec):
+                self._record_dgc_single(i, grad, wire, user)
+            elif self.error_feedback:
                 # ps_quantizer.py:35-39:  grad += scale*error ; error = grad - decoded
                 if grad.device.type == "cuda" and grad.is_contiguous() and grad.dtype == torch.float32:
                     native.axpy_inplace(grad, param.error[user].contiguous(), scale)
@@ -581,7 +642,7 @@ class PSQuantizer(object):
         for grp in self._groups:
             cls, idxs, obj = grp
             grads = list(self._pick_group[id(grp)](all_grads))
-            errs = [self.parameters[i].error[user] for i in idxs] if self.error_feedback else None
+            errs = self._state_for(idxs, user)
             dense = list(self._pick_dense(all_grads)) if obj.ndense else None
             if not obj.upload(grads, slot, errs, dense):
                 return False
@@ -626,11 +687,11 @@ class PSQuantizer(object):
             grads = list(pick(all_grads))
             # error feedback (ps_quantizer.py:35,39) rides in the same launches: grad += scale*error
             # before the encode, error = grad - decoded after it, both in place
-            errs = [self.parameters[i].error[user] for i in idxs] if self.error_feedback else None
+            errs = self._state_for(idxs, user)
             hdr = headers[gi] if headers is not None else None
             dense = list(self._pick_dense(all_grads)) if obj.ndense else None
             kw = {"skip_levels": True} if fuse_levels else {}
-            if obj.encode(grads, wire, slot, salt, errs, scale, draws=draws, graph_header=hdr, dense=dense, defer_reset=defer_resets,
+            if obj.encode(grads, wire, slot, salt, errs, scale if self.dgc_m is None else self.dgc_m, draws=draws, graph_header=hdr, dense=dense, defer_reset=defer_resets,
                           table_current=table_current, **kw):      # (table_current: an address-free graph's launches, shared header)
                 skip.update(idxs)
                 if dense is not None:
@@ -1002,6 +1063,7 @@ class RingQuantizer(PSQuantizer):
     re-compresses the sum of everything before it), so it costs `world` encode latencies."""
 
     def __init__(self, Compressor, parameters, args, process_group=None, codec_factory=None):
+        self._momentum_correction(Compressor, args, ring=True)      # (refused: the running sum is not a gradient)
         two_phase = args.two_phase
         args.two_phase = False           # ring_quantizer.py has no second phase and no server residual
         try:
