@@ -67,14 +67,6 @@ __global__ void sub_kernel(const float *__restrict__ a, const float *__restrict_
     for (; i < n; i += stride) o[i] = a[i] - b[i];
 }
 
-static inline int grid_for(int64_t n, int block) {
-    int64_t g = (n + block - 1) / block;
-    int64_t cap = (int64_t)cu_count() * 8;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-
 }  // namespace gq
 
 GQ_API int gq_abi_version(void) { return 5; }
@@ -96,7 +88,7 @@ GQ_API int gq_device_info(int device, int *cu_count, char *arch, size_t arch_len
 GQ_API int gq_axpy_inplace(float *grad, const float *err, float scale, int64_t n, void *stream) {
     if (n < 0 || (n > 0 && (!grad || !err))) return gq::fail(GQ_ERR_INVALID_ARG, "gq_axpy_inplace: bad arguments");
     if (n == 0) return GQ_OK;
-    hipLaunchKernelGGL(gq::axpy_inplace_kernel, dim3(gq::grid_for(n, 256)), dim3(256), 0, gq::as_stream(stream), grad,
+    hipLaunchKernelGGL(gq::axpy_inplace_kernel, dim3((unsigned)gq::grid_cap(n, 256)), dim3(256), 0, gq::as_stream(stream), grad,
                        err, scale, n);
     GQ_CHECK_LAUNCH("gq_axpy_inplace");
     return GQ_OK;
@@ -105,7 +97,7 @@ GQ_API int gq_axpy_inplace(float *grad, const float *err, float scale, int64_t n
 GQ_API int gq_sub(const float *grad, const float *decoded, float *err, int64_t n, void *stream) {
     if (n < 0 || (n > 0 && (!grad || !decoded || !err))) return gq::fail(GQ_ERR_INVALID_ARG, "gq_sub: bad arguments");
     if (n == 0) return GQ_OK;
-    hipLaunchKernelGGL(gq::sub_kernel, dim3(gq::grid_for(n, 256)), dim3(256), 0, gq::as_stream(stream), grad, decoded,
+    hipLaunchKernelGGL(gq::sub_kernel, dim3((unsigned)gq::grid_cap(n, 256)), dim3(256), 0, gq::as_stream(stream), grad, decoded,
                        err, n);
     GQ_CHECK_LAUNCH("gq_sub");
     return GQ_OK;
@@ -148,7 +140,7 @@ GQ_API int gq_mean_rows(const void *rows, int64_t row_stride_bytes, int R, int64
         hipLaunchKernelGGL(gq::rng_step_kernel, dim3(1), dim3(256), 0, gq::as_stream(stream), rng_state, rng_state ? rng_pairs : 0,
                            reset_dst, reset_src, reset_words);
     else
-        hipLaunchKernelGGL(gq::mean_rows_kernel, dim3(gq::grid_for(n, 256)), dim3(256), 0, gq::as_stream(stream),
+        hipLaunchKernelGGL(gq::mean_rows_kernel, dim3((unsigned)gq::grid_cap(n, 256)), dim3(256), 0, gq::as_stream(stream),
                            static_cast<const uint8_t *>(rows), row_stride_bytes, R, n, out, rng_state, rng_pairs, reset_dst,
                            reset_src, reset_words);
     GQ_CHECK_LAUNCH("gq_mean_rows");

@@ -20,6 +20,11 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
 
 // Number of compute units of the current device (cached).
 int cu_count();
+// workgroups for `items` at `per_group` items a workgroup: capped at CUs x 8 (2,048 threads a CU / 256), at least 1
+inline int64_t grid_cap(int64_t items, int64_t per_group) {
+    const int64_t groups = (items + per_group - 1) / per_group, cap = (int64_t)cu_count() * 8;
+    return groups > cap ? cap : groups < 1 ? 1 : groups;
+}
 // the start / stop events of a gq_profile_read slot (created on first use); false for slot < 0 or a failure:
 // the caller then launches plainly
 bool profile_events(int slot, hipEvent_t *start, hipEvent_t *stop);
@@ -109,7 +114,7 @@ __device__ __forceinline__ float level_to_norm<float>(float l, float, float, flo
 // rounded quotient (Markstein's correction step).  Valid while nothing on the way is subnormal: 2^-80 <= b <= 2^20 and
 // 2^-102 <= a <= b (then a/b >= 2^-122, and r, a multiple of 2^-47 ulp-units of a, is representable); a == 0 would be fine too
 // but is not worth a test.  The QSGD caller passes b = norm / s with s <= 2^16 and tests the NORM (quotient_window,
-// qsgd_batched.hip): 2^-64 <= norm <= 2^20, so that b >= 2^-80.  Checked against `a / b` on 5.9e9 (a, b) pairs
+// qsgd_common.hpp): 2^-64 <= norm <= 2^20, so that b >= 2^-80.  Checked against `a / b` on 5.9e9 (a, b) pairs
 // on the CPU (every mantissa of b; b with the 16 highest mantissas against every mantissa of a) and on the GPU by
 // the kernel-vs-oracle tests.  b == 0 with a == 0 gives 0 * inf = NaN like 0 / 0.
 __device__ __forceinline__ float shared_quotient(float a, float b, float y) {

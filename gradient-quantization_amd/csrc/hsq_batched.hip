@@ -912,9 +912,7 @@ static int launch_decode_any(const int64_t *seg_table, const int32_t *tile_seg, 
     const size_t cb_bytes = (size_t)K * d * sizeof(float);
     const int in_lds = cb_bytes <= 64 * 1024;
     const size_t lds = in_lds ? cb_bytes : 0;
-    int64_t blocks = ntiles;
-    const int64_t cap = (int64_t)cu_count() * 8;
-    if (blocks > cap) blocks = cap;
+    const int64_t blocks = grid_cap(ntiles, 1);
     if ((d & 3) == 0) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(hsq_decode_sum_batched_any_kernel<CodeT, LevelT, 4, ERR>),
                            dim3((unsigned)blocks), dim3(BT_THREADS), lds, st, seg_table, tile_seg, ntiles, gathered,
@@ -954,13 +952,6 @@ static int decode_any(const int64_t *seg_table, const int32_t *tile_seg, int nse
     return fail(GQ_ERR_INVALID_ARG, "%s: code_bytes must be 1 or 4, level_bytes 0 (f32 norms), 1, 2 or 4", what);
 }
 
-static inline int64_t bt_grid(int64_t items) {
-    int64_t blocks = (items + BT_THREADS - 1) / BT_THREADS;
-    const int64_t cap = (int64_t)cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return blocks < 1 ? 1 : blocks;
-}
-
 }  // namespace gq
 
 namespace gq {
@@ -995,16 +986,16 @@ GQ_INTERNAL int gqi_hsq_levels_batched_d16(const int64_t *seg_table, const int32
     const dim3 block(gq::BT_THREADS);
     hipStream_t st = gq::as_stream(stream);
     if (ef_codebook && packed6)
-        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_kernel, dim3((unsigned)gq::bt_grid(ntiles * 256)), block, 0, st,
+        hipLaunchKernelGGL(gq::hsq_levels_ef_batched_kernel, dim3((unsigned)gq::grid_cap(ntiles * 256, gq::BT_THREADS)), block, 0, st,
                            seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, ef_codebook, K, wire, dense_table, ndense);
     else if (ef_codebook)
         gq::launch_levels_ef_tile<16, uint8_t>(seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, ef_codebook, K, wire,
                                                dense_table, ndense, st);
     else if (packed6)
-        hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<gq::Packed6>, dim3((unsigned)gq::bt_grid(ntiles * 16)), block, 0, st,
+        hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<gq::Packed6>, dim3((unsigned)gq::grid_cap(ntiles * 16, gq::BT_THREADS)), block, 0, st,
                            seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, wire, dense_table, ndense);
     else
-        hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<uint8_t>, dim3((unsigned)gq::bt_grid(ntiles * 16)), block, 0, st,
+        hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<uint8_t>, dim3((unsigned)gq::grid_cap(ntiles * 16, gq::BT_THREADS)), block, 0, st,
                            seg_table, tile_seg, ntiles, u_flat, seg_minmax, n_bit, random_mode, seed, r_flat, wire, dense_table, ndense);
     GQ_CHECK_LAUNCH("gq_hsq_levels_batched");
     return GQ_OK;
@@ -1034,7 +1025,7 @@ GQ_INTERNAL int gqi_hsq_decode_sum_batched_d16(const int64_t *seg_table, const i
     } else if (packed6) {
         return gq::fail(GQ_ERR_UNSUPPORTED, "gq_hsq_decode_sum_batched: packed levels need 4-byte aligned wires");
     } else {
-        hipLaunchKernelGGL(gq::hsq_decode_sum_batched_kernel, dim3((unsigned)gq::bt_grid(ntiles * 256)),
+        hipLaunchKernelGGL(gq::hsq_decode_sum_batched_kernel, dim3((unsigned)gq::grid_cap(ntiles * 256, gq::BT_THREADS)),
                            dim3(gq::BT_THREADS), 0, gq::as_stream(stream), seg_table, tile_seg, ntiles, gathered,
                            user_stride_bytes, R, codebook, K, n_bit, out, plain);
     }
@@ -1189,7 +1180,7 @@ GQ_INTERNAL int gqi_hsq_levels_batched_any(const int64_t *seg_table, const int32
     if (random_mode == GQ_RANDOM_GIVEN && !r_flat && level_bytes != 0)
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_hsq_levels_batched: GQ_RANDOM_GIVEN needs r_flat");
     if (level_bytes == 0) {   // n_bit == 32 (nearest_neighbor_compressor.py:14,75-76): u itself is the payload
-        hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<float>, dim3((unsigned)gq::bt_grid(ntiles * 16)),
+        hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<float>, dim3((unsigned)gq::grid_cap(ntiles * 16, gq::BT_THREADS)),
                            dim3(gq::BT_THREADS), 0, gq::as_stream(stream), seg_table, tile_seg, ntiles, u_flat, seg_minmax,
                            1, GQ_RANDOM_OFF, (uint64_t)0, (const float *)nullptr, wire, dense_table, ndense);
         GQ_CHECK_LAUNCH("gq_hsq_levels_batched");
@@ -1199,7 +1190,7 @@ GQ_INTERNAL int gqi_hsq_levels_batched_any(const int64_t *seg_table, const int32
     if ((level_bytes == 1 && top > 255) || (level_bytes == 2 && top > 32767))
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_hsq_levels_batched: levels up to %lld do not fit %d byte(s)",
                         (long long)top, level_bytes);
-    const dim3 grid((unsigned)gq::bt_grid(ntiles * 16)), block(gq::BT_THREADS);
+    const dim3 grid((unsigned)gq::grid_cap(ntiles * 16, gq::BT_THREADS)), block(gq::BT_THREADS);
     hipStream_t st = gq::as_stream(stream);
     if (level_bytes == 1)
         hipLaunchKernelGGL(gq::hsq_levels_batched_kernel<uint8_t>, grid, block, 0, st, seg_table, tile_seg, ntiles, u_flat,

@@ -691,7 +691,6 @@ static int launch_decode(const CodeT *codes, const LevelT *levels, const float *
                          hipStream_t st) {
     const bool fma = (n_bit & GQ_AGGREGATE_FMA) != 0 && R >= 2;   // opt-in fused accumulation (the d16 / byte kernels, R = 2, 4, 8, 16)
     n_bit &= 0xFF;
-    const int64_t cap = (int64_t)cu_count() * 8;
     if constexpr (sizeof(CodeT) == 1 && (std::is_same<LevelT, uint8_t>::value || std::is_same<LevelT, Packed6>::value)) {
         constexpr bool P6 = std::is_same<LevelT, Packed6>::value;
         // the packed form reads codes and levels with alignment-free dword loads (a group of levels starts at any byte)
@@ -731,9 +730,7 @@ static int launch_decode(const CodeT *codes, const LevelT *levels, const float *
     } else {
     if ((d & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(cb) & 15) == 0) {
         const int64_t total = M * (d >> 2);
-        int64_t blocks = (total + DEC_THREADS - 1) / DEC_THREADS;
-        if (blocks > cap) blocks = cap;
-        if (blocks < 1) blocks = 1;
+        const int64_t blocks = grid_cap(total, DEC_THREADS);
         const size_t lds = (size_t)K * cb_row_stride(d) * sizeof(float);
         // stage the codebook in LDS when it fits and the launch is big enough to amortise it
         if (lds <= 64 * 1024 && total >= (int64_t)K * d) {
@@ -745,9 +742,7 @@ static int launch_decode(const CodeT *codes, const LevelT *levels, const float *
         }
     } else {
         const int64_t total = M * d;
-        int64_t blocks = (total + DEC_THREADS - 1) / DEC_THREADS;
-        if (blocks > cap) blocks = cap;
-        if (blocks < 1) blocks = 1;
+        const int64_t blocks = grid_cap(total, DEC_THREADS);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(hsq_decode_sum_scalar_kernel<CodeT, LevelT>), dim3((unsigned)blocks),
                            dim3(DEC_THREADS), 0, st, codes, levels, lb_ub, cs, ls, bs, cb, R, M, d, n_bit, out);
     }

@@ -3,10 +3,11 @@
 // Replaces qsgd_compressor.py:42-71 of the reference.  Pure HBM-bound byte work:
 // 4 B read per element, 2 B (sign + level) written; one wave owns one bucket, the
 // max-|v| reduction is a wave shuffle reduction, the second sweep over the bucket
-// hits L1/L2.  -ffp-contract=off; IEEE divide.
+// hits L1/L2.  -ffp-contract=off; IEEE divide.  The level step and the de-quantiser are csrc/qsgd_common.hpp's.
 #include <limits.h>
+#include <type_traits>
 
-#include "gq_common.hpp"
+#include "qsgd_common.hpp"
 
 namespace gq {
 
@@ -27,22 +28,9 @@ template <typename LevelT>
 __device__ __forceinline__ void qsgd_quantise_one(float v, float norm, float s, float smax, int random_mode,
                                                   const float *__restrict__ r, uint64_t seed, int64_t i,
                                                   uint8_t *__restrict__ signs, LevelT *__restrict__ levels) {
-    const float q = v / norm;
-    const float x = fabsf(q) * s;
-    LevelT out;
-    if (x != x) {
-        out = nan_level<LevelT>();
-    } else {
-        const float c = fminf(fmaxf(x, 0.0f), smax);
-        int l = (int)c;
-        if (random_mode != GQ_RANDOM_OFF) {
-            const float prob = x - (float)l;
-            const float rr = (random_mode == GQ_RANDOM_GIVEN) ? r[i] : uniform01(seed, (uint64_t)i);
-            l += (prob > rr) ? 1 : 0;
-        }
-        out = (LevelT)l;
-    }
-    levels[i] = out;
+    const float x = qsgd_quotient(v, norm, s);
+    auto draw = [&] { return (random_mode == GQ_RANDOM_GIVEN) ? r[i] : uniform01(seed, (uint64_t)i); };
+    levels[i] = x != x ? nan_level<LevelT>() : (LevelT)qsgd_level(x, smax, random_mode != GQ_RANDOM_OFF, draw);
     signs[i] = v > 0.0f ? 1 : 0;
 }
 
@@ -115,17 +103,22 @@ __global__ __launch_bounds__(QS_THREADS) void qsgd_decode_sum_kernel(const float
                                                                     float *__restrict__ out) {
     const int64_t total = Mb * (int64_t)d;
     const int64_t stride = (int64_t)gridDim.x * QS_THREADS;
-    const float s = (float)(1 << n_bit);
+    const float inv_s = 1.0f / (float)(1 << n_bit);
     const MeanDiv md = mean_div_of(R);
     for (int64_t i = (int64_t)blockIdx.x * QS_THREADS + threadIdx.x; i < total; i += stride) {
         const int64_t b = i / d;
         float acc = 0.0f;
         for (int r = 0; r < R; ++r) {
-            // qsgd_compressor.py:69-70: (l * (2*signs - 1)) * norm / s
-            const float sg = 2.0f * (float)signs[(int64_t)r * total + i] - 1.0f;
-            float t = (float)levels[(int64_t)r * total + i] * sg;
-            t = t * norm[(int64_t)r * Mb + b];
-            t = t / s;
+            const unsigned sign = signs[(int64_t)r * total + i];
+            const float nm = norm[(int64_t)r * Mb + b];
+            float t;
+            if constexpr (std::is_same<LevelT, uint8_t>::value) {
+                t = qsgd_scale(qsgd_signed_level(levels[(int64_t)r * total + i], sign ^ 1u), nm, inv_s);   // (signs are 0 / 1: only bit 0 counts)
+            } else {
+                // the ONE place that keeps qsgd_compressor.py:69's product by 2 sign - 1: an int32 level can be the NEGATIVE
+                // INT_MIN of a NaN quotient, and a sign bit put on (float)level would not negate it
+                t = qsgd_scale((float)levels[(int64_t)r * total + i] * (2.0f * (float)sign - 1.0f), nm, inv_s);
+            }
             acc = (r == 0) ? t : acc + t;
         }
         if (md.apply) acc = mean_div(acc, md);
@@ -133,22 +126,16 @@ __global__ __launch_bounds__(QS_THREADS) void qsgd_decode_sum_kernel(const float
     }
 }
 
-static inline int64_t grid_cap(int64_t blocks) {
-    const int64_t cap = (int64_t)cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return blocks < 1 ? 1 : blocks;
-}
-
 template <typename LevelT>
 static int launch_qsgd_compress(const float *grad, int64_t Mb, int d, int n_bit, int random_mode, const float *r,
                                 uint64_t seed, float *norm, uint8_t *signs, LevelT *levels, hipStream_t st) {
     if (d <= 8192) {
-        const int64_t blocks = grid_cap((Mb + (QS_THREADS / 64) - 1) / (QS_THREADS / 64));
+        const int64_t blocks = grid_cap(Mb, QS_THREADS / 64);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(qsgd_compress_wave_kernel<LevelT>), dim3((unsigned)blocks),
                            dim3(QS_THREADS), 0, st, grad, Mb, d, n_bit, random_mode, r, seed, norm, signs, levels);
     } else {
         const int64_t total = Mb * (int64_t)d;
-        const int64_t blocks = grid_cap((total + QS_THREADS - 1) / QS_THREADS);
+        const int64_t blocks = grid_cap(total, QS_THREADS);
         hipError_t e = hipMemsetAsync(norm, 0, (size_t)Mb * sizeof(float), st);
         if (e != hipSuccess) return fail(GQ_ERR_HIP, "gq_qsgd_compress: memset: %s", hipGetErrorString(e));
         hipLaunchKernelGGL(qsgd_absmax_kernel, dim3((unsigned)blocks), dim3(QS_THREADS), 0, st, grad, Mb, d,
@@ -187,7 +174,7 @@ GQ_API int gq_qsgd_decode_sum(const float *norm, const uint8_t *signs, const voi
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum: bad sizes");
     if (!norm || !signs || !levels || !out) return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum: null pointer");
     hipStream_t st = gq::as_stream(stream);
-    const int64_t blocks = gq::grid_cap((Mb * (int64_t)d + gq::QS_THREADS - 1) / gq::QS_THREADS);
+    const int64_t blocks = gq::grid_cap(Mb * (int64_t)d, gq::QS_THREADS);
     if (level_bytes == 1)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(gq::qsgd_decode_sum_kernel<uint8_t>), dim3((unsigned)blocks),
                            dim3(gq::QS_THREADS), 0, st, norm, signs, static_cast<const uint8_t *>(levels), R, Mb, d,

@@ -14,14 +14,14 @@
 // chunk_seg[chunk] names the tensor; seg_table[seg] = { grad ptr (8-byte aligned), d, first chunk, norm off,
 // codes off (bytes inside ONE user's wire), out off (floats), first word in norm_bits, error ptr }.
 // HBM-bound: 4 B read (+4 B from the MALL) and 0.5..1 B written per element.
-#include "gq_common.hpp"
+// The coder, the de-quantiser and the code units and pairs are csrc/qsgd_common.hpp's; an element's draw here is
+// uniform01(seed, (bucket << 32) + element).
+#include "qsgd_common.hpp"
 
 namespace gq {
 
 constexpr int QW_THREADS = 256;
 constexpr int QW_CHUNK = GQ_QSGD_WIDE_CHUNK;
-
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 struct WideItem {
     const int64_t *rec;
@@ -116,24 +116,6 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_absmax_kernel(const int6
     flush();
 }
 
-__device__ __forceinline__ unsigned wide_code(float v, float norm, float s, float smax, int random_mode, uint64_t seed,
-                                              uint64_t gidx, int bits) {
-    const float q = v / norm;
-    const float x = fabsf(q) * s;
-    unsigned l = 0, sgn = v > 0.0f ? 1u : 0u;
-    if (x != x) {  // NaN (zero bucket) -> level 0 carrying the sign of the reference's INT_MIN level (qsgd_batched.hip: qsgd_code)
-        sgn ^= 1u;
-    } else {
-        const float c = fminf(fmaxf(x, 0.0f), smax);
-        l = (unsigned)(int)c;
-        if (random_mode >= GQ_RANDOM_DEVICE) {   // DEVICE, or DEVICE_KEYED with the keyed seed handed in
-            const float prob = x - (float)l;
-            l += (prob > uniform01(seed, gidx)) ? 1u : 0u;
-        }
-    }
-    return l | (sgn << (bits - 1));
-}
-
 template <bool EF, int BITS>
 __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_quantise_kernel(
     const int64_t *__restrict__ seg_table, const int32_t *__restrict__ chunk_seg, int64_t nchunks, int n_bit,
@@ -141,8 +123,7 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_quantise_kernel(
     resolve_seed(random_mode, seed);
     copy_dense_segments(dense_table, ndense, wire);
     const int lane = threadIdx.x & 63;
-    const float s = (float)(1 << n_bit), smax = s - 1.0f;
-    constexpr unsigned lmask = (1u << (BITS - 1)) - 1u;
+    const float s = (float)(1 << n_bit), smax = s - 1.0f, inv_s = 1.0f / s;
     int64_t c_begin, c_end;
     wide_run(nchunks, c_begin, c_end);
     // the chunk -> tensor -> record lookups of chunk c + 1 are issued before chunk c's data is touched: three
@@ -187,48 +168,12 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_quantise_kernel(
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k)
-                code[k] = wide_code(val[k], norm, s, smax, random_mode, sd, g0 + (uint64_t)(e0 + k), BITS);
-            if (BITS == 4) {
-                if (whole && dwords) {
-                    unsigned w = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) w |= code[k] << (4 * k);
-                    *reinterpret_cast<unsigned *>(dst + (e0 >> 1)) = w;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (e0 + 2 * k < it.n) dst[(e0 >> 1) + k] = (uint8_t)(code[2 * k] | (code[2 * k + 1] << 4));
-                }
-            } else if (BITS == 16) {
-                if (whole && dwords) {
-                    *reinterpret_cast<uint4 *>(dst + 2 * e0) = make_uint4(code[0] | (code[1] << 16), code[2] | (code[3] << 16),
-                                                                          code[4] | (code[5] << 16), code[6] | (code[7] << 16));
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (e0 + 2 * k < it.n)
-                            *reinterpret_cast<unsigned *>(dst + 2 * (e0 + 2 * k)) = code[2 * k] | (code[2 * k + 1] << 16);
-                }
-            } else {
-                if (whole && dwords) {
-                    const unsigned w0 = code[0] | (code[1] << 8) | (code[2] << 16) | (code[3] << 24);
-                    const unsigned w1 = code[4] | (code[5] << 8) | (code[6] << 16) | (code[7] << 24);
-                    *reinterpret_cast<uint2 *>(dst + e0) = make_uint2(w0, w1);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        if (e0 + k < it.n) dst[e0 + k] = (uint8_t)code[k];
-                }
-            }
+                code[k] = qsgd_code<false>(val[k], qsgd_quotient(val[k], norm, s), smax, random_mode >= GQ_RANDOM_DEVICE,   // DEVICE, or DEVICE_KEYED with the keyed seed
+                                           [&] { return uniform01(sd, g0 + (uint64_t)(e0 + k)); }, BITS);
             if (EF && err) {
-                float res[8];   // qsgd_compressor.py:69-70 on the element's own code, then ps_quantizer.py:39
+                float res[8];   // the element's own code decoded, then ps_quantizer.py:39
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    float t = (float)(code[k] & lmask) * (2.0f * (float)(code[k] >> (BITS - 1)) - 1.0f);
-                    t = t * norm;
-                    t = t / s;
-                    res[k] = val[k] - t;
-                }
+                for (int k = 0; k < 8; ++k) res[k] = val[k] - qsgd_dequant(code[k], BITS, norm, inv_s);
                 if (whole && quads) {
                     *reinterpret_cast<f32x4 *>(err + e0) = f32x4{res[0], res[1], res[2], res[3]};
                     *reinterpret_cast<f32x4 *>(err + e0 + 4) = f32x4{res[4], res[5], res[6], res[7]};
@@ -239,6 +184,14 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_quantise_kernel(
                         if (e < it.n) *reinterpret_cast<v2f *>(err + e) = v2f{res[2 * k], res[2 * k + 1]};
                     }
                 }
+            }
+            uint8_t *unit = dst + BITS * (e0 >> 3);   // the lane's unit; a partial one pair by pair
+            if (whole && dwords) {
+                store_unit<BITS>(unit, code);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (e0 + 2 * k < it.n) store_pair(unit + pair_at(2 * k, BITS), BITS, code[2 * k], code[2 * k + 1]);
             }
         }
     }
@@ -257,7 +210,6 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_decode_kernel(const int6
     const int lane = threadIdx.x & 63;
     const float inv_s = 1.0f / (float)(1 << n_bit);
     const MeanDiv md = mean_div_of(R, !plain);   // the aggregate of R users (ps_quantizer.py:48)
-    constexpr unsigned lmask = (1u << (BITS - 1)) - 1u;
     int64_t c_begin, c_end;
     wide_run(nchunks, c_begin, c_end);
     // the chunk -> tensor -> record lookups of chunk c + 1 are issued before chunk c's data is touched: three
@@ -279,37 +231,24 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_decode_kernel(const int6
             for (int r = 0; r < R; ++r) {
                 const uint8_t *p = gathered + (int64_t)r * user_stride;
                 const float norm = reinterpret_cast<const float *>(p + it.rec[3])[it.b];
-                unsigned code[8];
-                if (BITS == 4) {
-                    unsigned w = 0;
-                    if (whole && dwords) {
-                        w = *reinterpret_cast<const unsigned *>(p + code_off + (e0 >> 1));
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (e0 + 2 * k < it.n) w |= (unsigned)p[code_off + (e0 >> 1) + k] << (8 * k);
-                    }
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) code[k] = (w >> (4 * k)) & 15u;
-                } else if (BITS == 16) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const unsigned cc = (e0 + 2 * k < it.n)
-                                                ? *reinterpret_cast<const unsigned *>(p + code_off + 2 * (e0 + 2 * k)) : 0u;
-                        code[2 * k] = cc & 0xFFFFu;
-                        code[2 * k + 1] = cc >> 16;
-                    }
+                unsigned w[BITS / 4] = {}, nw[BITS / 4];   // the lane's unit; a partial one pair by pair (codes 0 behind the chunk)
+                const uint8_t *unit = p + code_off + BITS * (e0 >> 3);
+                if (whole && dwords) {
+                    load_unit<BITS>((gbyte_ptr)unit, w);
                 } else {
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) code[k] = (e0 + k < it.n) ? (unsigned)p[code_off + e0 + k] : 0u;
+                    for (int k = 0; k < 4; ++k)
+                        if (e0 + 2 * k < it.n) {
+                            unsigned c0, c1;
+                            load_pair(unit + pair_at(2 * k, BITS), BITS, c0, c1);
+                            w[2 * k * BITS / 32] |= (c0 | (c1 << BITS)) << (2 * k * BITS % 32);
+                        }
                 }
 #pragma unroll
+                for (int i = 0; i < BITS / 4; ++i) nw[i] = ~w[i];
+#pragma unroll
                 for (int k = 0; k < 8; ++k) {
-                    const float lf = (float)(code[k] & lmask);
-                    const unsigned neg = ((~code[k]) >> (BITS - 1)) & 1u;
-                    float t = __uint_as_float(__float_as_uint(lf) | (neg << 31));   // l * (2*sign - 1), -0 for l = 0
-                    t = t * norm;
-                    t = t * inv_s;
+                    const float t = qsgd_scale(unit_signed_level<BITS>(w, nw, k), norm, inv_s);
                     acc[k] = (r == 0) ? t : acc[k] + t;
                 }
             }
@@ -331,28 +270,17 @@ __global__ __launch_bounds__(QW_THREADS) void qsgd_wide_decode_kernel(const int6
     }
 }
 
-static inline int64_t qw_grid(int64_t nchunks) {
-    int64_t blocks = (nchunks + (QW_THREADS / 64) - 1) / (QW_THREADS / 64);
-    const int64_t cap = (int64_t)cu_count() * 8;
-    if (blocks > cap) blocks = cap;
-    return blocks < 1 ? 1 : blocks;
-}
-
 }  // namespace gq
 
 GQ_INTERNAL int gqi_qsgd_wide_compress(const int64_t *seg_table, const int32_t *chunk_seg, int nseg, int64_t nchunks,
                                  int n_bit, int random_mode, uint64_t seed, int ef, float ef_scale,
                                  uint32_t *norm_bits, uint8_t *wire, const int64_t *dense_table, int ndense, void *stream) {
-    if (nseg < 1 || nchunks < 1 || n_bit < 1) return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_compress_batched (wide): bad sizes");
-    if (!seg_table || !chunk_seg || !norm_bits || !wire)
-        return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_compress_batched (wide): null pointer");
-    if (random_mode != GQ_RANDOM_OFF && random_mode != GQ_RANDOM_DEVICE && random_mode != GQ_RANDOM_DEVICE_KEYED &&
-        random_mode != GQ_RANDOM_DEVICE_COUNTER)
-        return gq::fail(GQ_ERR_UNSUPPORTED, "gq_qsgd_compress_batched (wide): random_mode must be OFF, DEVICE, DEVICE_KEYED or DEVICE_COUNTER");
-    const int bits = gq_qsgd_code_bits(n_bit, random_mode);
-    if (!bits) return gq::fail(GQ_ERR_UNSUPPORTED, "gq_qsgd_compress_batched (wide): n_bit %d has no packed format", n_bit);
+    int bits;
+    if (const int rc = gq::qsgd_compress_check("gq_qsgd_compress_batched (wide)", seg_table && chunk_seg && norm_bits && wire, nseg, nchunks, n_bit,
+                                               random_mode, &bits))
+        return rc;
     hipStream_t st = gq::as_stream(stream);
-    const dim3 grid((unsigned)gq::qw_grid(nchunks)), block(gq::QW_THREADS);
+    const dim3 grid((unsigned)gq::grid_cap(nchunks, gq::QW_THREADS / 64)), block(gq::QW_THREADS);
     if (ef)
         hipLaunchKernelGGL(gq::qsgd_wide_absmax_kernel<true>, grid, block, 0, st, seg_table, chunk_seg, nchunks, ef_scale,
                            norm_bits);
@@ -379,14 +307,12 @@ GQ_INTERNAL int gqi_qsgd_wide_decode_sum(const int64_t *seg_table, const int32_t
     plain = plain ? 1 : 0;
     if (tail_taken) *tail_taken = 0;
     const gq::StepTail tail = tail_or_null ? *tail_or_null : gq::StepTail{};
-    if (nseg < 1 || nchunks < 1 || n_bit < 1 || R < 1 || (bits != 4 && bits != 8 && bits != 16))
-        return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum_batched (wide): bad sizes");
-    if (!seg_table || !chunk_seg || !gathered || !out)
-        return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum_batched (wide): null pointer");
+    if (const int rc = gq::qsgd_decode_check("gq_qsgd_decode_sum_batched (wide)", seg_table && chunk_seg && gathered && out, nseg, nchunks, n_bit, bits, R))
+        return rc;
     if ((user_stride_bytes & 3) != 0 || (reinterpret_cast<uintptr_t>(gathered) & 3) != 0 ||
         (reinterpret_cast<uintptr_t>(out) & 15) != 0)
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum_batched (wide): wires must be 4-byte, out 16-byte aligned");
-    const dim3 grid((unsigned)gq::qw_grid(nchunks)), block(gq::QW_THREADS);
+    const dim3 grid((unsigned)gq::grid_cap(nchunks, gq::QW_THREADS / 64)), block(gq::QW_THREADS);
     if (bits == 4)
         hipLaunchKernelGGL(gq::qsgd_wide_decode_kernel<4>, grid, block, 0, gq::as_stream(stream), seg_table, chunk_seg,
                            nchunks, n_bit, gathered, user_stride_bytes, R, out, plain, tail);

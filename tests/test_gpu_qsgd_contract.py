@@ -392,6 +392,66 @@ def test_per_tensor_compress_and_decode_sum(level_bytes, given, oracle):
         assert qc.same_bits(got[:nb * d], exp) and np.all(got[nb * d:] == OUT_FILL)
 
 
+# ---- error feedback and the per-tensor decode at tiny norms: the one de-quantiser (csrc/qsgd_common.hpp) on every path --------------------
+TINY_PATHS = {       # path -> (d, tensors, bits, wide): lanes per bucket 16 (hint 128)
+    "reg1": (128, 1, 4, False), "reg2": (256, 1, 4, False), "walk": (264, 1, 4, False), "pairs": (10, 1, 4, False),
+    "generic": (10, 257, 8, False), "nolds4": (8, 257, 4, False), "wide": (1030, 1, 4, True),
+}
+
+
+@pytest.mark.parametrize("path", list(TINY_PATHS))
+def test_error_feedback_with_subnormal_residuals(path):
+    """three buckets a tensor: maxima 2^-120 ... 2^-140 (the decoded values and the new errors are subnormal), all +0, all -0"""
+    d, nseg, bits, wide = TINY_PATHS[path]
+    if not wide and nseg == 1:
+        assert qc.compress_path(d, 16) == path
+    # more tensors than QB_LDS_SEGS = 256 (csrc/qsgd_batched.hip): the launcher leaves the kernels that keep the table in LDS -- 8-bit
+    # codes go to qsgd_compress_batched_kernel, 4-bit codes to qsgd_compress_batched4_kernel<EF, false>
+    assert (nseg > 256) == (path in ("generic", "nolds4")) and (not wide or d % 1024 == 6)
+    rs = np.random.RandomState(d)
+    G, E = [], []
+    for i in range(nseg):
+        top = f32(2.0 ** -(120 + (5 * i) % 21))
+        g, e = (rs.uniform(-0.5, 0.5, (3, d)) * top).astype(f32), (rs.uniform(-0.2, 0.2, (3, d)) * top).astype(f32)
+        g[0, 0], e[0, 0] = top, 0
+        g[1], e[1], g[2], e[2] = 0.0, 0.0, -0.0, -0.0
+        G.append(g), E.append(e)
+    with np.errstate(all="ignore"):
+        v = G[-1] + f32(0.75) * E[-1]
+    assert f32(2.0 ** -140) <= np.abs(v[0]).max() == v[0, 0] <= f32(2.0 ** -120) and np.signbit(v[2]).all() and not np.signbit(v[1]).any()
+    L = qc.Layout([(d, 3)] * nseg, bits, wide=wide)
+    check_compress(L, G, E, 0.75, qc.N_BIT_OF[(bits, 1)], qc.DEVICE, seed=0xABCDEF12345, hint=128)
+
+
+@pytest.mark.parametrize("level_bytes", [1, 4])
+@pytest.mark.parametrize("R", [1, 3])
+def test_per_tensor_decode_sum_tiny_norms(level_bytes, R):
+    """gq_qsgd_decode_sum against qsgd_compressor.py:69-70 spelled out: subnormal norms, level 0 with both signs, and for int32 levels
+    the INT_MIN of a NaN quotient on a zero-norm bucket (why that instantiation keeps the product by 2 sign - 1)"""
+    from gq_amd import native
+    d, nb, n_bit = 8, 8, 3
+    rs = np.random.RandomState(R + level_bytes)
+    norm = np.stack([np.array([2.0 ** -130, 2.0 ** -149, 0.0, -0.0, 2.0 ** -126, 1.5 * 2.0 ** -127, 3.0, 2.0 ** -140], f32) * f32(1 + r) for r in range(R)])
+    sg = rs.randint(0, 2, (R, nb, d)).astype(np.uint8)
+    lv = rs.randint(0, 9, (R, nb, d)).astype(np.int64)
+    lv[:, :, 0], sg[:, :, 0], lv[:, :, 1], sg[:, :, 1] = 0, 0, 0, 1
+    if level_bytes == 4:
+        lv[:, 2:4, 2:6] = -2 ** 31
+    assert nb * d <= 64
+    with np.errstate(all="ignore"):
+        parts = [(lv[r].astype(f32) * (f32(2) * sg[r].astype(f32) - f32(1))) * norm[r][:, None] / f32(1 << n_bit) for r in range(R)]
+    if level_bytes == 1:
+        for r in range(R):
+            assert qc.same_bits(parts[r], qc.decode_one(lv[r].astype(np.uint32) | (sg[r].astype(np.uint32) << np.uint32(8)), norm[r], n_bit, 9))
+    exp = qc.mean_of(parts, R == 1).reshape(-1)
+    assert not np.isnan(exp).any() and (np.abs(exp[exp != 0]) < f32(2.0 ** -126)).sum() >= 16
+    out = torch.full((nb * d + 4,), OUT_FILL, dtype=torch.float32, device=_dev())
+    native.qsgd_decode_sum(_t(norm.reshape(-1)), _t(sg.reshape(-1)), _t(lv.astype(np.uint8 if level_bytes == 1 else np.int32).reshape(-1)),
+                           d, n_bit, out[:nb * d], R=R)
+    got = out.cpu().numpy()
+    assert qc.same_bits(got[:nb * d], exp) and np.all(got[nb * d:] == OUT_FILL)
+
+
 # ---- part, set_table, set_dense ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("bits,wide", [(4, False), (8, False), (4, True)])
 def test_part_set_table_set_dense(bits, wide):

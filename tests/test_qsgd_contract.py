@@ -185,6 +185,37 @@ def test_payload_wires_hold_every_code_and_the_mean_is_the_oracles(oracle, bits)
     assert L.code_off[-1] + 4 * 6 * bits // 8 == L.ub or (4 * 6 * bits // 8) % 16        # the wire ends with its last codes
 
 
+# ---- the one de-quantiser (csrc/qsgd_common.hpp) --------------------------------------------------------------------------------------
+DEQ_NORMS = np.array([0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x00000123, 0x007FFFFF, 0x807FFFFF, 0x00800000, 0x80800000,
+                      0x00800001, 0x00FFFFFF, 0x01000000, 0x3F800000, 0xBFC00000, 0x7F7FFFFF, 0xFF7FFFFF, 0x7E967699, 0x7F800000,
+                      0xFF800000, 0x7FC00000, 0xFFC00001], np.uint32).view(f32)
+
+
+@pytest.mark.parametrize("n_bit", [1, 2, 6, 8, 15, 30])
+def test_the_two_spellings_of_the_dequantiser_are_the_same_bits(n_bit):
+    """qsgd_compressor.py:69-70 as (l * (2 sign - 1)) * norm / s, and as ((+-l) * norm) * 2^-n_bit with the sign on the float's sign bit
+    (decode_one, the form the kernels use): l * -1 = -l and 0 * -1 = -0 exactly, and both scalings are one correct rounding of the same
+    exact real -- for every code of the 4- and 8-bit widths and (at five norms) of the 16-bit width, a sample of 16-bit codes elsewhere;
+    norms 0, -0, subnormals, the smallest normals, 2^-126 (1 + ulp), huge, +-inf, NaN.  Any NaN equals any NaN."""
+    assert DEQ_NORMS[9] == f32(2.0 ** -126) * (f32(1) + f32(2.0 ** -23)) and np.isnan(DEQ_NORMS[-2:]).all() and np.isinf(DEQ_NORMS[-4:-2]).all()
+    assert np.signbit(DEQ_NORMS[1]) and DEQ_NORMS[1] == 0 and (np.abs(DEQ_NORMS[2:7]) < f32(2.0 ** -126)).all()
+    s, inv_s = f32(1 << n_bit), f32(2.0 ** -n_bit)
+    assert f32(1) / s == inv_s
+    rs = np.random.RandomState(n_bit)
+    for bits in (4, 8, 16):
+        every = np.arange(1 << bits, dtype=np.uint32)
+        norms = DEQ_NORMS if bits < 16 else np.concatenate([DEQ_NORMS[[0, 2, 9, 14, 17]], DEQ_NORMS, rs.randint(0, 1 << 32, 40, dtype=np.int64).astype(np.uint32).view(f32)])
+        code = np.stack([every if bits < 16 or i < 5 else rs.randint(0, 1 << 16, every.size).astype(np.uint32) for i in range(norms.size)])
+        l, sgn = code & np.uint32((1 << (bits - 1)) - 1), code >> np.uint32(bits - 1)
+        with np.errstate(all="ignore"):
+            a = (l.astype(f32) * (f32(2) * sgn.astype(f32) - f32(1))) * norms[:, None] / s
+        b = qc.decode_one(code, norms, n_bit, bits)
+        assert a.dtype == f32 and b.dtype == f32 and qc.same_bits(a, b, True)
+        assert np.array_equal(np.isnan(a), np.isnan(b))
+        sub = np.isfinite(a) & (np.abs(a) < f32(2.0 ** -126)) & (a != 0)
+        assert sub.any() or n_bit == 30               # subnormal results are among them (2^-30: those norms' products round to 0)
+
+
 # ---- the draws ----------------------------------------------------------------------------------------------------------------------
 def test_draws_agree_with_the_other_host_restatements():
     import importlib
