@@ -218,6 +218,16 @@ int gq_hsq_levels_decode(const float *u, int64_t M, int n_bit, int random_mode, 
  *                                    error buffer (float *, aligned like grad; 0 = no error feedback for this tensor) }
  *   seg_minmax uint32[nseg][2]     order-mapped (min,max) of u; the caller resets it before each encode to
  *                                  { 0xFFFFFFFF, 0 }
+ *                                  What the decode relies on (tests/hsq_decode_contract.py builds its wires to exactly this):
+ *                                  - a codes or levels section that is READ is readable up to the next multiple of 16 bytes
+ *                                    (gq_amd.codecs pads every section so): the d = 16 byte-code kernels fetch the codes and
+ *                                    the byte levels of four subvectors as one aligned 32-bit word, a packed group as one
+ *                                    unaligned word (GQ_LEVELS_PACKED6 above); what the padding holds never reaches `out`;
+ *                                  - payload r's (lb, ub) at gathered + r * user_stride_bytes + offset is 4-byte aligned;
+ *                                  - the float offset in `out` is a multiple of 4, and `out` 16-byte aligned, when
+ *                                    d % 4 == 0 (every dispatch then stores float4); any offset when d % 4 != 0;
+ *                                  - nothing else is written: not a float of `out` between the tensors' spans, not a byte
+ *                                    of `gathered`.
  *   u_flat     float[ntiles*64]    projection spill, padded index space
  *   workspace  gq_hsq_workspace_bytes(ntiles*64) bytes (same contract as gq_hsq_encode); may be NULL when
  *              gq_hsq_batched_path() says GQ_BATCH_EXACT
