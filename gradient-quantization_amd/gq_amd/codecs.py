@@ -10,7 +10,8 @@ device memory, through gq_amd.native).
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
     MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
-    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey
+    MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP8 code per element
+    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -24,7 +25,7 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (IdenticalCompressor, MaureySparsification, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
@@ -540,7 +541,7 @@ class QSGDCodec(object):
 
 
 class _SparseCodec(object):
-    """What TopKCodec, SignCodec and MaureyCodec share: every call is a one-tensor group of the codec's multi-tensor class
+    """What TopKCodec, SignCodec, MaureyCodec and MXCodec share: every call is a one-tensor group of the codec's multi-tensor class
     (GROUP, set below that class), and roundtrip / encode_decode_into return the compress launches' own dense decode, not a
     decode of the wire.  A subclass sets numel, shape and nbytes; `extra` are further arguments of its group's encode."""
 
@@ -660,6 +661,52 @@ class MaureyCodec(_SparseCodec):
     def _draws(self, r, dev):
         if r is None and self.uses_reference_draws():
             r = torch.rand(self.k).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
+        return (r, {0: 0}) if r is not None else None
+
+    def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None):
+        _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out)
+
+
+def mx_section_bytes(numel, fmt):
+    """Bytes of one tensor's section of the microscaling wire (include/gq_mx.h): ceil(numel / 32) scale bytes, 16-byte aligned,
+    then 16 (fp4) or 32 (fp8) code bytes per block.  fmt: 'fp4' / 'fp8' or native.MX_FP4 / MX_FP8."""
+    fmt = native.MX_FORMATS.get(fmt, fmt)
+    nb = -(-numel // native.MX_BLOCK)
+    return _up(nb) + nb * native.MX_BLOCK * native.MX_CODE_BITS[fmt] // 8
+
+
+class MXCodec(_SparseCodec):
+    """MXCompressor on the HIP kernels (libgq_mx.so).  Wire per tensor: the blocks' scale bytes (E8M0, padded to 16 bytes), then
+    one FP4 code per element, element 2i in the low nibble, or one FP8 byte -- mx_section_bytes.  The wire carries the decoded
+    tensor exactly (-0, and NaN for a block that held an infinity or a NaN), so ring mode ships it as it is.  Every call is a
+    one-tensor BatchedMX; roundtrip / encode_decode_into return the compress launch's own dense decode.
+    The draws (compressor.random; otherwise the rounding is to nearest-even and there are none), by the compressor's gq_rng:
+    "device" -- the library's counter-based generator, a fresh seed per call (the multi-tensor launch keys its stream by the
+    quantizer's { seed, step } words); "reference" -- torch.rand(numel) per tensor from the CPU generator, in parameter order,
+    handed to the kernels as given draws; "keyed" draws like "device".
+    `r` (float32 [numel] on the device) hands a call its uniforms whatever the mode; `seed` pins the device generator's."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        if numel < 1:
+            raise ValueError("MXCodec: a tensor of %d elements" % numel)
+        self.format = native.MX_FORMATS[compressor.format]
+        self.random = bool(compressor.random)
+        self.nbytes = mx_section_bytes(numel, self.format)
+        self._rng = getattr(compressor, "_rng", "device")
+
+    def uses_reference_draws(self):
+        return self.random and self._rng == "reference"
+
+    def draw_count(self):
+        return self.numel
+
+    def _wire_bytes(self):
+        return self.nbytes      # (never empty: numel >= 1)
+
+    def _draws(self, r, dev):
+        if r is None and self.uses_reference_draws():
+            r = torch.rand(self.numel).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
         return (r, {0: 0}) if r is not None else None
 
     def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None):
@@ -1446,7 +1493,7 @@ class BatchedQSGD(_BatchedBase):
 
 
 class _ItemGroup(_BatchedBase):
-    """What BatchedTopK, BatchedSign and BatchedMaurey share: a segment table over an item table (native._ItemBatch), a compress
+    """What BatchedTopK, BatchedSign, BatchedMaurey and BatchedMX share: a segment table over an item table (native._ItemBatch), a compress
     that also writes the dense decoded tensors where a caller asks for them -- which is what roundtrip returns -- and a
     decode-mean without a step tail."""
 
@@ -1736,6 +1783,89 @@ class BatchedMaurey(_ItemGroup):
 MaureyCodec.GROUP = BatchedMaurey
 
 
+class BatchedMX(_ItemGroup):
+    """All MXCompressor tensors of one format in ONE gq_mx_compress_batched launch and ONE gq_mx_decode_sum_batched launch
+    (include/gq_mx.h).  No scratch.  Element i of tensor s owns draw first draw + i of the group's stream (first draw = the
+    elements of the tensors before it).  The compress also writes the dense decode where a caller asks for it (the two-phase
+    re-compress returns it); with error feedback it updates the gradient and the residual in the same launch.  Deterministic
+    rounding, or gq_rng "device" with the quantizer's { seed, step } pairs: nothing in the launches changes from record to
+    record, they replay from a HIP graph (and draw afresh every step); "reference": the quantizer's draw plan (torch.rand(numel)
+    per tensor, in parameter order) as given draws; "keyed" / a group without pairs: a fresh seed per call."""
+
+    align = 4
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is MXCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.format, int(codec.random), codec._rng)
+
+    def _layout(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        """The group's tables (host work only; the launch descriptor is __init__'s) -> (tensors, items)."""
+        ns = [codecs[i].numel for i in idxs]
+        first_draw = list(itertools.accumulate([0] + ns[:-1]))
+        self._first_draw, self.ndraws = first_draw, sum(ns)
+        # an item is a run of elements (numel >= 1: never none); 16-byte aligned views in the output buffer: float4 stores
+        return self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                lambda cd: -(-cd.numel // native.MX_ITEM_ELEMS), {6: first_draw}, 4)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        nseg, item = self._layout(codecs, offsets, idxs, device, slots, user_bytes, dense)
+        c0 = self.codecs[0]
+        self.format, self.random = c0.format, c0.random
+        self.counter = self.random and c0._rng == "device"      # the quantizer gives such a group its { seed, step } pairs
+        self.reference_draws = self.random and c0._rng == "reference"
+        self._r = None
+        self._batch = native.MXBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.format)
+
+    def graphable(self):
+        return not self.random or (self.counter and self.rng_pairs is not None)
+
+    def _given_draws(self, draws):
+        """draws = (r_all on the device, {parameter index: offset of its numel draws}) -> float32 [ndraws] in the group's layout."""
+        r_all, offsets = draws
+        if self._r is None:
+            self._r = torch.empty(self.ndraws, dtype=torch.float32, device=self.device)
+        if len(self.idxs) == 1 and r_all.numel() >= offsets[self.idxs[0]] + self.ndraws and r_all.dtype == torch.float32:
+            return r_all[offsets[self.idxs[0]]:offsets[self.idxs[0]] + self.ndraws]
+        for i, cd, fd in zip(self.idxs, self.codecs, self._first_draw):
+            self._r[fd:fd + cd.numel].copy_(r_all[offsets[i]:offsets[i] + cd.numel])
+        return self._r
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None, seed=None):
+        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
+        feedback in the same launch (t += ef_scale*err before the rounding, err = t - decoded after it, both in place).
+        draws (given uniforms, see _given_draws): required for gq_rng "reference", taken in any stochastic mode when handed in.
+        seed: the device generator's seed for this call.  graph_header, table_current: see _choose_header; dense, rng_slot: see
+        BatchedHSQ.encode."""
+        given = self.random and draws is not None and all(i in draws[1] for i in self.idxs)
+        if self.reference_draws and not given:
+            return False
+        if wire_user.data_ptr() % 16:
+            return False
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
+            return False
+        counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
+        if not self.random:
+            mode, sd, r = native.RANDOM_OFF, 0, None
+        elif given:
+            mode, sd, r = native.RANDOM_GIVEN, 0, self._given_draws(draws)
+        elif seed is not None:
+            mode, sd, r = native.RANDOM_DEVICE, int(seed), None
+        elif self.counter and counter_seed is not None:
+            mode, sd, r = native.RANDOM_DEVICE_COUNTER, counter_seed, None
+        else:
+            mode, sd, r = native.RANDOM_DEVICE, _next_seed() ^ salt, None
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, mode, sd, r, out, ef_scale if errs is not None else None)
+        return True
+
+
+MXCodec.GROUP = BatchedMX
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -1751,6 +1881,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return SignCodec(compressor, numel, shape)
     if isinstance(compressor, MaureySparsification):
         return MaureyCodec(compressor, numel, shape)
+    if isinstance(compressor, MXCompressor):
+        return MXCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

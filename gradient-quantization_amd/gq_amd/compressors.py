@@ -559,6 +559,41 @@ class MaureySparsification(object):
         return (scale * out).view(self.shape)
 
 
+class MXCompressor(object):
+    """Block-scaled small floats (OCP Microscaling; no counterpart in the reference's catalogue): 32 consecutive elements share a
+    power-of-two scale byte, every element is an FP4 (E2M1) or FP8 (E4M3) value -- 4.25 or 8.25 bits per element, unbiased
+    under stochastic rounding, relative precision inside a block (include/gq_mx.h defines it to the bit).  args.mx_format:
+    'fp4' (the default) or 'fp8'; args.random: stochastic rounding (otherwise to nearest, ties to the even code); gq_rng: where
+    the draws come from (MXCodec).  compress returns the decoded tensor -- the wire carries it exactly -- and decompress is the
+    identity, as for SignSGDCompressor.  HIP kernels only (libgq_mx.so): a float32 tensor on the device."""
+
+    def __init__(self, size, shape, args):
+        fmt = getattr(args, "mx_format", None) or "fp4"
+        if fmt not in ("fp4", "fp8"):
+            raise ValueError("mx_format must be 'fp4' or 'fp8', got %r" % (fmt,))
+        self.format = fmt
+        self.random = bool(getattr(args, "random", True))
+        self.size, self.shape = size, shape
+        self._rng = _rng_mode(args)
+
+    def compress(self, vec):
+        from .codecs import MXCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("MXCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), got %s on %s"
+                            % (vec.dtype, vec.device))
+        n = vec.numel()
+        if n == 0:
+            return vec.clone()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = MXCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification"]
+           "MaureySparsification", "MXCompressor"]

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (IdenticalCompressor, MaureySparsification, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
@@ -45,6 +45,7 @@ quantizer_choices = {          # main.py:20-26
     'pvq': ProbabilisticVectorCompressor,      # the unbiased vector quantiser (not in main.py's table: INTEGRATION.md)
     'rq': ResidualCompressor,                  # two stages: hsq, then pvq on what it leaves (not in main.py's table either)
     'maurey': MaureySparsification,            # the unbiased sparsifier: k draws with P(i) = |v_i| / ||v||_1 (likewise)
+    'mx': MXCompressor,                        # block-scaled small floats (MXFP4 / MXFP8, --mx-format): not in the reference at all
 }
 
 
@@ -169,6 +170,8 @@ def build_parser():
     p.add_argument('--momentum-correction', dest='momentum_correction', type=float, default=None, metavar='M',
                    help='--quantizer topk only, not with --ef: momentum correction and momentum factor masking (Deep Gradient Compression) '
                         'with momentum M in the quantizer; the optimizer then runs with momentum 0 (weight decay stays with it)')
+    p.add_argument('--mx-format', dest='mx_format', type=str, default='fp4', choices=['fp4', 'fp8'],
+                   help='--quantizer mx: the element format under the per-block scale byte (4.25 or 8.25 bits per element)')
     p.add_argument('--seed', type=int, default=1)
     p.add_argument('--train-size', type=int, default=4096, help='synthetic samples per epoch')
     p.add_argument('--log-interval', type=int, default=8, help='iterations between JSON log lines')

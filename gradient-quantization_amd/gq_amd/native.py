@@ -609,7 +609,7 @@ def qsgd_decode_sum(norm, signs, levels, d, n_bit, out, R=1):
     _check(rc, "gq_qsgd_decode_sum")
 
 
-# ---- the item-table libraries: one descriptor base for top-k, sign and Maurey ------------------------------------------------
+# ---- the item-table libraries: one descriptor base for top-k, sign, Maurey and MX -----------------------------------------------
 class _ItemBatch(_Tables):
     """A descriptor over a segment table and an item table (item_seg names the tensor of every item) -- gq_topk_batch,
     gq_sign_batch, gq_maurey_batch -- and its <prefix>decode_sum_batched launch.  A subclass names its library (LIBRARY) and
@@ -957,6 +957,54 @@ class MaureyBatch(_ItemBatch):
                                                ctypes.c_float(_NAN if ef_scale is None else ef_scale),
                                                _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
         _check(rc, "gq_maurey_compress_batched", MAUREY_LIBRARY)
+
+
+# ---- block-scaled small floats (MXFP4 / MXFP8): libgq_mx.so (include/gq_mx.h) ---------------------------------------------------
+MX_ABI_VERSION = 1
+MX_EXPORTS = ["gq_mx_abi_version", "gq_mx_last_error", "gq_mx_compress_batched", "gq_mx_decode_sum_batched"]
+MX_BLOCK = 32               # GQ_MX_BLOCK: elements that share a scale byte
+MX_ITEM_ELEMS = 4096        # GQ_MX_ITEM_ELEMS: elements per item
+MX_FP4, MX_FP8 = 0, 1       # GQ_MX_FP4 / GQ_MX_FP8
+MX_FORMATS = {"fp4": MX_FP4, "fp8": MX_FP8}
+MX_CODE_BITS = {MX_FP4: 4, MX_FP8: 8}
+
+MX_LIBRARY = Library("libgq_mx.so", "GQ_MX_LIB_PATH", "gq_mx_", MX_ABI_VERSION, MX_EXPORTS)
+MX_LIB_PATH = MX_LIBRARY.path
+
+
+def mx_lib():
+    return MX_LIBRARY.handle or _load(MX_LIBRARY)
+
+
+class _MXBatchStruct(ctypes.Structure):       # gq_mx_batch (include/gq_mx.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
+                ("ndense", ctypes.c_int32), ("format", ctypes.c_int32)]
+
+
+class MXBatch(_ItemBatch):
+    """The multi-tensor microscaling launches: gq_mx_compress_batched (scale bytes and codes, + the dense decode and the residual)
+    and gq_mx_decode_sum_batched.  No scratch: both are one launch over the segment table."""
+
+    LIBRARY, STRUCT = MX_LIBRARY, _MXBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4):
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt))
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.format)
+
+    def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
+        """random_mode: RANDOM_OFF (nearest, ties to even), RANDOM_GIVEN (r: float32, element i of tensor s reads
+        r[first draw + i]), RANDOM_DEVICE (seed) or RANDOM_DEVICE_COUNTER (seed = the address of a { seed, step } pair).
+        out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
+        (seg_table[:, 7] = error buffers)."""
+        rc = self.L.gq_mx_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
+                                           _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
+                                           ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                           ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                           _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_mx_compress_batched", MX_LIBRARY)
 
 
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------

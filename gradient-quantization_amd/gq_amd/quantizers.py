@@ -46,8 +46,8 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedDGC, BatchedHSQ, BatchedMaurey, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
-    MaureyCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec,
+    BatchedDGC, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
+    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -228,7 +228,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -270,10 +270,11 @@ class PSQuantizer(object):
         # draws twice (probabilistic_vector_compressor.py:52 for the codewords, then the level quantiser's): it owns two
         # consecutive slices in that order (PVQCodec.draw_count); a ResidualCompressor tensor up to three: stage 1's level draws,
         # stage 2's codeword draws, stage 2's level draws (residual_compressor.py:17-24; ResidualCodec.draw_runs).  A
-        # MaureySparsification tensor owns k: one uniform per draw (MaureyCodec; not the reference's k x n matrix).
+        # MaureySparsification tensor owns k: one uniform per draw (MaureyCodec; not the reference's k x n matrix); an MXCompressor
+        # tensor that rounds stochastically one per element (MXCodec).
         self._draw_off, n = {}, 0
         for i, c in enumerate(self.codecs):
-            if isinstance(c, (HSQCodec, ResidualCodec, MaureyCodec)) and c.uses_reference_draws():
+            if isinstance(c, (HSQCodec, ResidualCodec, MaureyCodec, MXCodec)) and c.uses_reference_draws():
                 self._draw_off[i] = n
                 n += c.draw_count()
         self._draw_total = n

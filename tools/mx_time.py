@@ -1,0 +1,170 @@
+"""Time the microscaling kernels (libgq_mx.so) on one MI355X, next to signSGD and QSGD in the same process:
+
+    python tools/mx_time.py [--out FILE]      (default: profiles/mx_time.jsonl)
+
+Rows (one JSON line each):
+  resnet50_step   PSQuantizer record + apply over the ResNet-50 parameter list (tests/golden/resnet50_cifar_shapes.json), one
+                  user, default launches (graph replay), gradients at fixed addresses: --quantizer mx with fp4 and fp8,
+                  --quantizer sign, and QSGD --c-dim 32 --n-bit 2 (the same 4-bit codes, the same draw per element), alternated
+                  in this process, three rounds each; wire bytes per user against the dense 94,083,376.
+  single_25m      one 25 M-element tensor: the compress launch alone (fp4 / fp8, stochastic rounding from the device generator
+                  and deterministic) and the decode-mean at R = 1 and 8, next to the QSGD c_dim 32 bucketed compress launch
+                  (the same bytes moved, one draw per element) and the sign compress; mx_fp4_over_qsgd is the ratio the README
+                  quotes.  *_given_*: the draws handed in (no hash); *_graphed_*: ten launches replayed from one HIP graph (the
+                  device's time without the host's share of an eager launch).
+Times: HIP events around a window of back-to-back calls after untimed ones, median of the windows, microseconds per call; the
+paths of a row are alternated round by round and the minimum over the rounds is reported next to every round."""
+import argparse
+import json
+import os
+import sys
+from argparse import Namespace
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gradient-quantization_amd"))
+
+from gq_amd.codecs import BatchedMX, BatchedQSGD, BatchedSign, MXCodec, QSGDCodec, SignCodec  # noqa: E402
+from gq_amd.compressors import MXCompressor, QSGDCompressor, SignSGDCompressor  # noqa: E402
+from gq_amd.quantizers import PSQuantizer  # noqa: E402
+
+DENSE_RESNET50_BYTES = 94083376
+
+
+def timed(fn, iters=50, warm=20, windows=5):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    res = []
+    for _ in range(windows):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(iters):
+            fn()
+        e.record()
+        torch.cuda.synchronize()
+        res.append(s.elapsed_time(e) / iters * 1e3)
+    return sorted(res)[len(res) // 2]
+
+
+def graphed(fn, reps=10):
+    """Microseconds per call of `fn` with `reps` calls captured into one HIP graph and the graph replayed."""
+    fn()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(reps):
+            fn()
+    return timed(graph.replay, iters=20, warm=5) / reps
+
+
+def _args(**kw):
+    base = dict(no_cuda=False, random=1, ef=False, two_phase=False, scale="exp", num_users=1, mode="ps", c_dim=32, k_bit=8, n_bit=2,
+                cr=256, mx_format="fp4")
+    base.update(kw)
+    return Namespace(**base)
+
+
+def resnet50_rows(dev):
+    with open(os.path.join(ROOT, "tests", "golden", "resnet50_cifar_shapes.json")) as f:
+        shapes = json.load(f)["parameter_shapes"]
+    torch.manual_seed(0)
+    src = [torch.randn(s, device=dev) * 1e-2 for s in shapes]
+    variants = {}
+    for name, comp, kw in (("mx_fp4", MXCompressor, {}), ("mx_fp8", MXCompressor, {"mx_format": "fp8"}),
+                           ("sign", SignSGDCompressor, {"random": 0}), ("qsgd_c32_n2", QSGDCompressor, {})):
+        params = [torch.nn.Parameter(torch.zeros(s, device=dev)) for s in shapes]
+        variants[name] = (PSQuantizer(comp, params, _args(**kw)), params)
+    rows = {}
+    for rnd in range(3):
+        for name, (q, params) in variants.items():
+            fixed = [g.clone() for g in src]
+
+            def step():
+                for p, g in zip(params, fixed):
+                    p.grad = g
+                q.record(0, 0)
+                q.apply()
+            rows.setdefault(name, []).append(timed(step, iters=100, warm=30, windows=3))
+    out = []
+    for name, ts in rows.items():
+        q = variants[name][0]
+        wb = q.wire_bytes_per_user()
+        out.append({"case": "resnet50_step", "path": name, "us_per_step_rounds": [round(t, 2) for t in ts], "us_per_step_min": round(min(ts), 2),
+                    "wire_bytes_per_user": wb, "dense_bytes_per_user": DENSE_RESNET50_BYTES,
+                    "wire_over_dense": round(wb / DENSE_RESNET50_BYTES, 4), "record_paths": dict(q.record_paths)})
+    return out
+
+
+def single_rows(dev, n=25_000_000):
+    torch.manual_seed(1)
+    t = torch.randn(n, device=dev)
+    paths, groups, wires = {}, {}, {}
+
+    def one(cls, cd):
+        g = cls([cd], [0], [0], dev, 1, cd.nbytes)
+        wire = torch.zeros((8, cd.nbytes), dtype=torch.uint8, device=dev)
+        assert g.encode([t], wire[0], 0, 0)
+        for r in range(1, 8):
+            wire[r].copy_(wire[0])
+        return g, wire
+
+    for fmt in ("fp4", "fp8"):
+        for random in (1, 0):
+            name = "mx_%s_%s" % (fmt, "stochastic" if random else "nearest")
+            cd = MXCodec(MXCompressor(n, (n,), _args(mx_format=fmt, random=random)), n, (n,))
+            groups[name], wires[name] = one(BatchedMX, cd)
+    qc = QSGDCodec(QSGDCompressor(n, (n,), _args()), n, (n,))
+    BatchedQSGD.place_lone_buckets([qc])
+    assert qc.bits == 4 and qc.d == 32 and not BatchedQSGD.is_wide(qc)
+    groups["qsgd_c32_n2"], wires["qsgd_c32_n2"] = one(BatchedQSGD, qc)
+    groups["sign"], wires["sign"] = one(BatchedSign, SignCodec(None, n, (n,)))
+    for rnd in range(3):
+        for name, g in groups.items():
+            w = wires[name]
+            paths.setdefault(name, []).append(timed(lambda: g.encode([t], w[0], 0, 0)))
+    row = {"case": "single_25m", "elements": n}
+    for name, ts in paths.items():
+        row[name + "_compress_us_rounds"] = [round(x, 2) for x in ts]
+        row[name + "_compress_us"] = round(min(ts), 2)
+        row[name + "_wire_bytes"] = int(wires[name].shape[1])
+    # what the stochastic path costs beside the hash: the same launch with the draws handed in (GQ_RANDOM_GIVEN: 4 B more read per
+    # element, no hash, the same fraction rebuild and comparison)
+    r = torch.rand(n, device=dev)
+    for fmt in ("fp4", "fp8"):
+        g, w = groups["mx_%s_stochastic" % fmt], wires["mx_%s_stochastic" % fmt]
+        row["mx_%s_given_compress_us" % fmt] = round(timed(lambda: g.encode([t], w[0], 0, 0, draws=(r, {0: 0}))), 2)
+    # the device's own time: ten launches captured into one HIP graph and replayed (no host work between them), per launch --
+    # against the eager figures above, which cannot go below what the host needs to issue a launch
+    for name, g in groups.items():
+        w = wires[name]
+        row[name + "_compress_graphed_us"] = round(graphed(lambda: g.encode([t], w[0], 0, 0)), 2)
+    g, w = groups["mx_fp4_stochastic"], wires["mx_fp4_stochastic"]
+    row["mx_fp4_given_compress_graphed_us"] = round(graphed(lambda: g.encode([t], w[0], 0, 0, draws=(r, {0: 0}))), 2)
+    row["mx_fp4_over_qsgd_graphed"] = round(row["mx_fp4_stochastic_compress_graphed_us"] / row["qsgd_c32_n2_compress_graphed_us"], 3)
+    row["mx_fp4_over_qsgd"] = round(row["mx_fp4_stochastic_compress_us"] / row["qsgd_c32_n2_compress_us"], 3)
+    row["mx_fp4_over_qsgd_rounds"] = [round(a / b, 3) for a, b in zip(paths["mx_fp4_stochastic"], paths["qsgd_c32_n2"])]
+    for name in ("mx_fp4_stochastic", "mx_fp8_stochastic", "qsgd_c32_n2", "sign"):
+        g, w = groups[name], wires[name]
+        for R in (1, 8):
+            row["%s_decode_mean_R%d_us" % (name, R)] = round(timed(lambda: g.decode_mean(w[:R], R)), 2)
+    nb = row["mx_fp4_stochastic_wire_bytes"]
+    row["mx_fp4_compress_TBps"] = round((4 * n + nb) / (row["mx_fp4_stochastic_compress_us"] * 1e-6) / 1e12, 2)
+    return [row]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx_time.jsonl"))
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    rows = single_rows(dev) + resnet50_rows(dev)
+    lines = [json.dumps(r) for r in rows]
+    print("\n".join(lines))
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
