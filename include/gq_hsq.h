@@ -228,6 +228,27 @@ int gq_hsq_levels_decode(const float *u, int64_t M, int n_bit, int random_mode, 
  *                                    d % 4 == 0 (every dispatch then stores float4); any offset when d % 4 != 0;
  *                                  - nothing else is written: not a float of `out` between the tensors' spans, not a byte
  *                                    of `gathered`.
+ *                                  What the encode writes and relies on (tests/hsq_encode_contract.py holds every path to it):
+ *                                  - exactly M * code_bytes bytes of a tensor's code section: no byte of its padding up to the
+ *                                    next multiple of 16, no other byte of the wire;
+ *                                  - u_flat[first tile * 64 + i] for i < M; a padding slot of the tensor's last tile keeps its
+ *                                    value or becomes +0 (the exact path stores the projection of the zero rows it pads with);
+ *                                  - seg_minmax[s] = the caller's words folded (integer min / max) with the order-mapped
+ *                                    (min, max) of the tensor's u.  A tensor that has a NaN projection (a NaN gradient, or an
+ *                                    infinite one: inf - inf, 0 * inf) gets { min(., 0x003FFFFF), max(., 0xFFC00000) } folded in
+ *                                    on top -- the images of -NaN / +NaN, so that (lb, ub) un-map to NaN as torch.min /
+ *                                    torch.max give it; its finite projections may or may not be folded in besides;
+ *                                  - with ef_scale: grad <- v, bit for bit, over the M * d floats of every row that has an
+ *                                    error buffer; the error buffers are only read; a row without one is only read;
+ *                                  - the workspace's fix-up log is NOT written (the per-tensor entry points write it).
+ *                                  What the level launches write (gq_hsq_levels_batched, gq_hsq_levels_decode_batched):
+ *                                  - exactly M level units (GQ_LEVELS_PACKED6: 3 * ceil(M / 4) bytes, slots past M zero) and,
+ *                                    unless level_bytes == 0, the 8 bytes of (lb, ub) = the un-mapped seg_minmax[s] (lb == ub:
+ *                                    all levels 0); level_bytes == 0: the M projections, and the 8 bytes are NOT written;
+ *                                  - the dense_table copies; with write_error the M * d floats of every error buffer; the
+ *                                    fused launch the tensors' spans of `out` and the tail's outputs.  The codes, the sections'
+ *                                    padding, u_flat, r_flat, seg_minmax (but through the tail's reset words) and the
+ *                                    gradients are only read.
  *   u_flat     float[ntiles*64]    projection spill, padded index space
  *   workspace  gq_hsq_workspace_bytes(ntiles*64) bytes (same contract as gq_hsq_encode); may be NULL when
  *              gq_hsq_batched_path() says GQ_BATCH_EXACT

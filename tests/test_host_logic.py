@@ -154,7 +154,7 @@ def test_compressor_constructor_contract():
     assert c.code_dtype == torch.int32 and c.codewords.shape == (512, 12)
     c = NearestNeighborCompressor(64, torch.Size([64]), make_args(c_dim=8, k_bit=0, n_bit=32))
     assert c.K == 8 and not c.compressed_norm
-    cw = c.codewords.double()
+    cw = c.codewords.double().cpu()      # (the codewords live on the GPU where there is one)
     assert torch.allclose(cw @ cw.t(), torch.eye(8, dtype=torch.float64), atol=1e-5)  # orthogonal
     with pytest.raises(AssertionError):
         NearestNeighborCompressor(1030, torch.Size([1030]), make_args())       # never divisible
