@@ -29,6 +29,17 @@ static int fail(int code, const char *fmt, ...) {
         if (e__ != hipSuccess) return gql::fail(GQ_ERR_HIP, "%s: %s", what, hipGetErrorString(e__)); \
     } while (0)
 
+// compute units of the current device, asked once (256 where the runtime does not say)
+static int cu_count() {
+    static int cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        return n;
+    }();
+    return cus;
+}
+
 // the identity-compressed tensors into the wire, a workgroup of THREADS lanes per tensor in turn (dense_table: int64
 // [ndense, 3] = source pointer, byte offset in the wire, elements)
 template <int THREADS>

@@ -33,16 +33,6 @@ __host__ __device__ constexpr int points_per_lane(int D4) { return D4 <= 4 ? 4 :
 
 typedef unsigned long long u64;
 
-static int cu_count_here() {
-    static int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
-            n = 256;
-        return n;
-    }();
-    return cus;
-}
-
 __global__ __launch_bounds__(THREADS) void kmeans_zero_kernel(u64 *__restrict__ ws, int64_t words) {
     for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < words; i += (int64_t)gridDim.x * THREADS) ws[i] = 0;
 }
@@ -211,7 +201,7 @@ static Plan plan(int N, int d, int K, int acc_mode) {
     p.rows = (int)(fit < (size_t)K ? fit : (size_t)K);
     p.lds = part + p.rows * row_bytes;
     const int per_pass = THREADS * points_per_lane(p.D4);
-    const int64_t passes = ((int64_t)N + per_pass - 1) / per_pass, cap = (int64_t)cu_count_here() * GQ_KMEANS_BLOCKS_PER_CU;
+    const int64_t passes = ((int64_t)N + per_pass - 1) / per_pass, cap = (int64_t)gql::cu_count() * GQ_KMEANS_BLOCKS_PER_CU;
     p.grid = (int)(passes < cap ? passes : cap);
     return p;
 }

@@ -14,7 +14,7 @@
 // cross-check and the fallback for wider subvectors: one subvector per lane; C_dagger is broadcast from LDS (or
 // read through L1 when it does not fit); two sweeps over the K codewords (l1, then the inverse-CDF walk) with the
 // same fmaf chain as the NearestNeighbor encode, ~2*K*d FMAs per subvector.
-#include "pvq_walk.hpp"   // the one-sweep + walk tile encode, shared with pvq_batched.hip
+#include "pvq_walk.hpp"   // the one-sweep + walk tile encode, shared with pvq_batched.hip and rq_batched.hip
 
 namespace gq {
 
@@ -380,9 +380,11 @@ __global__ __launch_bounds__(ENC_THREADS) void pvq_encode_lds_kernel(const float
 // launch took 194 us instead of 153.)  $GQ_PVQ_EPS (tests) widens eps so that these paths run for most lanes.
 // Per tile: 128 MFMAs + ~1,400 VALU instructions instead of 256 + ~2,900.
 
-// Registers: d <= 16 is held to three waves per SIMD (168 VGPRs; the allocator took 169 on its own: 144.8 against 148.1 us);
-// d = 32 needs its 200+ (held to three waves it spills: 175 against 129 us).
-// The tile encode itself is pw_encode_tile (pvq_walk.hpp), which the multi-tensor launch of libgq_pvq.so runs too.
+// Registers: d <= 16 is held to three waves per SIMD (at most 168 VGPRs; the allocator took 169 on its own: 144.8 against 148.1 us);
+// d = 32 needs its 200+ (held to three waves it spills: 175 against 129 us).  What the build reports: profiles/pvq_run_ab.txt.
+// The tile encode itself is pw_encode_tile (pvq_walk.hpp), which the multi-tensor launches of libgq_pvq.so and libgq_rq.so run
+// too; the LDS carve-up, the row fetch and stage 1's residual are theirs as well.  The loop is this kernel's own: it strides by
+// the grid, folds into the workspace partials and carries the PVQ_DIAG hooks.
 template <typename CodeT, int D>
 __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(D <= 16 ? 3 : 1))) void pvq_encode_walk_kernel(const float *__restrict__ grad,
                                                                      const float *__restrict__ cdag, int64_t M, int K,
@@ -390,12 +392,10 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(D <
                                                                      uint64_t seed, CodeT *__restrict__ codes,
                                                                      float *__restrict__ u, float *__restrict__ partials,
                                                                      double eps, PvqResidual rs) {
-    using S = PwShape<D>;
-    constexpr int NQ = S::NQ;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int NQ = PwShape<D>::NQ;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float *const s_cb = lds;
-    float *const s_v = lds + S::CB_FLOATS + wave * S::TILE_FLOATS;
+    const PwLds lds = pw_carve_lds<D>(wave);
+    float *const s_cb = lds.cb, *const s_v = lds.v;
     const bool force_slow = eps < 0.0;   // tests: every unsettled lane walks term by term
     eps = fabs(eps);
     pw_stage_codebook<D>(cdag, K, s_cb);
@@ -405,22 +405,18 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(D <
     float pre_n1[NQ];
     auto fetch_tile = [&](int64_t t) {
         const int64_t sv0 = t * 64;
+        const int left = M - sv0 < 64 ? (int)(M - sv0) : 64;
+        pw_fetch_rows<D>(pre, (uintptr_t)(grad + sv0 * D), left);
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
-            const int q = i * 64 + lane;
-            const int rr = q / NQ;
-            const int e0 = (q - rr * NQ) * 4;
-            const int64_t m = sv0 + rr;
-            pre[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            const int rr = (i * 64 + lane) / NQ;
             pre_c1[i] = 0;
             pre_n1[i] = 0.0f;
-            if (m < M) {
-                pre[i] = *reinterpret_cast<const f32x4 *>(grad + m * (int64_t)D + e0);
-                if (rs.codes1) {
-                    pre_c1[i] = rs.code1_bytes == 1 ? (int)static_cast<const uint8_t *>(rs.codes1)[m]
-                                                    : static_cast<const int32_t *>(rs.codes1)[m];
-                    pre_n1[i] = rs.norm1[m];
-                }
+            if (rs.codes1 && rr < left) {
+                const int64_t m = sv0 + rr;
+                pre_c1[i] = rs.code1_bytes == 1 ? (int)static_cast<const uint8_t *>(rs.codes1)[m]
+                                                : static_cast<const int32_t *>(rs.codes1)[m];
+                pre_n1[i] = rs.norm1[m];
             }
         }
     };
@@ -432,14 +428,8 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(D <
             const int rr = q / NQ;
             const int e0 = (q - rr * NQ) * 4;
             f32x4 val = pre[i];
-            if (rs.codes1 && sv0 + rr < M) {
-                const f32x4 c = *reinterpret_cast<const f32x4 *>(rs.cb1 + (int64_t)pre_c1[i] * D + e0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float dec = c[e] * pre_n1[i];   // stage 1's decoded element (product rounded)
-                    val[e] = val[e] - dec;
-                }
-            }
+            if (rs.codes1 && sv0 + rr < M)
+                pw_residual_quad(val, *reinterpret_cast<const f32x4 *>(rs.cb1 + (int64_t)pre_c1[i] * D + e0), pre_n1[i]);
             pw_stage_quad<D>(s_v, rr, e0, val);
         }
     };
@@ -453,14 +443,12 @@ __global__ __launch_bounds__(ENC_THREADS) __attribute__((amdgpu_waves_per_eu(D <
     if (t < ntiles) fetch_tile(t);
     for (; t < ntiles; t += nw) {
         const int64_t sv = t * 64 + lane;           // this lane's subvector
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // the previous tile's reads are done
-        __builtin_amdgcn_wave_barrier();
+        pw_wave_fence();   // the previous tile's reads are done
         if (!(PVQ_DIAG & 512)) {
             commit_tile(t);
             if (t + nw < ntiles) fetch_tile(t + nw);
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        pw_wave_fence();   // the tile is staged
         const bool mine = sv < M;
         int code;
         float val;

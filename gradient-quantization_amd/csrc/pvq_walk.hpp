@@ -1,9 +1,13 @@
-// The one-sweep + lane-local-walk encode of a 64-subvector tile of the ProbabilisticVectorCompressor, as device code that
-// both translation units include: pvq.hip (gq_pvq_encode, one tensor per launch; libgq_hsq.so) and pvq_batched.hip
-// (gq_pvq_encode_batched, every tensor of a model per launch; libgq_pvq.so).  One body, so the two give the same bits.
-// The scheme is described where it was written: pvq.hip, in front of pvq_encode_walk_kernel.
+// The ProbabilisticVectorCompressor's encode as device code, written once for its three users:
+//   pvq.hip          gq_pvq_encode: one tensor per launch, tiles one grid apart, partials in the workspace (libgq_hsq.so)
+//   pvq_batched.hip  gq_pvq_encode_batched: every tensor of a model per launch, tiles of the gradient (libgq_pvq.so)
+//   rq_batched.hip   gq_rq_encode2_batched: the same over  v - decode(stage 1)  (libgq_rq.so)
+// pw_encode_tile is the one-sweep + lane-local-walk encode of a 64-subvector tile (the scheme is described where it was
+// written: pvq.hip, in front of pvq_encode_walk_kernel): one body, so all three give the same bits.  pw_encode_run is the whole
+// kernel of the two multi-tensor launches -- a wave's RUN of consecutive tiles over the segment tables -- around a tile source
+// that each file defines; pvq.hip keeps a loop of its own and shares the LDS carve-up, the row fetch and stage 1's residual.
 #pragma once
-#include "hsq_encode_common.hpp"
+#include "hsq_pf_common.hpp"      // order_map; hsq_encode_common.hpp
 
 namespace gq {
 
@@ -302,6 +306,188 @@ __device__ __forceinline__ void pw_encode_tile(const float *s_cb, const float *s
     const float sg = (sel > 0.0f) ? 1.0f : ((sel < 0.0f) ? -1.0f : 0.0f);
     code_out = code;
     val_out = sg * l1;
+}
+
+// ---- what the kernels around the tile encode share -------------------------------------------------------------------------
+
+// the draws of the sampler and the level quantiser's stochastic rounding come from different streams of one seed: the
+// multi-tensor launches of both libraries salt theirs with this (tests/rq_contract.py and tests/test_gpu_pvq.py hold copies)
+constexpr uint64_t PW_SAMPLER_SALT = 0xA0761D6478BD642Full;
+
+// Pointers out of the segment table are cast to GLOBAL pointers (address space 1): as plain pointers they would be flat,
+// and the wait for a flat access sits behind the previous tile's stores (hsq_encode_pf.hip); members of a by-value argument
+// struct are flat pointers otherwise, too.  The tables themselves do not change while the kernel runs: read through the
+// constant address space they are scalar loads.
+typedef const f32x4 __attribute__((address_space(1))) *pw_gcv_ptr;
+typedef f32x4 __attribute__((address_space(1))) *pw_gv_ptr;
+typedef uint8_t __attribute__((address_space(1))) *pw_gcode_ptr;
+typedef float __attribute__((address_space(1))) *pw_gf_ptr;
+typedef const float __attribute__((address_space(1))) *pw_gcf_ptr;
+typedef unsigned __attribute__((address_space(1))) *pw_gu_ptr;
+typedef const int64_t __attribute__((address_space(4))) *pw_crec_ptr;
+typedef const int32_t __attribute__((address_space(4))) *pw_cseg_ptr;
+
+// the workgroup's dynamic LDS (PwShape<D>::LDS_BYTES): the staged codebook, then one tile per wave
+struct PwLds {
+    float *cb, *v;
+};
+template <int D>
+__device__ __forceinline__ PwLds pw_carve_lds(int wave) {
+    extern __shared__ __attribute__((aligned(16))) float pw_lds[];
+    return PwLds{pw_lds, pw_lds + PwShape<D>::CB_FLOATS + wave * PwShape<D>::TILE_FLOATS};
+}
+
+// the wave's ordering point between its reads of a staged tile and the stores of the next one (and back)
+__device__ __forceinline__ void pw_wave_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// The float4s of a tile's rows below `left` into pre[] (zeros above): float4 q = i * 64 + lane of the tile is row q / NQ,
+// elements 4 (q mod NQ) ..., 16 q bytes behind `base`, the tile's first float.
+template <int D>
+__device__ __forceinline__ void pw_fetch_rows(f32x4 (&pre)[PwShape<D>::NQ], uintptr_t base, int left) {
+    constexpr int NQ = PwShape<D>::NQ;
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        const int q = i * 64 + lane;
+        pre[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (q / NQ < left) pre[i] = *(pw_gcv_ptr)(base + (unsigned)q * 16u);
+    }
+}
+
+// one float4 of  v - codebook1[code1] * norm1 : gq_pvq_encode's stage1 form and the residual compressor's second stage
+__device__ __forceinline__ void pw_residual_quad(f32x4 &val, const f32x4 c, float n1) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float dec = c[e] * n1;   // stage 1's decoded element (product rounded)
+        val[e] = val[e] - dec;         // residuals -= decompressed (residual_compressor.py:22)
+    }
+}
+
+// What both multi-tensor launches are given: gq_hsq_batch's tables (tile_seg names the tensor of every 64-subvector tile,
+// seg_table its pointers, sizes and wire offsets), the sampler's codebook and draws, and where the results go.
+struct PwRunArgs {
+    const int64_t *seg_table;
+    const int32_t *tile_seg;
+    int64_t ntiles;
+    const float *cdag;
+    uint8_t *wire;
+    float *u_flat;
+    unsigned *seg_minmax;
+    const float *r_flat;
+    uint64_t seed;
+    double eps;
+    int K, random_mode;
+    int tiles_per_wave, waves_with_one_more;      // a wave's RUN of consecutive tiles: ntiles = waves * tiles_per_wave + waves_with_one_more
+};
+
+// What the walker reads of a tile; wave-uniform, in scalar registers.  A source's Tile derives from it.
+struct PwTile {
+    uintptr_t grad;         // the tile's first float
+    pw_gcode_ptr codes;     // where the tile's first code goes (the source sets it)
+    int64_t local0;         // the tile's first subvector within its tensor
+    int left;               // subvectors of the tensor from the tile's start on, capped at 64
+    int seg;
+};
+// seg, local0, left and grad of tile t from the tables -> the tensor's record (scalar loads)
+template <int D>
+__device__ __forceinline__ pw_crec_ptr pw_tile_common(const PwRunArgs &a, int64_t t, PwTile &ti) {
+    ti.seg = ((pw_cseg_ptr)(uintptr_t)a.tile_seg)[t];
+    const pw_crec_ptr rec = (pw_crec_ptr)(uintptr_t)(a.seg_table + 8 * (int64_t)ti.seg);
+    ti.local0 = (t - rec[2]) * 64;
+    const int64_t left = rec[1] - ti.local0;
+    ti.left = left < 64 ? (int)left : 64;
+    ti.grad = (uintptr_t)rec[0] + (uintptr_t)ti.local0 * (D * sizeof(float));
+    return rec;
+}
+
+// The body of a multi-tensor encode kernel (ENC_THREADS lanes, PwShape<D>::LDS_BYTES of dynamic LDS).  A wave owns a tile at
+// a time; per tile the encode is pw_encode_tile, so a tensor's codes and projections are gq_pvq_encode's bit for bit.  What
+// differs between the launches is the Source:
+//   struct Tile : PwTile { ... };                  the tile's record
+//   Tile tile(const PwRunArgs &, int64_t t)        ... from the tables (pw_tile_common + its own fields, `codes` among them)
+//   void fetch(const Tile &)                       the tile's global loads into the source's registers
+//   void commit(const Tile &, float *s_v)          ... into the wave's staged tile (pw_stage_quad), as the values to encode
+// A tile's record is loaded one tile ahead of the tile's fetch, the fetch one tile ahead of its encode.  When the tensor
+// changes, the wave's running (min, max) of u is folded into the tensor's order-mapped words, which the level launch of
+// libgq_hsq.so unmaps into (lb, ub).  Like the flat kernel's fminf / fmaxf fold, the words never see a NaN projection.
+template <int D, class Source>
+__device__ __forceinline__ void pw_encode_run(const PwRunArgs &a, Source &src) {
+    using Tile = typename Source::Tile;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const PwLds lds = pw_carve_lds<D>(wave);
+    const bool force_slow = a.eps < 0.0;   // tests: every unsettled lane walks term by term
+    const double eps = fabs(a.eps);
+    int random_mode = a.random_mode;
+    uint64_t seed = a.seed;
+    resolve_seed(random_mode, seed);       // GQ_RANDOM_DEVICE_COUNTER: { seed, step } words -> this launch's seed
+    seed ^= PW_SAMPLER_SALT;
+    pw_stage_codebook<D>(a.cdag, a.K, lds.cb);
+    __syncthreads();
+    const pw_gf_ptr u_flat = (pw_gf_ptr)(uintptr_t)a.u_flat;
+    const pw_gcf_ptr r_flat = (pw_gcf_ptr)(uintptr_t)a.r_flat;
+    const pw_gu_ptr seg_minmax = (pw_gu_ptr)(uintptr_t)a.seg_minmax;
+    float lmin = INFINITY, lmax = -INFINITY;
+    int cur_seg = -1;
+    // the wave's running (min, max) into its tensor's words.  Look before the atomic: the words only move towards the
+    // extremes, so a value that is already as good as ours -- however stale -- makes ours redundant (hsq_encode_pf.hip)
+    auto flush_minmax = [&]() {
+        const float lo = wave_min(lmin), hi = wave_max(lmax);
+        if (lane == 0 && cur_seg >= 0) {
+            const pw_gu_ptr mm = seg_minmax + 2 * cur_seg;
+            const unsigned mlo = order_map(lo), mhi = order_map(hi);
+            if (mlo < __hip_atomic_load(mm, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) (void)__hip_atomic_fetch_min(mm, mlo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (mhi > __hip_atomic_load(mm + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) (void)__hip_atomic_fetch_max(mm + 1, mhi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        lmin = INFINITY;
+        lmax = -INFINITY;
+    };
+    // A wave takes a RUN of consecutive tiles (the flat kernel strides by the grid): consecutive tiles mostly belong to one
+    // tensor, so the wave folds into a tensor's (min, max) words once per run instead of once per tile.  With the grid's
+    // stride every wave changed tensor at nearly every tile of a list of mid-sized tensors, and the ~23,000 look-ups and
+    // atomics of a ResNet-50 step on a handful of cache lines serialised in L2: 76 equal tensors took 344 us against 144 us for
+    // the same elements as one tensor (profiles/pvq_encode_grid_stride.jsonl; now 162 us: profiles/pvq_step_time.jsonl).  Same tiles per wave either way; same results.
+    const int wid = (int)blockIdx.x * ENC_WAVES + wave;
+    int64_t t = (int64_t)wid * a.tiles_per_wave + (wid < a.waves_with_one_more ? wid : a.waves_with_one_more);
+    const int64_t t_end = t + a.tiles_per_wave + (wid < a.waves_with_one_more ? 1 : 0);
+    Tile cur = {}, nxt = {};
+    if (t < t_end) {
+        cur = src.tile(a, t);
+        src.fetch(cur);
+    }
+    for (; t < t_end; ++t) {
+        const bool more = t + 1 < t_end;
+        if (more) nxt = src.tile(a, t + 1);
+        pw_wave_fence();   // the previous tile's reads are done
+        src.commit(cur, lds.v);
+        if (more) src.fetch(nxt);
+        pw_wave_fence();   // the tile is staged
+        if (cur.seg != cur_seg) {      // wave-uniform
+            flush_minmax();
+            cur_seg = cur.seg;
+        }
+        const bool mine = lane < cur.left;
+        const uint64_t idx = (uint64_t)t * 64 + (uint64_t)lane;      // the subvector's slot in the padded space (u_flat, r_flat)
+        int code = 0;
+        float val = 0.0f;
+        pw_encode_tile<D>(lds.cb, lds.v, a.K, mine,
+                          [&](float l1) {
+                              if (!mine) return 0.0f;
+                              if (random_mode == GQ_RANDOM_GIVEN) return r_flat[idx];
+                              return uniform01(random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, l1, l1) : seed, idx);
+                          },
+                          eps, force_slow, code, val);
+        if (mine) {
+            cur.codes[lane] = (uint8_t)code;
+            u_flat[idx] = val;
+            lmin = fminf(lmin, val);
+            lmax = fmaxf(lmax, val);
+        }
+        cur = nxt;
+    }
+    flush_minmax();
 }
 
 }  // namespace gq

@@ -47,6 +47,8 @@ int gq_pvq_batched_serves(int d, int K, int code_bytes);
  *   GQ_RANDOM_DEVICE_COUNTER  `seed` is the address of device words { seed, step }: what gq_hsq_levels_batched takes
  *   GQ_RANDOM_DEVICE_KEYED    as DEVICE, the stream of a subvector keyed by the bits of its l1 as well
  * In the device modes the seed is salted, so that the level launch, given the SAME seed argument, draws from another stream.
+ * A GQ_RANDOM_DEVICE_COUNTER address that is null or not 8-byte aligned is refused: GQ_ERR_INVALID_ARG, nothing is launched
+ * (as gq_rq_encode2_batched does; the words are read with 64-bit loads).
  * ef_scale: NaN = no error feedback; otherwise every tile of a row with an error buffer (seg_table[seg][7] != 0) is read as
  * v = grad + ef_scale * error (product rounded, then the sum: ps_quantizer.py:35), v is stored back over grad and v is
  * encoded; gq_hsq_levels_batched(write_error = 1) then leaves error = v - decoded.

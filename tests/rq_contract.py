@@ -13,7 +13,7 @@ import oracle
 
 F = np.float32
 M32, M64 = 0xFFFFFFFF, (1 << 64) - 1
-RQ_CODE_SALT = 0xA0761D6478BD642F        # csrc/rq_batched.hip
+RQ_CODE_SALT = 0xA0761D6478BD642F        # PW_SAMPLER_SALT of csrc/pvq_walk.hpp
 RQ_LEVEL2_SALT = 0xE7037ED1A0B428DB
 GQ_ODD_DIV_MAX = 4097                    # csrc/gq_common.hpp
 MEAN, PLAIN, ERROR = 0, 1, 2             # GQ_RQ_* of include/gq_rq.h

@@ -79,7 +79,12 @@ def _tensors(Ms, d, seed, dev, special=True):
 RAGGED = [1, 63, 64, 65, 150_000, 7, 128, 1000]      # 150,000 subvectors of 16 floats = 2.4 M elements between small tensors
 
 
-def _check_against_flat(Ms, d, K, seed, n_bit=6):
+def _check_against_flat(Ms, d, K, seed, n_bit=6, ef_scale=None):
+    """One multi-tensor encode + level launch over tensors of Ms subvectors against the flat kernel (gq_pvq_encode) and the
+    flat level launch per tensor, given the same draws: codes, u, (lb, ub), levels and the canaries round the wire sections.
+    ef_scale: through gq_pvq_encode_batched's error-feedback form, every third tensor without an error buffer; the flat
+    kernel is fed g + e * s as two separately rounded torch operations, which is also what the launch must leave over the
+    gradients that have an error buffer (the others stay as they are)."""
     from gq_amd import native
     dev = torch.device("cuda:0")
     grp, codecs, offsets, wire = _group(Ms, d, K, dev, n_bit=n_bit)
@@ -91,7 +96,21 @@ def _check_against_flat(Ms, d, K, seed, n_bit=6):
     for i, M in enumerate(Ms):
         draw_off[i] = n
         n += 2 * M
-    assert grp.encode([t.clone() for t in ts], wire[0], 0, 0, draws=(r_all, draw_off))
+    if ef_scale is None:
+        assert grp.encode([t.clone() for t in ts], wire[0], 0, 0, draws=(r_all, draw_off))
+    else:
+        s_dev = torch.tensor(ef_scale, dtype=torch.float32, device=dev)
+        nothing = torch.empty(0, dtype=torch.float32, device=dev)
+        assert nothing.data_ptr() == 0
+        errs = [nothing if i % 3 == 2 else e for i, e in enumerate(_tensors(Ms, d, seed + 1, dev, special=False))]
+        before = [t.clone() for t in ts]
+        grads = [t.clone() for t in ts]
+        ts = [g if e is nothing else g + e * s_dev for g, e in zip(before, errs)]      # the product rounded, then the sum
+        assert grp._upload(grads, 0, grp.align, errs)
+        grp._batch.encode(wire[0], ef_scale, native.RANDOM_GIVEN, 0, grp._given_draws((r_all, draw_off), 0))
+        grp._batch.levels(wire[0], native.RANDOM_GIVEN, 0, grp._given_draws((r_all, draw_off), 1))
+        for i, (g, v, g0, e) in enumerate(zip(grads, ts, before, errs)):
+            assert torch.equal(g.view(torch.int32), (g0 if e is nothing else v).view(torch.int32)), (i, Ms[i], "the gradient afterwards")
     torch.cuda.synchronize()
     assert _canaries_intact(wire, codecs, offsets)
     for i, (cd, t) in enumerate(zip(codecs, ts)):
@@ -118,6 +137,59 @@ def _check_against_flat(Ms, d, K, seed, n_bit=6):
 def test_multi_tensor_encode_equals_the_flat_kernel(d, K):
     Ms = RAGGED if d == 16 else [1, 63, 64, 65, 5000, 7, 128]
     _check_against_flat(Ms, d, K, 11 + d + K)
+
+
+def _run_list(d, which):
+    """tests/rq_contract.py's multi-tile list (five large tensors, 300 small ones of 1 ... 200 subvectors between them) sized
+    from the device's CU count: more tiles than twice the waves the launch can have resident, so every wave's run holds two
+    tiles or more and runs cross tensors; the second total is no multiple of the waves, so some waves run one tile more."""
+    import rq_contract as rc
+    from gq_amd import native
+    cus = native.device_info(0)[0]
+    total = rc.multi_tile_totals(d, cus)[which]
+    Ms = rc.multi_tile_Ms(d, cus, total)
+    assert sum((M + 63) // 64 for M in Ms) == total > rc.encode_wave_bound(d, cus)
+    assert which == 0 or (total + 1) % (4 * cus) == 0
+    return Ms
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["above_the_bound", "one_short_of_twice_the_bound"])
+@pytest.mark.parametrize("d,K", [(8, 64), (16, 256), (32, 64)])
+def test_encode_runs_that_cross_tensors(d, K, which):
+    """The run walker under gq_pvq_encode_batched: the wave's run of tiles, the prefetch across a tile's encode, the fold of
+    (min, max) where the tensor changes inside a run, waves_with_one_more -- every tensor against the flat kernel."""
+    _check_against_flat(_run_list(d, which), d, K, 200 + d + which)
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["above_the_bound", "one_short_of_twice_the_bound"])
+@pytest.mark.parametrize("d,K", [(8, 64), (16, 256), (32, 64)])
+def test_encode_runs_with_error_feedback(d, K, which):
+    """The same lists through the error-feedback form (d = 16: the instantiation built for two waves per SIMD), every third
+    tensor without an error buffer: v = g + e * s is encoded and left over the gradient, the other gradients are untouched."""
+    _check_against_flat(_run_list(d, which), d, K, 300 + d + which, ef_scale=0.3)
+
+
+def test_misaligned_counter_address_is_refused():
+    """GQ_RANDOM_DEVICE_COUNTER with an address that is not 8-byte aligned: GQ_ERR_INVALID_ARG, and nothing is launched --
+    wire, u_flat and seg_minmax stay as they were."""
+    from gq_amd import native
+    dev = torch.device("cuda:0")
+    Ms = [65, 700, 7]
+    grp, codecs, offsets, wire = _group(Ms, 16, 256, dev, rng="device")
+    assert grp._upload(_tensors(Ms, 16, 3, dev), 0, grp.align)
+    grp.u_flat.fill_(7.0)
+    words = torch.tensor([0x1234ABCD5678EF01, 5, 0], dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+    minmax = grp._dev[grp._table_words:grp._dense_at]
+    was = (wire.clone(), grp.u_flat.clone(), minmax.clone())
+    assert words.data_ptr() % 8 == 0
+    with pytest.raises(native.GQNativeError):
+        grp._batch.encode(wire[0], None, native.RANDOM_DEVICE_COUNTER, words.data_ptr() + 4)
+    torch.cuda.synchronize()
+    assert torch.equal(wire, was[0]) and torch.equal(grp.u_flat.view(torch.int32), was[1].view(torch.int32)) and torch.equal(minmax, was[2])
+    grp._batch.encode(wire[0], None, native.RANDOM_DEVICE_COUNTER, words.data_ptr())      # the same rig is served when asked properly
+    torch.cuda.synchronize()
+    assert not torch.equal(wire, was[0]) and _canaries_intact(wire, codecs, offsets)
 
 
 @pytest.mark.parametrize("eps", ["1e-3", "-1e-3"], ids=["wave_walk", "term_by_term"])
@@ -269,7 +341,7 @@ def _uniform01_host(seed, idx):
     return out
 
 
-PVQ_STREAM_SALT = 0xA0761D6478BD642F      # csrc/pvq_batched.hip
+PVQ_STREAM_SALT = 0xA0761D6478BD642F      # PW_SAMPLER_SALT of csrc/pvq_walk.hpp
 
 
 def _resolved_counter_seed(seed, step):
