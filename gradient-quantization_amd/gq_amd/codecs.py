@@ -11,7 +11,7 @@ device memory, through gq_amd.native).
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
     MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
     MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP8 code per element
-    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX
+    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -711,6 +711,16 @@ class MXCodec(_SparseCodec):
 
     def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None):
         _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out)
+
+
+class MXRCodec(MXCodec):
+    """MXCompressor with mx_rotate = 'hadamard' on libgq_mxr.so (include/gq_mxr.h): MXCodec's wire, bytes and draw rules over the
+    tensor rotated in blocks of 256 by H * diag(signs) / 16; every decode ends with the inverse rotation, so the wire no longer
+    carries the decoded tensor itself.  Every call is a one-tensor BatchedMXR."""
+
+    def __init__(self, compressor, numel, shape):
+        MXCodec.__init__(self, compressor, numel, shape)
+        self.signs = tuple(int(w) for w in compressor.rotate_signs)
 
 
 _DATA_PTR = torch.Tensor.data_ptr
@@ -1866,6 +1876,33 @@ class BatchedMX(_ItemGroup):
 MXCodec.GROUP = BatchedMX
 
 
+class BatchedMXR(BatchedMX):
+    """BatchedMX over libgq_mxr.so: all MXCompressor tensors of one format, rounding and set of sign words in ONE
+    gq_mxr_compress_batched launch and ONE gq_mxr_decode_sum_batched launch (include/gq_mxr.h).  The layout, the draws and the
+    graph rules are BatchedMX's; `out` and the residual of error feedback are inverse-rotated, and the decode-mean rotates the
+    mean back once."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is MXRCodec
+
+    @staticmethod
+    def group_key(codec):
+        return BatchedMX.group_key(codec) + tuple(codec.signs)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        nseg, item = self._layout(codecs, offsets, idxs, device, slots, user_bytes, dense)
+        c0 = self.codecs[0]
+        self.format, self.random, self.signs = c0.format, c0.random, c0.signs
+        self.counter = self.random and c0._rng == "device"      # the quantizer gives such a group its { seed, step } pairs
+        self.reference_draws = self.random and c0._rng == "reference"
+        self._r = None
+        self._batch = native.MXRBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.format, self.signs)
+
+
+MXRCodec.GROUP = BatchedMXR
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -1882,7 +1919,7 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, MaureySparsification):
         return MaureyCodec(compressor, numel, shape)
     if isinstance(compressor, MXCompressor):
-        return MXCodec(compressor, numel, shape)
+        return (MXRCodec if getattr(compressor, "rotate", None) else MXCodec)(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

@@ -565,7 +565,25 @@ class MXCompressor(object):
     under stochastic rounding, relative precision inside a block (include/gq_mx.h defines it to the bit).  args.mx_format:
     'fp4' (the default) or 'fp8'; args.random: stochastic rounding (otherwise to nearest, ties to the even code); gq_rng: where
     the draws come from (MXCodec).  compress returns the decoded tensor -- the wire carries it exactly -- and decompress is the
-    identity, as for SignSGDCompressor.  HIP kernels only (libgq_mx.so): a float32 tensor on the device."""
+    identity, as for SignSGDCompressor.  HIP kernels only (libgq_mx.so): a float32 tensor on the device.
+    args.mx_rotate: None / 'none' (the default) or 'hadamard' -- a randomized 256-point Hadamard rotation in front of the
+    quantiser and its inverse behind the decode (include/gq_mxr.h, libgq_mxr.so): one large entry no longer sets the grid of its
+    31 neighbours, at the same bits on the same wire.  args.mx_rotate_seed (default 1) gives the four sign words, outputs
+    0 ... 3 of splitmix64 started at the seed, computed here in Python integers: every rank with the same arguments has the same
+    signs.  With rotation compress returns the inverse-rotated dense decode."""
+
+    @staticmethod
+    def sign_words(seed):
+        """Outputs 0 ... 3 of splitmix64 started at `seed` (include/gq_mxr.h writes the recurrence out)."""
+        M = (1 << 64) - 1
+        state, words = int(seed) & M, []
+        for _ in range(4):
+            state = (state + 0x9E3779B97F4A7C15) & M
+            z = state
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+            words.append(z ^ (z >> 31))
+        return tuple(words)
 
     def __init__(self, size, shape, args):
         fmt = getattr(args, "mx_format", None) or "fp4"
@@ -575,9 +593,16 @@ class MXCompressor(object):
         self.random = bool(getattr(args, "random", True))
         self.size, self.shape = size, shape
         self._rng = _rng_mode(args)
+        rotate = getattr(args, "mx_rotate", None)
+        if rotate not in (None, "none", "hadamard"):
+            raise ValueError("mx_rotate must be 'none' or 'hadamard', got %r" % (rotate,))
+        self.rotate = "hadamard" if rotate == "hadamard" else None
+        seed = getattr(args, "mx_rotate_seed", None)
+        self.rotate_seed = 1 if seed is None else int(seed)
+        self.rotate_signs = self.sign_words(self.rotate_seed) if self.rotate else None
 
     def compress(self, vec):
-        from .codecs import MXCodec      # (codecs imports this module)
+        from .codecs import MXCodec, MXRCodec      # (codecs imports this module)
         if vec.device.type != "cuda" or vec.dtype != torch.float32:
             raise TypeError("MXCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), got %s on %s"
                             % (vec.dtype, vec.device))
@@ -587,7 +612,7 @@ class MXCompressor(object):
         codecs = self.__dict__.setdefault("_codecs", {})
         codec = codecs.get(n)
         if codec is None:
-            codec = codecs[n] = MXCodec(self, n, (n,))
+            codec = codecs[n] = (MXRCodec if self.rotate else MXCodec)(self, n, (n,))
         return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
 
     def decompress(self, signature):

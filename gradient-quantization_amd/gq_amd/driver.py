@@ -172,6 +172,11 @@ def build_parser():
                         'with momentum M in the quantizer; the optimizer then runs with momentum 0 (weight decay stays with it)')
     p.add_argument('--mx-format', dest='mx_format', type=str, default='fp4', choices=['fp4', 'fp8'],
                    help='--quantizer mx: the element format under the per-block scale byte (4.25 or 8.25 bits per element)')
+    p.add_argument('--mx-rotate', dest='mx_rotate', type=str, default='none', choices=['none', 'hadamard'],
+                   help='--quantizer mx: a randomized 256-point Hadamard rotation in front of the quantiser and its inverse behind the '
+                        'decode (lower error on heavy-tailed gradients, the same bits per element; not in ring mode)')
+    p.add_argument('--mx-rotate-seed', dest='mx_rotate_seed', type=int, default=1,
+                   help='--mx-rotate hadamard: the seed of the four sign words (every rank must use the same)')
     p.add_argument('--seed', type=int, default=1)
     p.add_argument('--train-size', type=int, default=4096, help='synthetic samples per epoch')
     p.add_argument('--log-interval', type=int, default=8, help='iterations between JSON log lines')

@@ -1007,6 +1007,48 @@ class MXBatch(_ItemBatch):
         _check(rc, "gq_mx_compress_batched", MX_LIBRARY)
 
 
+# ---- the same behind a randomized Hadamard rotation: libgq_mxr.so (include/gq_mxr.h) ----------------------------------------------
+MXR_ABI_VERSION = 1
+MXR_EXPORTS = ["gq_mxr_abi_version", "gq_mxr_last_error", "gq_mxr_compress_batched", "gq_mxr_decode_sum_batched"]
+MXR_BLOCK = 256             # GQ_MXR_BLOCK: elements of a rotation block
+
+MXR_LIBRARY = Library("libgq_mxr.so", "GQ_MXR_LIB_PATH", "gq_mxr_", MXR_ABI_VERSION, MXR_EXPORTS)
+MXR_LIB_PATH = MXR_LIBRARY.path
+
+
+def mxr_lib():
+    return MXR_LIBRARY.handle or _load(MXR_LIBRARY)
+
+
+class _MXRBatchStruct(ctypes.Structure):      # gq_mxr_batch (include/gq_mxr.h): gq_mx_batch's fields, then the sign words
+    _fields_ = _MXBatchStruct._fields_ + [("signs", ctypes.c_uint64 * 4)]
+
+
+class MXRBatch(_ItemBatch):
+    """The two launches of libgq_mxr.so: MXBatch's calls over tensors rotated in blocks of 256 by H * diag(signs) / 16.
+    signs: the four 64-bit sign words (element j of a rotation block owns bit j & 63 of word j >> 6)."""
+
+    LIBRARY, STRUCT = MXR_LIBRARY, _MXRBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4, signs=(0, 0, 0, 0)):
+        signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
+        assert len(signs) == 4
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt), signs=(ctypes.c_uint64 * 4)(*signs))
+        self.signs = signs
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.signs)
+
+    def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
+        """MXBatch.compress; out and the residual of error feedback are inverse-rotated (include/gq_mxr.h)."""
+        rc = self.L.gq_mxr_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
+                                            _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
+                                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_mxr_compress_batched", MXR_LIBRARY)
+
+
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
 KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]
