@@ -139,9 +139,12 @@ __global__ __launch_bounds__(THREADS) void mx_compress_kernel(const int64_t *__r
                 }
             }
         }
-        // the lane's codes: element 2i in the low nibble (FP4) / element i in byte i (FP8), little-endian words
+        // the lane's codes: element 2i in the low nibble (FP4) / element i in byte i (FP8), little-endian words; FP6: the quad's
+        // six dwords (store_codes6, + the pad behind an odd number of blocks)
         const int64_t blk = e0 / GQ_MX_BLOCK;
-        if (blk < nb) {
+        if (F::bits == 6) {
+            store_codes6(codes, blk, nb, c);
+        } else if (blk < nb) {
             if (FMT == GQ_MX_FP4) {
                 uint32_t word = 0;
 #pragma unroll
@@ -166,7 +169,7 @@ __global__ __launch_bounds__(THREADS) void mx_decode_kernel(const int64_t *__res
                                                             const uint8_t *__restrict__ gathered, int64_t stride, int R,
                                                             float *__restrict__ out, int plain) {
     using F = Fmt<FMT>;
-    constexpr int CODE_BYTES = PER_LANE * F::bits / 8;      // a lane's code bytes: 4 (FP4) or 8 (FP8)
+    constexpr int CODE_BYTES = PER_LANE * F::bits / 8;      // a lane's code bytes: 4 (FP4), 6 (FP6) or 8 (FP8)
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
@@ -178,6 +181,8 @@ __global__ __launch_bounds__(THREADS) void mx_decode_kernel(const int64_t *__res
     const float fR = (float)R;
     // (wire offsets are multiples of 16: the payloads' own alignment decides)
     const bool words = ((reinterpret_cast<uintptr_t>(gathered) | (uintptr_t)(R > 1 ? stride : 0)) & 7u) == 0;
+    // (FP6: a pair of lanes owns 12 bytes at a multiple of 12 -- dword loads wherever the payloads are 4-byte aligned)
+    const bool words6 = ((reinterpret_cast<uintptr_t>(gathered) | (uintptr_t)(R > 1 ? stride : 0)) & 3u) == 0;
     for (int s = 0; s < STEPS; ++s) {
         const int64_t e0 = base + (int64_t)s * STEP + (int64_t)threadIdx.x * PER_LANE;
         if (e0 >= n) break;
@@ -189,7 +194,10 @@ __global__ __launch_bounds__(THREADS) void mx_decode_kernel(const int64_t *__res
             const uint32_t sb = p[e0 / GQ_MX_BLOCK];
             const uint8_t *cp = p + nb_pad + (e0 / PER_LANE) * CODE_BYTES;
             uint32_t lo = 0, hi = 0;
-            if (words) {
+            uint64_t six = 0;
+            if (F::bits == 6) {
+                six = load_codes6(cp, (e0 / PER_LANE) & 1, words6);
+            } else if (words) {
                 if (FMT == GQ_MX_FP4) {
                     lo = *reinterpret_cast<const uint32_t *>(cp);
                 } else {
@@ -207,7 +215,9 @@ __global__ __launch_bounds__(THREADS) void mx_decode_kernel(const int64_t *__res
             const int e = (int)sb - 127;
 #pragma unroll
             for (int k = 0; k < PER_LANE; ++k) {
-                const uint32_t code = FMT == GQ_MX_FP4 ? (lo >> (4 * k)) & 15u : ((k < 4 ? lo : hi) >> (8 * (k & 3))) & 255u;
+                const uint32_t code = F::bits == 6     ? (uint32_t)(six >> (6 * k)) & 63u
+                                      : FMT == GQ_MX_FP4 ? (lo >> (4 * k)) & 15u
+                                                         : ((k < 4 ? lo : hi) >> (8 * (k & 3))) & 255u;
                 const float d = sb == 0xFFu ? __uint_as_float(QNAN) : decode_value<F>(code, e);
                 acc[k] = direct ? d : acc[k] + d;
             }
@@ -226,7 +236,8 @@ __global__ __launch_bounds__(THREADS) void mx_decode_kernel(const int64_t *__res
 
 static int check_batch(const gq_mx_batch *b, const char *what, bool compress) {
     if (!b || b->struct_bytes != sizeof(gq_mx_batch)) return fail(GQ_ERR_INVALID_ARG, "%s: descriptor missing or of another size", what);
-    if (b->format != GQ_MX_FP4 && b->format != GQ_MX_FP8) return fail(GQ_ERR_INVALID_ARG, "%s: format %d (GQ_MX_FP4 or GQ_MX_FP8)", what, b->format);
+    if (b->format != GQ_MX_FP4 && b->format != GQ_MX_FP8 && b->format != GQ_MX_FP6_E2M3 && b->format != GQ_MX_FP6_E3M2)
+        return fail(GQ_ERR_INVALID_ARG, "%s: format %d (GQ_MX_FP4, GQ_MX_FP8, GQ_MX_FP6_E2M3 or GQ_MX_FP6_E3M2)", what, b->format);
     if (b->nseg < 1 || b->nitems < 1 || b->nitems > 0x7fffffff || b->ndense < 0)
         return fail(GQ_ERR_INVALID_ARG, "%s: bad sizes (nseg %d, nitems %lld, ndense %d)", what, b->nseg, (long long)b->nitems, b->ndense);
     if (!b->seg_table || !b->item_seg) return fail(GQ_ERR_INVALID_ARG, "%s: null table", what);
@@ -281,8 +292,12 @@ GQX_API int gq_mx_compress_batched(const gq_mx_batch *b, uint8_t *wire, int rand
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (b->format == GQ_MX_FP4)
         launch_compress<GQ_MX_FP4>(b, wire, random_mode, r, seed, ef_scale, out, st);
-    else
+    else if (b->format == GQ_MX_FP8)
         launch_compress<GQ_MX_FP8>(b, wire, random_mode, r, seed, ef_scale, out, st);
+    else if (b->format == GQ_MX_FP6_E2M3)
+        launch_compress<GQ_MX_FP6_E2M3>(b, wire, random_mode, r, seed, ef_scale, out, st);
+    else
+        launch_compress<GQ_MX_FP6_E3M2>(b, wire, random_mode, r, seed, ef_scale, out, st);
     GQL_CHECK_LAUNCH("gq_mx_compress_batched");
     return GQ_OK;
 }
@@ -301,8 +316,14 @@ GQX_API int gq_mx_decode_sum_batched(const gq_mx_batch *b, const uint8_t *gather
     if (b->format == GQ_MX_FP4)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(mx_decode_kernel<GQ_MX_FP4>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
                            user_stride_bytes, R, out, plain ? 1 : 0);
-    else
+    else if (b->format == GQ_MX_FP8)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(mx_decode_kernel<GQ_MX_FP8>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0);
+    else if (b->format == GQ_MX_FP6_E2M3)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mx_decode_kernel<GQ_MX_FP6_E2M3>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mx_decode_kernel<GQ_MX_FP6_E3M2>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
                            user_stride_bytes, R, out, plain ? 1 : 0);
     GQL_CHECK_LAUNCH("gq_mx_decode_sum_batched");
     return GQ_OK;

@@ -24,6 +24,16 @@ struct Fmt<GQ_MX_FP8> {
     static constexpr int bits = 8, mb = 3, bias = 7, emax = 8;
     static constexpr uint32_t mthr = 0x600000u;
 };
+template <>
+struct Fmt<GQ_MX_FP6_E2M3> {
+    static constexpr int bits = 6, mb = 3, bias = 1, emax = 2;
+    static constexpr uint32_t mthr = 0x700000u;
+};
+template <>
+struct Fmt<GQ_MX_FP6_E3M2> {
+    static constexpr int bits = 6, mb = 2, bias = 3, emax = 4;
+    static constexpr uint32_t mthr = 0x600000u;
+};
 
 __host__ __device__ constexpr int64_t up16(int64_t x) { return (x + 15) / 16 * 16; }
 
@@ -69,6 +79,47 @@ __device__ __forceinline__ float decode_value(uint32_t code, int e) {
     const uint32_t sig = ce ? (cm | (1u << F::mb)) : cm;
     const float m = ldexpf((float)sig, (int)max(ce, 1u) - F::bias - F::mb + e);
     return __uint_as_float(__float_as_uint(m) | ((code >> (F::bits - 1)) << 31));
+}
+
+// ---- the 6-bit wire: a block is 24 bytes at 24 * blk, element i in bits 6i .. 6i+5 of the little-endian bit string ----------------
+// A lane's eight codes are 48 bits at byte 6 * (lane & 3) of its block; lo = bits 0 .. 31, hi = bits 32 .. 47.
+
+// The quad's 24 bytes as three 8-byte stores (24 * blk is 8-byte aligned: the wire is 16-byte aligned, and so are a section and
+// its scale bytes).  The block is the 192-bit string v0 | v1 << 48 | v2 << 96 | v3 << 144 of the lanes' 48-bit values; lane
+// q = 0, 1, 2 stores its bits 64 q .. 64 q + 63 = (v_q >> 16 q) | (v_{q+1} << (48 - 16 q)): the next lane's lo and hi come by two
+// DPP moves, and the two 64-bit shifts by the lane's own q need no select and no branch.  Lane 3 stores nothing of the block --
+// it writes the 8 zero bytes that pad an odd number of blocks to 16, behind the last one.
+// EVERY lane of the wave calls this (the DPP moves sit outside the bounds test); c[k] < 64.
+__device__ __forceinline__ void store_codes6(uint8_t *codes, int64_t blk, int64_t nb, const uint32_t (&c)[8]) {
+    const uint32_t lo = c[0] | (c[1] << 6) | (c[2] << 12) | (c[3] << 18) | (c[4] << 24) | (c[5] << 30);
+    const uint32_t hi = (c[5] >> 2) | (c[6] << 4) | (c[7] << 10);
+    const uint32_t nlo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)lo, 0xF9, 0xF, 0xF, true);      // quad_perm [1, 2, 3, 3]
+    const uint32_t nhi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hi, 0xF9, 0xF, 0xF, true);
+    const uint32_t q = threadIdx.x & 3u;
+    const uint64_t v = ((uint64_t)hi << 32) | lo, nv = ((uint64_t)nhi << 32) | nlo;
+    const uint64_t d = (v >> (16 * q)) | (nv << (48 - 16 * q));      // (q = 3: not stored)
+    if (blk < nb) {
+        if (q < 3)
+            *reinterpret_cast<uint2 *>(codes + 24 * blk + 8 * q) = make_uint2((uint32_t)d, (uint32_t)(d >> 32));
+        else if (blk == nb - 1 && (nb & 1))
+            *reinterpret_cast<uint2 *>(codes + 24 * nb) = make_uint2(0u, 0u);
+    }
+}
+
+// A lane's 48 bits from cp = the payload's codes + 6 * (e0 / 8).  words (the payload 4-byte aligned): a pair of lanes owns 12
+// bytes = three dwords at a multiple of 12; the even lane loads dwords 0 and 1, the odd lane dwords 1 and 2 -- both inside the
+// pair, so inside the section, and no lane waits for another (gfx950 takes the pair of dwords as one 8-byte load at a 4-byte
+// aligned address; the compiler emits that).  Otherwise its own six bytes (emitted as a dword and a 16-bit load of them).
+__device__ __forceinline__ uint64_t load_codes6(const uint8_t *cp, bool odd, bool words) {
+    if (words) {
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(cp - (odd ? 2 : 0));
+        const uint32_t a = p[0], b = p[1];
+        return odd ? ((uint64_t)b << 16) | (a >> 16) : ((uint64_t)(b & 0xffffu) << 32) | a;
+    }
+    uint64_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) v |= (uint64_t)cp[k] << (8 * k);
+    return v;
 }
 
 }  // namespace gqx

@@ -10,7 +10,7 @@ device memory, through gq_amd.native).
     TopKCodec                  TopKSparsificationCompressor: k ascending uint32 indices, then their k f32 values
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
     MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
-    MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP8 code per element
+    MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP6 / FP8 code per element
     BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
@@ -669,15 +669,17 @@ class MaureyCodec(_SparseCodec):
 
 def mx_section_bytes(numel, fmt):
     """Bytes of one tensor's section of the microscaling wire (include/gq_mx.h): ceil(numel / 32) scale bytes, 16-byte aligned,
-    then 16 (fp4) or 32 (fp8) code bytes per block.  fmt: 'fp4' / 'fp8' or native.MX_FP4 / MX_FP8."""
+    then 16 (fp4), 24 (fp6_e2m3 / fp6_e3m2) or 32 (fp8) code bytes per block, zero bytes up to a multiple of 16 (fp6 with an odd
+    number of blocks: 8).  fmt: a name of native.MX_FORMATS or its id."""
     fmt = native.MX_FORMATS.get(fmt, fmt)
     nb = -(-numel // native.MX_BLOCK)
-    return _up(nb) + nb * native.MX_BLOCK * native.MX_CODE_BITS[fmt] // 8
+    return _up(nb) + _up(nb * native.MX_BLOCK * native.MX_CODE_BITS[fmt] // 8)
 
 
 class MXCodec(_SparseCodec):
     """MXCompressor on the HIP kernels (libgq_mx.so).  Wire per tensor: the blocks' scale bytes (E8M0, padded to 16 bytes), then
-    one FP4 code per element, element 2i in the low nibble, or one FP8 byte -- mx_section_bytes.  The wire carries the decoded
+    one FP4 code per element, element 2i in the low nibble, one FP8 byte, or one FP6 code (element i in bits 6i .. 6i+5 of its
+    block's 24 bytes) -- mx_section_bytes.  The wire carries the decoded
     tensor exactly (-0, and NaN for a block that held an infinity or a NaN), so ring mode ships it as it is.  Every call is a
     one-tensor BatchedMX; roundtrip / encode_decode_into return the compress launch's own dense decode.
     The draws (compressor.random; otherwise the rounding is to nearest-even and there are none), by the compressor's gq_rng:

@@ -561,9 +561,9 @@ class MaureySparsification(object):
 
 class MXCompressor(object):
     """Block-scaled small floats (OCP Microscaling; no counterpart in the reference's catalogue): 32 consecutive elements share a
-    power-of-two scale byte, every element is an FP4 (E2M1) or FP8 (E4M3) value -- 4.25 or 8.25 bits per element, unbiased
-    under stochastic rounding, relative precision inside a block (include/gq_mx.h defines it to the bit).  args.mx_format:
-    'fp4' (the default) or 'fp8'; args.random: stochastic rounding (otherwise to nearest, ties to the even code); gq_rng: where
+    power-of-two scale byte, every element is an FP4 (E2M1), FP6 (E2M3 or E3M2) or FP8 (E4M3) value -- 4.25, 6.25 or 8.25 bits
+    per element, unbiased under stochastic rounding, relative precision inside a block (include/gq_mx.h defines it to the bit).
+    args.mx_format: 'fp4' (the default), 'fp6_e2m3', 'fp6_e3m2' or 'fp8' ('fp6' alone names no format); args.random: stochastic rounding (otherwise to nearest, ties to the even code); gq_rng: where
     the draws come from (MXCodec).  compress returns the decoded tensor -- the wire carries it exactly -- and decompress is the
     identity, as for SignSGDCompressor.  HIP kernels only (libgq_mx.so): a float32 tensor on the device.
     args.mx_rotate: None / 'none' (the default) or 'hadamard' -- a randomized 256-point Hadamard rotation in front of the
@@ -571,6 +571,8 @@ class MXCompressor(object):
     31 neighbours, at the same bits on the same wire.  args.mx_rotate_seed (default 1) gives the four sign words, outputs
     0 ... 3 of splitmix64 started at the seed, computed here in Python integers: every rank with the same arguments has the same
     signs.  With rotation compress returns the inverse-rotated dense decode."""
+
+    FORMATS = ("fp4", "fp6_e2m3", "fp6_e3m2", "fp8")
 
     @staticmethod
     def sign_words(seed):
@@ -587,8 +589,8 @@ class MXCompressor(object):
 
     def __init__(self, size, shape, args):
         fmt = getattr(args, "mx_format", None) or "fp4"
-        if fmt not in ("fp4", "fp8"):
-            raise ValueError("mx_format must be 'fp4' or 'fp8', got %r" % (fmt,))
+        if fmt not in self.FORMATS:
+            raise ValueError("mx_format must be one of %s, got %r" % (", ".join(repr(f) for f in self.FORMATS), fmt))
         self.format = fmt
         self.random = bool(getattr(args, "random", True))
         self.size, self.shape = size, shape

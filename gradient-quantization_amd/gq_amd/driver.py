@@ -45,7 +45,7 @@ quantizer_choices = {          # main.py:20-26
     'pvq': ProbabilisticVectorCompressor,      # the unbiased vector quantiser (not in main.py's table: INTEGRATION.md)
     'rq': ResidualCompressor,                  # two stages: hsq, then pvq on what it leaves (not in main.py's table either)
     'maurey': MaureySparsification,            # the unbiased sparsifier: k draws with P(i) = |v_i| / ||v||_1 (likewise)
-    'mx': MXCompressor,                        # block-scaled small floats (MXFP4 / MXFP8, --mx-format): not in the reference at all
+    'mx': MXCompressor,                        # block-scaled small floats (MXFP4 / MXFP6 / MXFP8, --mx-format): not in the reference at all
 }
 
 
@@ -170,8 +170,8 @@ def build_parser():
     p.add_argument('--momentum-correction', dest='momentum_correction', type=float, default=None, metavar='M',
                    help='--quantizer topk only, not with --ef: momentum correction and momentum factor masking (Deep Gradient Compression) '
                         'with momentum M in the quantizer; the optimizer then runs with momentum 0 (weight decay stays with it)')
-    p.add_argument('--mx-format', dest='mx_format', type=str, default='fp4', choices=['fp4', 'fp8'],
-                   help='--quantizer mx: the element format under the per-block scale byte (4.25 or 8.25 bits per element)')
+    p.add_argument('--mx-format', dest='mx_format', type=str, default='fp4', choices=['fp4', 'fp6_e2m3', 'fp6_e3m2', 'fp8'],
+                   help='--quantizer mx: the element format under the per-block scale byte (4.25, 6.25 or 8.25 bits per element)')
     p.add_argument('--mx-rotate', dest='mx_rotate', type=str, default='none', choices=['none', 'hadamard'],
                    help='--quantizer mx: a randomized 256-point Hadamard rotation in front of the quantiser and its inverse behind the '
                         'decode (lower error on heavy-tailed gradients, the same bits per element; not in ring mode)')

@@ -959,14 +959,15 @@ class MaureyBatch(_ItemBatch):
         _check(rc, "gq_maurey_compress_batched", MAUREY_LIBRARY)
 
 
-# ---- block-scaled small floats (MXFP4 / MXFP8): libgq_mx.so (include/gq_mx.h) ---------------------------------------------------
-MX_ABI_VERSION = 1
+# ---- block-scaled small floats (MXFP4 / MXFP6 / MXFP8): libgq_mx.so (include/gq_mx.h) ---------------------------------------------------
+MX_ABI_VERSION = 2
 MX_EXPORTS = ["gq_mx_abi_version", "gq_mx_last_error", "gq_mx_compress_batched", "gq_mx_decode_sum_batched"]
 MX_BLOCK = 32               # GQ_MX_BLOCK: elements that share a scale byte
 MX_ITEM_ELEMS = 4096        # GQ_MX_ITEM_ELEMS: elements per item
 MX_FP4, MX_FP8 = 0, 1       # GQ_MX_FP4 / GQ_MX_FP8
-MX_FORMATS = {"fp4": MX_FP4, "fp8": MX_FP8}
-MX_CODE_BITS = {MX_FP4: 4, MX_FP8: 8}
+MX_FP6_E2M3, MX_FP6_E3M2 = 0x23, 0x32      # GQ_MX_FP6_E2M3 / GQ_MX_FP6_E3M2: exponent bits, mantissa bits as hex digits
+MX_FORMATS = {"fp4": MX_FP4, "fp8": MX_FP8, "fp6_e2m3": MX_FP6_E2M3, "fp6_e3m2": MX_FP6_E3M2}
+MX_CODE_BITS = {MX_FP4: 4, MX_FP8: 8, MX_FP6_E2M3: 6, MX_FP6_E3M2: 6}
 
 MX_LIBRARY = Library("libgq_mx.so", "GQ_MX_LIB_PATH", "gq_mx_", MX_ABI_VERSION, MX_EXPORTS)
 MX_LIB_PATH = MX_LIBRARY.path
@@ -1008,7 +1009,7 @@ class MXBatch(_ItemBatch):
 
 
 # ---- the same behind a randomized Hadamard rotation: libgq_mxr.so (include/gq_mxr.h) ----------------------------------------------
-MXR_ABI_VERSION = 1
+MXR_ABI_VERSION = 2
 MXR_EXPORTS = ["gq_mxr_abi_version", "gq_mxr_last_error", "gq_mxr_compress_batched", "gq_mxr_decode_sum_batched"]
 MXR_BLOCK = 256             # GQ_MXR_BLOCK: elements of a rotation block
 

@@ -1,5 +1,5 @@
 /*
- * libgq_mx.so -- a block-scaled small-float gradient compressor (OCP Microscaling: MXFP4 / MXFP8) on gfx950.
+ * libgq_mx.so -- a block-scaled small-float gradient compressor (OCP Microscaling: MXFP4 / MXFP6 / MXFP8) on gfx950.
  *
  * A library of its own next to libgq_hsq.so, with the conventions of libgq_sign.so and libgq_maurey.so:
  *   - return value: GQ_OK (0) or a negative GQ_ERR_* code (values of include/gq_hsq.h); gq_mx_last_error() gives text;
@@ -14,6 +14,10 @@
  * FORMATS      format 0  FP4 E2M1        bits 4, mb 1, bias 1, emax 2, magnitude codes 0..7   (cmax 7,   mag 6)
  *              format 1  FP8 E4M3 (OCP)  bits 8, mb 3, bias 7, emax 8, magnitude codes 0..126 (cmax 126, mag 448); no
  *                        infinities; magnitude code 127 (the format's NaN) is never written
+ *              format 0x23  FP6 E2M3     bits 6, mb 3, bias 1, emax 2, magnitude codes 0..31  (cmax 31,  mag 7.5)
+ *              format 0x32  FP6 E3M2     bits 6, mb 2, bias 3, emax 4, magnitude codes 0..31  (cmax 31,  mag 28)
+ *                        (the ids of the 6-bit formats: exponent bits, mantissa bits as hex digits; neither has infinities
+ *                        or NaNs, every one of the 64 codes is a value)
  *     mag(c) = c * 2^(1-bias-mb)                                      for c < 2^mb  (the format's subnormals)
  *     mag(c) = (2^mb + (c & (2^mb - 1))) * 2^((c >> mb) - bias - mb)  otherwise;    strictly increasing in c
  *     A code is  sign << (bits - 1) | c,  sign = the element's own sign bit (+-0 keep their sign).
@@ -26,7 +30,7 @@
  *     a >= 0x7f800000 (an infinity or a NaN in the block): the scale byte is 0xFF and EVERY code of the block is 0; every
  *              element of the block decodes to the NaN 0x7fc00000.
  *     otherwise  E = a >> 23,  M = a & 0x7fffff,  ea = E ? E - 127 : -126,
- *              over = E != 0 && M > MTHR,   MTHR = 0x400000 (FP4: 1.5) or 0x600000 (FP8: 1.75),
+ *              over = E != 0 && M > MTHR,   MTHR = 0x400000 (FP4: 1.5), 0x600000 (FP8, FP6 E3M2: 1.75) or 0x700000 (FP6 E2M3: 1.875),
  *              e = max(ea - emax + over, -127),   scale byte = e + 127   (0 ... 253).
  *     Then |w_i| * 2^-e <= mag(cmax) for every element: nothing is ever clamped.  An all-zero block gets byte 0.
  *
@@ -49,8 +53,13 @@
  *     _up(nb) bytes               the scale bytes, block b at byte b; zero bytes up to _up(nb)     (_up: to a multiple of 16)
  *     FP4: 16 bytes per block     element 2i in the low nibble of byte i, element 2i + 1 in the high nibble
  *     FP8: 32 bytes per block     element i in byte i
- *     The codes of the padding elements are 0.  The section, _up(nb) + 16 nb or _up(nb) + 32 nb bytes, is a multiple of 16,
- *     and EVERY byte of it is written: the wire depends on the input (and the draws) alone.
+ *     FP6: 24 bytes per block     the codes of block b are the 24 bytes at 24 b; read as a 192-bit little-endian bit string,
+ *                                 element i occupies bits 6i .. 6i+5 (the convention of GQ_LEVELS_PACKED6)
+ *     zero bytes up to a multiple of 16 (FP6 with an odd nb: 8 bytes; none otherwise)
+ *     The codes of the padding elements are 0.  The section, _up(nb) + _up(16 nb), _up(nb) + _up(24 nb) or _up(nb) + _up(32 nb)
+ *     bytes, is a multiple of 16, and EVERY byte of it is written, that pad included: the wire depends on the input (and the
+ *     draws) alone.
+ *     No launch loads a byte outside the sections it is given, and none stores one outside them (+ the dense tensors' copy).
  *
  * DECODE       An element's value is  +-ldexp(mag(c), e),  e = scale byte - 127: one exact scaling -- for every code and every
  *              scale byte a compress writes the result is representable (subnormal results included) unless it reaches 2^128,
@@ -67,11 +76,13 @@
 extern "C" {
 #endif
 
-#define GQ_MX_ABI_VERSION 1
+#define GQ_MX_ABI_VERSION 2
 #define GQ_MX_BLOCK 32            /* elements that share a scale byte */
 #define GQ_MX_ITEM_ELEMS 4096     /* elements (128 blocks) per item: every launch walks a tensor in items of this size */
 #define GQ_MX_FP4 0
 #define GQ_MX_FP8 1
+#define GQ_MX_FP6_E2M3 0x23
+#define GQ_MX_FP6_E3M2 0x32
 
 /*
  * The tensors of one group, table-driven like gq_sign_batch: ONE launch serves all of them.
@@ -90,7 +101,7 @@ typedef struct gq_mx_batch {
     const int32_t *item_seg;
     const int64_t *dense_table;
     int32_t ndense;
-    int32_t format;            /* GQ_MX_FP4 or GQ_MX_FP8 */
+    int32_t format;            /* GQ_MX_FP4, GQ_MX_FP8, GQ_MX_FP6_E2M3 or GQ_MX_FP6_E3M2 */
 } gq_mx_batch;
 
 int gq_mx_abi_version(void);

@@ -8,8 +8,8 @@
  *
  * The conventions are include/gq_mx.h's: return codes, gq_mxr_last_error(), nothing allocated, no scratch, ONE launch per call,
  * and every launch argument depends on the layout alone, so both launches replay from a HIP graph.  seg_table, item_seg,
- * dense_table, items of GQ_MX_ITEM_ELEMS, wire sections, draw numbering and random modes are exactly gq_mx.h's: the wire format
- * does not change, and a receiver needs the same sign words to decode.
+ * dense_table, items of GQ_MX_ITEM_ELEMS, formats (the two 6-bit ones and their zero pad included), wire sections, draw numbering
+ * and random modes are exactly gq_mx.h's: the wire format does not change, and a receiver needs the same sign words to decode.
  *
  * ROTATION BLOCK   GQ_MXR_BLOCK = 256 consecutive elements of the flattened tensor, starting at multiples of 256.  A tensor of n
  *              elements has n / 256 (integer) rotated blocks; its last n % 256 elements are NOT rotated (a tensor below 256
@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define GQ_MXR_ABI_VERSION 1
+#define GQ_MXR_ABI_VERSION 2
 #define GQ_MXR_BLOCK 256          /* elements of a rotation block: 8 MX blocks */
 
 /* gq_mx_batch's fields (include/gq_mx.h: the same tables), then the sign words; the kernels take the words by value. */
@@ -69,7 +69,7 @@ typedef struct gq_mxr_batch {
     const int32_t *item_seg;
     const int64_t *dense_table;
     int32_t ndense;
-    int32_t format;            /* GQ_MX_FP4 or GQ_MX_FP8 */
+    int32_t format;            /* GQ_MX_FP4, GQ_MX_FP8, GQ_MX_FP6_E2M3 or GQ_MX_FP6_E3M2 */
     uint64_t signs[4];
 } gq_mxr_batch;
 

@@ -1,20 +1,26 @@
 """Time the microscaling kernels (libgq_mx.so) on one MI355X, next to signSGD and QSGD in the same process:
 
-    python tools/mx_time.py [--out FILE]      (default: profiles/mx_time.jsonl)
+    python tools/mx_time.py [--out FILE] [--parent-lib libgq_mx.so]      (default: profiles/mx_time.jsonl)
 
 Rows (one JSON line each):
   resnet50_step   PSQuantizer record + apply over the ResNet-50 parameter list (tests/golden/resnet50_cifar_shapes.json), one
-                  user, default launches (graph replay), gradients at fixed addresses: --quantizer mx with fp4 and fp8,
+                  user, default launches (graph replay), gradients at fixed addresses: --quantizer mx with fp4, fp6_e2m3,
+                  fp6_e3m2 and fp8,
                   --quantizer sign, and QSGD --c-dim 32 --n-bit 2 (the same 4-bit codes, the same draw per element), alternated
                   in this process, three rounds each; wire bytes per user against the dense 94,083,376.
-  single_25m      one 25 M-element tensor: the compress launch alone (fp4 / fp8, stochastic rounding from the device generator
+  single_25m      one 25 M-element tensor: the compress launch alone (fp4 / fp6_e2m3 / fp6_e3m2 / fp8, stochastic rounding from the device generator
                   and deterministic) and the decode-mean at R = 1 and 8, next to the QSGD c_dim 32 bucketed compress launch
                   (the same bytes moved, one draw per element) and the sign compress; mx_fp4_over_qsgd is the ratio the README
                   quotes.  *_given_*: the draws handed in (no hash); *_graphed_*: ten launches replayed from one HIP graph (the
                   device's time without the host's share of an eager launch).
+                  --parent-lib: an older build of libgq_mx.so (say the parent commit's) loaded next to the in-tree one, its fp4 /
+                  fp8 launches alternated with the in-tree ones in the same rounds (parent_mx_*); *_over_parent_fp8: a launch of
+                  this build over the parent's fp8 launch of the same kind, *_over_parent: over the parent's same launch.
 Times: HIP events around a window of back-to-back calls after untimed ones, median of the windows, microseconds per call; the
 paths of a row are alternated round by round and the minimum over the rounds is reported next to every round."""
 import argparse
+import contextlib
+import ctypes
 import json
 import os
 import sys
@@ -25,6 +31,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gradient-quantization_amd"))
 
+from gq_amd import native  # noqa: E402
 from gq_amd.codecs import BatchedMX, BatchedQSGD, BatchedSign, MXCodec, QSGDCodec, SignCodec  # noqa: E402
 from gq_amd.compressors import MXCompressor, QSGDCompressor, SignSGDCompressor  # noqa: E402
 from gq_amd.quantizers import PSQuantizer  # noqa: E402
@@ -72,7 +79,8 @@ def resnet50_rows(dev):
     torch.manual_seed(0)
     src = [torch.randn(s, device=dev) * 1e-2 for s in shapes]
     variants = {}
-    for name, comp, kw in (("mx_fp4", MXCompressor, {}), ("mx_fp8", MXCompressor, {"mx_format": "fp8"}),
+    for name, comp, kw in (("mx_fp4", MXCompressor, {}), ("mx_fp6_e2m3", MXCompressor, {"mx_format": "fp6_e2m3"}),
+                           ("mx_fp6_e3m2", MXCompressor, {"mx_format": "fp6_e3m2"}), ("mx_fp8", MXCompressor, {"mx_format": "fp8"}),
                            ("sign", SignSGDCompressor, {"random": 0}), ("qsgd_c32_n2", QSGDCompressor, {})):
         params = [torch.nn.Parameter(torch.zeros(s, device=dev)) for s in shapes]
         variants[name] = (PSQuantizer(comp, params, _args(**kw)), params)
@@ -97,7 +105,28 @@ def resnet50_rows(dev):
     return out
 
 
-def single_rows(dev, n=25_000_000):
+FORMATS = ("fp4", "fp6_e2m3", "fp6_e3m2", "fp8")
+
+
+@contextlib.contextmanager
+def library(path):
+    """Groups built inside bind their launches to another build of libgq_mx.so (whatever ABI number it reports: the two entry
+    points and the descriptor's layout have not changed since version 1); path None: the in-tree library."""
+    if path is None:
+        yield
+        return
+    probe = ctypes.CDLL(path)
+    probe.gq_mx_abi_version.restype = ctypes.c_int
+    other = native.Library("libgq_mx.so", "GQ_MX_LIB_PATH", "gq_mx_", probe.gq_mx_abi_version(), native.MX_EXPORTS)
+    other.path = path
+    saved, native.MXBatch.LIBRARY = native.MXBatch.LIBRARY, other      # (a descriptor takes its library when it is built)
+    try:
+        yield
+    finally:
+        native.MXBatch.LIBRARY = saved
+
+
+def single_rows(dev, n=25_000_000, parent_lib=None):
     torch.manual_seed(1)
     t = torch.randn(n, device=dev)
     paths, groups, wires = {}, {}, {}
@@ -110,11 +139,14 @@ def single_rows(dev, n=25_000_000):
             wire[r].copy_(wire[0])
         return g, wire
 
-    for fmt in ("fp4", "fp8"):
+    for fmt in FORMATS:
         for random in (1, 0):
             name = "mx_%s_%s" % (fmt, "stochastic" if random else "nearest")
             cd = MXCodec(MXCompressor(n, (n,), _args(mx_format=fmt, random=random)), n, (n,))
             groups[name], wires[name] = one(BatchedMX, cd)
+            if parent_lib and fmt in ("fp4", "fp8"):
+                with library(parent_lib):
+                    groups["parent_" + name], wires["parent_" + name] = one(BatchedMX, cd)
     qc = QSGDCodec(QSGDCompressor(n, (n,), _args()), n, (n,))
     BatchedQSGD.place_lone_buckets([qc])
     assert qc.bits == 4 and qc.d == 32 and not BatchedQSGD.is_wide(qc)
@@ -145,10 +177,25 @@ def single_rows(dev, n=25_000_000):
     row["mx_fp4_over_qsgd_graphed"] = round(row["mx_fp4_stochastic_compress_graphed_us"] / row["qsgd_c32_n2_compress_graphed_us"], 3)
     row["mx_fp4_over_qsgd"] = round(row["mx_fp4_stochastic_compress_us"] / row["qsgd_c32_n2_compress_us"], 3)
     row["mx_fp4_over_qsgd_rounds"] = [round(a / b, 3) for a, b in zip(paths["mx_fp4_stochastic"], paths["qsgd_c32_n2"])]
-    for name in ("mx_fp4_stochastic", "mx_fp8_stochastic", "qsgd_c32_n2", "sign"):
-        g, w = groups[name], wires[name]
-        for R in (1, 8):
-            row["%s_decode_mean_R%d_us" % (name, R)] = round(timed(lambda: g.decode_mean(w[:R], R)), 2)
+    dec = ["mx_%s_stochastic" % f for f in FORMATS] + [k for k in groups if k.startswith("parent_") and k.endswith("stochastic")]
+    dec += ["qsgd_c32_n2", "sign"]
+    for R in (1, 8):
+        for rnd in range(3):
+            for name in dec:
+                g, w = groups[name], wires[name]
+                paths.setdefault("%s_decode_R%d" % (name, R), []).append(timed(lambda: g.decode_mean(w[:R], R)))
+        for name in dec:
+            ts = paths["%s_decode_R%d" % (name, R)]
+            row["%s_decode_mean_R%d_us_rounds" % (name, R)] = [round(x, 2) for x in ts]
+            row["%s_decode_mean_R%d_us" % (name, R)] = round(min(ts), 2)
+    if parent_lib:
+        for fmt in FORMATS:
+            ref = "fp8" if fmt.startswith("fp6") else fmt
+            tag = "_over_parent_fp8" if fmt.startswith("fp6") else "_over_parent"
+            for kind in ("stochastic_compress", "nearest_compress", "stochastic_compress_graphed", "nearest_compress_graphed",
+                         "stochastic_decode_mean_R1", "stochastic_decode_mean_R8"):
+                a, b = row["mx_%s_%s_us" % (fmt, kind)], row["parent_mx_%s_%s_us" % (ref, kind)]
+                row["mx_%s_%s%s" % (fmt, kind, tag)] = round(a / b, 3)
     nb = row["mx_fp4_stochastic_wire_bytes"]
     row["mx_fp4_compress_TBps"] = round((4 * n + nb) / (row["mx_fp4_stochastic_compress_us"] * 1e-6) / 1e12, 2)
     return [row]
@@ -157,9 +204,10 @@ def single_rows(dev, n=25_000_000):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx_time.jsonl"))
+    ap.add_argument("--parent-lib", default=None, help="an older libgq_mx.so to time next to the in-tree one (parent_mx_* fields)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    rows = single_rows(dev) + resnet50_rows(dev)
+    rows = single_rows(dev, parent_lib=a.parent_lib) + resnet50_rows(dev)
     lines = [json.dumps(r) for r in rows]
     print("\n".join(lines))
     with open(a.out, "w") as f:

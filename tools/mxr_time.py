@@ -7,7 +7,7 @@ Rows (one JSON line each):
                   user, default launches (graph replay), gradients at fixed addresses: --quantizer mx with and without
                   --mx-rotate hadamard, alternated, three rounds each.
   single_25m      one 25 M-element tensor: the compress launch alone, gq_mxr_compress_batched against gq_mx_compress_batched,
-                  fp4 / fp8, stochastic (device generator) and nearest, eager and as ten launches replayed from one HIP graph;
+                  fp4 / fp6_e2m3 / fp6_e3m2 / fp8, stochastic (device generator) and nearest, eager and as ten launches replayed from one HIP graph;
                   the decode-mean at R = 1 and R = 8.  *_over_plain: the ratio to the plain MX launch of the same run -- the
                   plain launch is the yardstick, not this code.
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gradient-quantization_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from mx_time import _args, graphed, timed  # noqa: E402
+from mx_time import FORMATS, _args, graphed, timed  # noqa: E402
 from gq_amd.codecs import BatchedMX, BatchedMXR, MXCodec, MXRCodec  # noqa: E402
 from gq_amd.compressors import MXCompressor  # noqa: E402
 from gq_amd.quantizers import PSQuantizer  # noqa: E402
@@ -35,8 +35,9 @@ def resnet50_rows(dev):
     torch.manual_seed(0)
     src = [torch.randn(s, device=dev) * 1e-2 for s in shapes]
     variants = {}
-    for name, kw in (("mx_fp4", {}), ("mxr_fp4", {"mx_rotate": "hadamard"}),
-                     ("mx_fp8", {"mx_format": "fp8"}), ("mxr_fp8", {"mx_format": "fp8", "mx_rotate": "hadamard"})):
+    for name, kw in [("mx_fp4", {}), ("mxr_fp4", {"mx_rotate": "hadamard"})] + [
+            (kind + "_" + f, dict({"mx_format": f}, **({"mx_rotate": "hadamard"} if kind == "mxr" else {})))
+            for f in FORMATS[1:] for kind in ("mx", "mxr")]:
         params = [torch.nn.Parameter(torch.zeros(s, device=dev)) for s in shapes]
         variants[name] = (PSQuantizer(MXCompressor, params, _args(**kw)), params)
     rows = {}
@@ -55,7 +56,7 @@ def resnet50_rows(dev):
         q = variants[name][0]
         out.append({"case": "resnet50_step", "path": name, "us_per_step_rounds": [round(t, 2) for t in ts], "us_per_step_min": round(min(ts), 2),
                     "wire_bytes_per_user": q.wire_bytes_per_user(), "record_paths": dict(q.record_paths)})
-    for fmt in ("fp4", "fp8"):
+    for fmt in FORMATS:
         out.append({"case": "resnet50_step", "path": "mxr_%s_over_plain" % fmt,
                     "ratio_min": round(min(rows["mxr_" + fmt]) / min(rows["mx_" + fmt]), 3),
                     "ratio_rounds": [round(a / b, 3) for a, b in zip(rows["mxr_" + fmt], rows["mx_" + fmt])]})
@@ -66,7 +67,7 @@ def single_rows(dev, n=25_000_000):
     torch.manual_seed(1)
     t = torch.randn(n, device=dev)
     groups, wires, paths = {}, {}, {}
-    for fmt in ("fp4", "fp8"):
+    for fmt in FORMATS:
         for random in (1, 0):
             for rot in (False, True):
                 name = "%s_%s_%s" % ("mxr" if rot else "mx", fmt, "stochastic" if random else "nearest")
@@ -90,7 +91,7 @@ def single_rows(dev, n=25_000_000):
         w = wires[name]
         row[name + "_compress_graphed_us"] = round(graphed(lambda: g.encode([t], w[0], 0, 0)), 2)
     out = torch.empty(groups["mx_fp4_nearest"].out_floats, device=dev)
-    for fmt in ("fp4", "fp8"):
+    for fmt in FORMATS:
         for R in (1, 8):
             for rnd in range(3):
                 for kind in ("mx", "mxr"):
