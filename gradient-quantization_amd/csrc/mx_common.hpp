@@ -37,6 +37,79 @@ struct Fmt<GQ_MX_FP6_E3M2> {
 
 __host__ __device__ constexpr int64_t up16(int64_t x) { return (x + 15) / 16 * 16; }
 
+// ---- the tensor-side element type (include/gq_mx.h, TENSOR-SIDE TYPE): sources, both launches' `out`, dense-copy sources -----------
+// An enum, not a C++ type, so that another 16-bit format can follow (its widen / narrow pair and a Tensor<> line).
+enum { TT_F32 = 0, TT_BF16 = 1 };
+template <int TT>
+struct Tensor;
+template <>
+struct Tensor<TT_F32> {
+    using type = float;
+};
+template <>
+struct Tensor<TT_BF16> {
+    using type = uint16_t;
+};
+
+// widen: the f32 with bits h << 16 -- exact, NaNs and signed zeros included
+__device__ __forceinline__ float widen(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
+
+// narrow: round to nearest even onto bf16, in integers; every NaN becomes 0x7FC0.  The carry runs into the exponent and reaches
+// +-inf at the top; f32 subnormals round onto bf16's grid as they are.
+__device__ __forceinline__ uint16_t narrow(float x) {
+    const uint32_t b = __float_as_uint(x);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return (uint16_t)0x7FC0u;
+    return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
+}
+
+__device__ __forceinline__ float to_f32(float x) { return x; }
+__device__ __forceinline__ float to_f32(uint16_t h) { return widen(h); }
+template <class T>
+__device__ __forceinline__ T from_f32(float x);
+template <>
+__device__ __forceinline__ float from_f32<float>(float x) {
+    return x;
+}
+template <>
+__device__ __forceinline__ uint16_t from_f32<uint16_t>(float x) {
+    return narrow(x);
+}
+__device__ __forceinline__ uint32_t narrow2(float lo, float hi) { return (uint32_t)narrow(lo) | ((uint32_t)narrow(hi) << 16); }
+
+// A lane's 8 elements as f32, full form: all 8 exist and p is 16-byte aligned -- two float4 loads, or ONE 16-byte load of 8 bf16.
+__device__ __forceinline__ void load8(const float *p, float (&w)[8]) {
+    const float4 a0 = *reinterpret_cast<const float4 *>(p), a1 = *reinterpret_cast<const float4 *>(p + 4);
+    w[0] = a0.x, w[1] = a0.y, w[2] = a0.z, w[3] = a0.w, w[4] = a1.x, w[5] = a1.y, w[6] = a1.z, w[7] = a1.w;
+}
+__device__ __forceinline__ void load8(const uint16_t *p, float (&w)[8]) {
+    const uint4 a = *reinterpret_cast<const uint4 *>(p);
+    w[0] = __uint_as_float(a.x << 16), w[1] = __uint_as_float(a.x & 0xffff0000u);
+    w[2] = __uint_as_float(a.y << 16), w[3] = __uint_as_float(a.y & 0xffff0000u);
+    w[4] = __uint_as_float(a.z << 16), w[5] = __uint_as_float(a.z & 0xffff0000u);
+    w[6] = __uint_as_float(a.w << 16), w[7] = __uint_as_float(a.w & 0xffff0000u);
+}
+// ragged form (a tensor's end, or a view that is not 16-byte aligned): the kernels walk the elements that exist one by one --
+// to_f32(p[k]) is the scalar load, p[k] = from_f32<T>(x) the scalar store
+
+// 8 f32 into a lane's 8 elements of T, full form (as load8): two float4 stores, or ONE 16-byte store of 8 narrowed values
+__device__ __forceinline__ void store8(float *p, const float (&f)[8]) {
+    *reinterpret_cast<float4 *>(p) = make_float4(f[0], f[1], f[2], f[3]);
+    *reinterpret_cast<float4 *>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
+}
+__device__ __forceinline__ void store8(uint16_t *p, const float (&f)[8]) {
+    *reinterpret_cast<uint4 *>(p) = make_uint4(narrow2(f[0], f[1]), narrow2(f[2], f[3]), narrow2(f[4], f[5]), narrow2(f[6], f[7]));
+}
+// gql::copy_dense with sources of T: the identity-compressed tensors into the wire's f32 dense region, widened where T is 16-bit
+template <int THREADS, class T>
+__device__ __forceinline__ void copy_dense_as_f32(const int64_t *__restrict__ dense_table, int ndense, uint8_t *__restrict__ wire) {
+    for (int t = blockIdx.x; t < ndense; t += gridDim.x) {
+        const T *src = reinterpret_cast<const T *>(dense_table[3 * t]);
+        float *dst = reinterpret_cast<float *>(wire + dense_table[3 * t + 1]);
+        const int64_t n = dense_table[3 * t + 2];
+        for (int64_t i = threadIdx.x; i < n; i += THREADS) dst[i] = to_f32(src[i]);
+    }
+}
+
 // the block exponent e of a block whose largest magnitude has the bits a (finite), integers only
 template <class F>
 __device__ __forceinline__ int block_exponent(uint32_t a) {

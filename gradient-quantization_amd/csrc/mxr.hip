@@ -113,24 +113,28 @@ __device__ __forceinline__ void inverse(float (&y)[PER_LANE], uint32_t sbyte, bo
     for (int k = 0; k < PER_LANE; ++k) y[k] = rot ? flip(t[k], sbyte, k) : y[k];
 }
 
-template <int FMT, int MODE, bool EF>
+template <int FMT, int MODE, bool EF, int TT>
 __global__ __launch_bounds__(THREADS) void mxr_compress_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
-                                                               uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
+                                                               uint8_t *__restrict__ wire, typename Tensor<TT>::type *__restrict__ out, float ef_scale,
                                                                int random_mode, const float *__restrict__ rbuf, uint64_t seed,
                                                                const int64_t *__restrict__ dense_table, int ndense, Signs signs) {
     using F = Fmt<FMT>;
+    using T = typename Tensor<TT>::type;
     if (MODE == DRAW_DEVICE) gq::resolve_seed(random_mode, seed);
-    copy_dense<THREADS>(dense_table, ndense, wire);
+    if (TT == TT_F32)
+        copy_dense<THREADS>(dense_table, ndense, wire);
+    else
+        copy_dense_as_f32<THREADS, T>(dense_table, ndense, wire);
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
     const int64_t n = rec[1];
     const int64_t nb = (n + GQ_MX_BLOCK - 1) / GQ_MX_BLOCK, nb_pad = up16(nb);
-    float *v = reinterpret_cast<float *>(rec[0]);
+    T *v = reinterpret_cast<T *>(rec[0]);
     float *err = EF ? reinterpret_cast<float *>(rec[7]) : nullptr;
     uint8_t *scales = wire + rec[3];
     uint8_t *codes = scales + nb_pad;
-    float *o = out ? out + rec[5] : nullptr;
+    T *o = out ? out + rec[5] : nullptr;
     const int64_t first_draw = rec[6];
     const int lane = threadIdx.x & 63;
     const uint32_t sbyte = sign_byte(signs);
@@ -145,11 +149,10 @@ __global__ __launch_bounds__(THREADS) void mxr_compress_kernel(const int64_t *__
         const bool ef = EF && err;
         const bool full = e0 + PER_LANE - 1 < n && aligned16(v + e0) && (!ef || aligned16(err + e0));
         if (full) {
-            const float4 a0 = *reinterpret_cast<const float4 *>(v + e0), a1 = *reinterpret_cast<const float4 *>(v + e0 + 4);
-            w[0] = a0.x, w[1] = a0.y, w[2] = a0.z, w[3] = a0.w, w[4] = a1.x, w[5] = a1.y, w[6] = a1.z, w[7] = a1.w;
+            load8(v + e0, w);
             if (ef) {
-                const float4 r0 = *reinterpret_cast<const float4 *>(err + e0), r1 = *reinterpret_cast<const float4 *>(err + e0 + 4);
-                const float rr[PER_LANE] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+                float rr[PER_LANE];
+                load8(err + e0, rr);
 #pragma unroll
                 for (int k = 0; k < PER_LANE; ++k) {
                     const float p = ef_scale * rr[k];      // (-ffp-contract=off: the product rounded, then the sum)
@@ -160,7 +163,7 @@ __global__ __launch_bounds__(THREADS) void mxr_compress_kernel(const int64_t *__
 #pragma unroll
             for (int k = 0; k < PER_LANE; ++k) {
                 if (e0 + k < n) {
-                    w[k] = v[e0 + k];
+                    w[k] = to_f32(v[e0 + k]);
                     if (ef) {
                         const float p = ef_scale * err[e0 + k];
                         w[k] = w[k] + p;
@@ -199,21 +202,19 @@ __global__ __launch_bounds__(THREADS) void mxr_compress_kernel(const int64_t *__
                 const bool vec = e0 + PER_LANE - 1 < n;
                 if (o) {
                     if (vec && aligned16(o + e0)) {
-                        *reinterpret_cast<float4 *>(o + e0) = make_float4(d[0], d[1], d[2], d[3]);
-                        *reinterpret_cast<float4 *>(o + e0 + 4) = make_float4(d[4], d[5], d[6], d[7]);
+                        store8(o + e0, d);
                     } else {
-                        for (int k = 0; k < PER_LANE && e0 + k < n; ++k) o[e0 + k] = d[k];
+                        for (int k = 0; k < PER_LANE && e0 + k < n; ++k) o[e0 + k] = from_f32<T>(d[k]);
                     }
                 }
-                if (ef) {
+                if (ef) {      // the residual from the UNROUNDED w; only the copy stored back into the source is narrowed (T = bf16)
                     if (full) {
-                        *reinterpret_cast<float4 *>(v + e0) = make_float4(w[0], w[1], w[2], w[3]);
-                        *reinterpret_cast<float4 *>(v + e0 + 4) = make_float4(w[4], w[5], w[6], w[7]);
+                        store8(v + e0, w);
                         *reinterpret_cast<float4 *>(err + e0) = make_float4(w[0] - d[0], w[1] - d[1], w[2] - d[2], w[3] - d[3]);
                         *reinterpret_cast<float4 *>(err + e0 + 4) = make_float4(w[4] - d[4], w[5] - d[5], w[6] - d[6], w[7] - d[7]);
                     } else {
                         for (int k = 0; k < PER_LANE && e0 + k < n; ++k) {
-                            v[e0 + k] = w[k];
+                            v[e0 + k] = from_f32<T>(w[k]);
                             err[e0 + k] = w[k] - d[k];
                         }
                     }
@@ -245,10 +246,10 @@ __global__ __launch_bounds__(THREADS) void mxr_compress_kernel(const int64_t *__
     }
 }
 
-template <int FMT>
+template <int FMT, int TT>
 __global__ __launch_bounds__(THREADS) void mxr_decode_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                              const uint8_t *__restrict__ gathered, int64_t stride, int R,
-                                                             float *__restrict__ out, int plain, Signs signs) {
+                                                             typename Tensor<TT>::type *__restrict__ out, int plain, Signs signs) {
     using F = Fmt<FMT>;
     constexpr int CODE_BYTES = PER_LANE * F::bits / 8;      // a lane's code bytes: 4 (FP4), 6 (FP6) or 8 (FP8)
     const int64_t item = blockIdx.x;
@@ -256,7 +257,8 @@ __global__ __launch_bounds__(THREADS) void mxr_decode_kernel(const int64_t *__re
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
     const int64_t n = rec[1], off = rec[3];
     const int64_t nb_pad = up16((n + GQ_MX_BLOCK - 1) / GQ_MX_BLOCK);
-    float *o = out + rec[5];
+    using T = typename Tensor<TT>::type;
+    T *o = out + rec[5];
     const int64_t base = (item - rec[2]) * GQ_MX_ITEM_ELEMS;
     const bool direct = plain && R == 1;
     const float fR = (float)R;
@@ -312,10 +314,9 @@ __global__ __launch_bounds__(THREADS) void mxr_decode_kernel(const int64_t *__re
         inverse(f, sbyte, rot);      // the mean first, then ONE inverse rotation
         if (live) {
             if (e0 + PER_LANE - 1 < n && aligned16(o + e0)) {
-                *reinterpret_cast<float4 *>(o + e0) = make_float4(f[0], f[1], f[2], f[3]);
-                *reinterpret_cast<float4 *>(o + e0 + 4) = make_float4(f[4], f[5], f[6], f[7]);
+                store8(o + e0, f);      // (T = bf16: the f32 result narrowed once, here)
             } else {
-                for (int k = 0; k < PER_LANE && e0 + k < n; ++k) o[e0 + k] = f[k];
+                for (int k = 0; k < PER_LANE && e0 + k < n; ++k) o[e0 + k] = from_f32<T>(f[k]);
             }
         }
     }
@@ -334,86 +335,110 @@ static int check_batch(const gq_mxr_batch *b, const char *what, bool compress) {
 
 static Signs signs_of(const gq_mxr_batch *b) { return Signs{{b->signs[0], b->signs[1], b->signs[2], b->signs[3]}}; }
 
-template <int FMT, int MODE>
-static void launch_compress(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale, float *out,
-                            hipStream_t st) {
+template <int FMT, int MODE, int TT>
+static void launch_compress(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
+                            typename Tensor<TT>::type *out, hipStream_t st) {
     const dim3 grid((unsigned)b->nitems), block(THREADS);
     if (!isnan(ef_scale))
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_compress_kernel<FMT, MODE, true>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_compress_kernel<FMT, MODE, true, TT>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
                            ef_scale, random_mode, r, seed, b->dense_table, b->ndense, signs_of(b));
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_compress_kernel<FMT, MODE, false>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_compress_kernel<FMT, MODE, false, TT>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
                            0.0f, random_mode, r, seed, b->dense_table, b->ndense, signs_of(b));
 }
 
-template <int FMT>
-static void launch_compress(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale, float *out,
-                            hipStream_t st) {
+template <int FMT, int TT>
+static void launch_compress(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
+                            typename Tensor<TT>::type *out, hipStream_t st) {
     if (random_mode == GQ_RANDOM_OFF)
-        launch_compress<FMT, DRAW_OFF>(b, wire, random_mode, r, seed, ef_scale, out, st);
+        launch_compress<FMT, DRAW_OFF, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
     else if (random_mode == GQ_RANDOM_GIVEN)
-        launch_compress<FMT, DRAW_GIVEN>(b, wire, random_mode, r, seed, ef_scale, out, st);
+        launch_compress<FMT, DRAW_GIVEN, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
     else
-        launch_compress<FMT, DRAW_DEVICE>(b, wire, random_mode, r, seed, ef_scale, out, st);
+        launch_compress<FMT, DRAW_DEVICE, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
+}
+
+// The two entry points of a tensor-side type: `what` is the exported name (the refusals quote it).  out needs the alignment of T.
+template <int TT>
+static int compress_batched(const char *what, const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
+                            typename Tensor<TT>::type *out, void *stream) {
+    constexpr unsigned ALIGN = sizeof(typename Tensor<TT>::type);
+    const int rc = check_batch(b, what, true);
+    if (rc != GQ_OK) return rc;
+    if (random_mode != GQ_RANDOM_OFF && random_mode != GQ_RANDOM_GIVEN && random_mode != GQ_RANDOM_DEVICE &&
+        random_mode != GQ_RANDOM_DEVICE_COUNTER)
+        return fail(GQ_ERR_INVALID_ARG, "%s: random_mode %d (off, given, device or device counter)", what, random_mode);
+    if (random_mode == GQ_RANDOM_GIVEN && !r) return fail(GQ_ERR_INVALID_ARG, "%s: GQ_RANDOM_GIVEN without draws", what);
+    if (random_mode == GQ_RANDOM_DEVICE_COUNTER && (seed == 0 || (seed & 7) != 0))
+        return fail(GQ_ERR_INVALID_ARG, "%s: GQ_RANDOM_DEVICE_COUNTER needs the address of a { seed, step } pair", what);
+    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
+        return fail(GQ_ERR_INVALID_ARG, "%s: the wire must be a 16-byte aligned device buffer", what);
+    if ((reinterpret_cast<uintptr_t>(out) & (ALIGN - 1)) != 0 || (reinterpret_cast<uintptr_t>(r) & 3) != 0)
+        return fail(GQ_ERR_INVALID_ARG, "%s: out must be %u-byte aligned and r 4-byte aligned", what, ALIGN);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (b->format == GQ_MX_FP4)
+        launch_compress<GQ_MX_FP4, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
+    else if (b->format == GQ_MX_FP8)
+        launch_compress<GQ_MX_FP8, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
+    else if (b->format == GQ_MX_FP6_E2M3)
+        launch_compress<GQ_MX_FP6_E2M3, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
+    else
+        launch_compress<GQ_MX_FP6_E3M2, TT>(b, wire, random_mode, r, seed, ef_scale, out, st);
+    GQL_CHECK_LAUNCH(what);
+    return GQ_OK;
+}
+
+template <int TT>
+static int decode_sum_batched(const char *what, const gq_mxr_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R,
+                              typename Tensor<TT>::type *out, int plain, void *stream) {
+    constexpr unsigned ALIGN = sizeof(typename Tensor<TT>::type);
+    const int rc = check_batch(b, what, false);
+    if (rc != GQ_OK) return rc;
+    if (!gathered || !out) return fail(GQ_ERR_INVALID_ARG, "%s: null pointer", what);
+    if (R < 1 || (R > 1 && user_stride_bytes < 0))
+        return fail(GQ_ERR_INVALID_ARG, "%s: R = %d, user stride %lld", what, R, (long long)user_stride_bytes);
+    if ((reinterpret_cast<uintptr_t>(out) & (ALIGN - 1)) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be %u-byte aligned", what, ALIGN);
+    const dim3 grid((unsigned)b->nitems), block(THREADS);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (b->format == GQ_MX_FP4)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP4, TT>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
+    else if (b->format == GQ_MX_FP8)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP8, TT>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
+    else if (b->format == GQ_MX_FP6_E2M3)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP6_E2M3, TT>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP6_E3M2, TT>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
+    GQL_CHECK_LAUNCH(what);
+    return GQ_OK;
 }
 
 }  // namespace gqx
 
 GQXR_API int gq_mxr_abi_version(void) { return GQ_MXR_ABI_VERSION; }
-
+                                
 GQXR_API const char *gq_mxr_last_error(void) { return gqx::err_buf; }
 
 GQXR_API int gq_mxr_compress_batched(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
                                      float *out, void *stream) {
-    using namespace gqx;
-    const int rc = check_batch(b, "gq_mxr_compress_batched", true);
-    if (rc != GQ_OK) return rc;
-    if (random_mode != GQ_RANDOM_OFF && random_mode != GQ_RANDOM_GIVEN && random_mode != GQ_RANDOM_DEVICE &&
-        random_mode != GQ_RANDOM_DEVICE_COUNTER)
-        return fail(GQ_ERR_INVALID_ARG, "gq_mxr_compress_batched: random_mode %d (off, given, device or device counter)", random_mode);
-    if (random_mode == GQ_RANDOM_GIVEN && !r) return fail(GQ_ERR_INVALID_ARG, "gq_mxr_compress_batched: GQ_RANDOM_GIVEN without draws");
-    if (random_mode == GQ_RANDOM_DEVICE_COUNTER && (seed == 0 || (seed & 7) != 0))
-        return fail(GQ_ERR_INVALID_ARG, "gq_mxr_compress_batched: GQ_RANDOM_DEVICE_COUNTER needs the address of a { seed, step } pair");
-    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
-        return fail(GQ_ERR_INVALID_ARG, "gq_mxr_compress_batched: the wire must be a 16-byte aligned device buffer");
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0 || (reinterpret_cast<uintptr_t>(r) & 3) != 0)
-        return fail(GQ_ERR_INVALID_ARG, "gq_mxr_compress_batched: out and r must be 4-byte aligned");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (b->format == GQ_MX_FP4)
-        launch_compress<GQ_MX_FP4>(b, wire, random_mode, r, seed, ef_scale, out, st);
-    else if (b->format == GQ_MX_FP8)
-        launch_compress<GQ_MX_FP8>(b, wire, random_mode, r, seed, ef_scale, out, st);
-    else if (b->format == GQ_MX_FP6_E2M3)
-        launch_compress<GQ_MX_FP6_E2M3>(b, wire, random_mode, r, seed, ef_scale, out, st);
-    else
-        launch_compress<GQ_MX_FP6_E3M2>(b, wire, random_mode, r, seed, ef_scale, out, st);
-    GQL_CHECK_LAUNCH("gq_mxr_compress_batched");
-    return GQ_OK;
+    return gqx::compress_batched<gqx::TT_F32>("gq_mxr_compress_batched", b, wire, random_mode, r, seed, ef_scale, out, stream);
 }
 
 GQXR_API int gq_mxr_decode_sum_batched(const gq_mxr_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
                                        void *stream) {
-    using namespace gqx;
-    const int rc = check_batch(b, "gq_mxr_decode_sum_batched", false);
-    if (rc != GQ_OK) return rc;
-    if (!gathered || !out) return fail(GQ_ERR_INVALID_ARG, "gq_mxr_decode_sum_batched: null pointer");
-    if (R < 1 || (R > 1 && user_stride_bytes < 0))
-        return fail(GQ_ERR_INVALID_ARG, "gq_mxr_decode_sum_batched: R = %d, user stride %lld", R, (long long)user_stride_bytes);
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "gq_mxr_decode_sum_batched: out must be 4-byte aligned");
-    const dim3 grid((unsigned)b->nitems), block(THREADS);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (b->format == GQ_MX_FP4)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP4>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
-                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
-    else if (b->format == GQ_MX_FP8)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP8>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
-                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
-    else if (b->format == GQ_MX_FP6_E2M3)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP6_E2M3>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
-                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mxr_decode_kernel<GQ_MX_FP6_E3M2>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
-                           user_stride_bytes, R, out, plain ? 1 : 0, signs_of(b));
-    GQL_CHECK_LAUNCH("gq_mxr_decode_sum_batched");
-    return GQ_OK;
+    return gqx::decode_sum_batched<gqx::TT_F32>("gq_mxr_decode_sum_batched", b, gathered, user_stride_bytes, R, out, plain, stream);
+}
+
+// the same launches over bf16 sources, `out` and dense-copy sources (include/gq_mxr.h, TENSOR-SIDE TYPE); the wire is the f32 twin's
+GQXR_API int gq_mxr_compress_batched_bf16(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
+                                          uint16_t *out, void *stream) {
+    return gqx::compress_batched<gqx::TT_BF16>("gq_mxr_compress_batched_bf16", b, wire, random_mode, r, seed, ef_scale, out, stream);
+}
+
+GQXR_API int gq_mxr_decode_sum_batched_bf16(const gq_mxr_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, uint16_t *out,
+                                            int plain, void *stream) {
+    return gqx::decode_sum_batched<gqx::TT_BF16>("gq_mxr_decode_sum_batched_bf16", b, gathered, user_stride_bytes, R, out, plain, stream);
 }

@@ -547,6 +547,7 @@ class _SparseCodec(object):
 
     GROUP = None
     _single = None
+    dtype = torch.float32      # of the gradients, and of what roundtrip / decode_mean return (MXCodec: float32 or bfloat16)
 
     def _wire_bytes(self):
         """Bytes of a wire of this tensor alone (a launch is handed a valid address also when the section is empty)."""
@@ -570,10 +571,10 @@ class _SparseCodec(object):
         _require_device(grad, name + (".encode_decode_into" if extra.get("out") is not None else ".encode_into"))
         flat = grad.contiguous().view(-1)
         ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt, **extra)
-        assert ok, name + ": the gradient must be a float32 tensor on the current device"
+        assert ok, name + ": the gradient must be a %s tensor on the current device" % (self.dtype,)
 
     def roundtrip(self, grad, salt, **extra):
-        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
+        out = torch.empty(self.numel, dtype=self.dtype, device=grad.device)
         tmp = torch.empty(self._wire_bytes(), dtype=torch.uint8, device=grad.device)
         self.encode_decode_into(grad, tmp, 0, salt, out, **extra)
         return out.view(self.shape)
@@ -585,7 +586,7 @@ class _SparseCodec(object):
         self._batched1(gathered.device).decode_into(gathered[:, off:off + self.nbytes], R, out, plain=plain)
 
     def decode_mean(self, gathered, off, R, plain=False):
-        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        out = torch.empty(self.numel, dtype=self.dtype, device=gathered.device)
         self._decode_rows(gathered, off, R, out, plain=plain)
         return out.view(self.shape)
 
@@ -686,12 +687,15 @@ class MXCodec(_SparseCodec):
     "device" -- the library's counter-based generator, a fresh seed per call (the multi-tensor launch keys its stream by the
     quantizer's { seed, step } words); "reference" -- torch.rand(numel) per tensor from the CPU generator, in parameter order,
     handed to the kernels as given draws; "keyed" draws like "device".
-    `r` (float32 [numel] on the device) hands a call its uniforms whatever the mode; `seed` pins the device generator's."""
+    `r` (float32 [numel] on the device) hands a call its uniforms whatever the mode; `seed` pins the device generator's.
+    dtype: torch.float32 or torch.bfloat16 -- what the gradients are and what every decode returns (include/gq_mx.h, TENSOR-SIDE
+    TYPE).  The wire and its bytes do not depend on it; error buffers are float32 either way."""
 
-    def __init__(self, compressor, numel, shape):
+    def __init__(self, compressor, numel, shape, dtype=torch.float32):
         self.c, self.numel, self.shape = compressor, numel, shape
         if numel < 1:
             raise ValueError("MXCodec: a tensor of %d elements" % numel)
+        self.set_dtype(dtype)
         self.format = native.MX_FORMATS[compressor.format]
         self.random = bool(compressor.random)
         self.nbytes = mx_section_bytes(numel, self.format)
@@ -711,8 +715,19 @@ class MXCodec(_SparseCodec):
             r = torch.rand(self.numel).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
         return (r, {0: 0}) if r is not None else None
 
-    def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None):
-        _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out)
+    def set_dtype(self, dtype):
+        """(the quantizers: a codec factory is not told the parameter's dtype)"""
+        if dtype not in native.MX_DTYPES:
+            raise TypeError("%s: the kernels take float32 or bfloat16 tensors, got %s" % (type(self).__name__, dtype))
+        self.dtype, self._single = dtype, None
+
+    def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None, err=None, ef_scale=None):
+        """err, ef_scale: error feedback in the same launch -- grad <- w = grad + ef_scale * err (narrowed where grad is bfloat16),
+        err <- w - decoded from the unrounded w.  err: float32, contiguous, of grad's size; grad must then be contiguous itself."""
+        if err is not None and not grad.is_contiguous():
+            raise ValueError("MXCodec: error feedback updates the gradient in place and needs a contiguous one")
+        _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out,
+                                 errs=[err.view(-1)] if err is not None else None, ef_scale=ef_scale)
 
 
 class MXRCodec(MXCodec):
@@ -720,8 +735,8 @@ class MXRCodec(MXCodec):
     tensor rotated in blocks of 256 by H * diag(signs) / 16; every decode ends with the inverse rotation, so the wire no longer
     carries the decoded tensor itself.  Every call is a one-tensor BatchedMXR."""
 
-    def __init__(self, compressor, numel, shape):
-        MXCodec.__init__(self, compressor, numel, shape)
+    def __init__(self, compressor, numel, shape, dtype=torch.float32):
+        MXCodec.__init__(self, compressor, numel, shape, dtype)
         self.signs = tuple(int(w) for w in compressor.rotate_signs)
 
 
@@ -738,6 +753,9 @@ class _BatchedBase(object):
     pinned H2D copy; a ring of pinned buffers keeps a copy in flight from being overwritten."""
 
     UPLOAD_RING = 8
+    # what a group's launches read and write: the gradients' (and the dense-copy sources') dtype -- `dtype`, as a set in `_dtypes`
+    # for the upload's check -- and the alignment of the dense-copy sources.  Error buffers are float32 in every group.
+    dtype, _dtypes, _dense_align = torch.float32, _F32_ONLY, 4
 
     def _setup(self, table, extra, device, slots, user_bytes, dense=None):
         """dense: [(byte offset in one user's wire, elements), ...] of the identity-compressed tensors this group's compress
@@ -788,7 +806,7 @@ class _BatchedBase(object):
         k = self._out_turn
         self._out_turn ^= 1
         if self._outs[k] is None or self._outs[k].device != device:
-            out = torch.empty(self.out_floats, dtype=torch.float32, device=device)
+            out = torch.empty(self.out_floats, dtype=self.dtype, device=device)
             self._outs[k] = out
             self._out_views[k] = [out[o:o + cd.numel].view(cd.shape) for o, cd in zip(self.out_off, self.codecs)]
             self._out_gen += 1
@@ -894,8 +912,8 @@ class _BatchedBase(object):
         # ride on the last upload's validation.  (map() over the C-level accessors: ~6 us for 76 tensors; a Python-level
         # list of (dtype, is_contiguous) tuples cost 20.)
         if (self.ready and ptrs == self._last_ptrs and eptrs == self._last_eptrs and dptrs == self._last_dptrs
-                and all(map(_IS_CONTIGUOUS, tensors)) and set(map(_DTYPE_OF, tensors)) == _F32_ONLY
-                and (dense is None or (all(map(_IS_CONTIGUOUS, dense)) and set(map(_DTYPE_OF, dense)) == _F32_ONLY))):
+                and all(map(_IS_CONTIGUOUS, tensors)) and set(map(_DTYPE_OF, tensors)) == self._dtypes
+                and (dense is None or (all(map(_IS_CONTIGUOUS, dense)) and set(map(_DTYPE_OF, dense)) == self._dtypes))):
             if not self._resets:
                 return True     # nothing but the table in this header, and the device copy still holds it
             self._dev.copy_(self._host[self._last_slot], non_blocking=True)     # unchanged since its last copy
@@ -904,10 +922,11 @@ class _BatchedBase(object):
         # (the same facts for a new set of pointers, from the C-level accessors: a Python loop over
         # `g.device != ... or g.dtype != ...` cost 40 us for 76 tensors, most of it building torch.device objects)
         dev_index = self.device.index if self.device.index is not None else torch._C._cuda_getDevice()
-        for ts, ps, al in ((tensors, ptrs, align), (errs or (), eptrs if errs is not None else (), align), (dense or (), dptrs or (), 4)):
+        for ts, ps, al, dts in ((tensors, ptrs, align, self._dtypes), (errs or (), eptrs if errs is not None else (), max(align, 4), _F32_ONLY),
+                                (dense or (), dptrs or (), self._dense_align, self._dtypes)):
             if not ts:
                 continue
-            if (not all(map(_IS_CONTIGUOUS, ts)) or set(map(_DTYPE_OF, ts)) != _F32_ONLY
+            if (not all(map(_IS_CONTIGUOUS, ts)) or set(map(_DTYPE_OF, ts)) != dts
                     or set(map(_GET_DEVICE, ts)) != {dev_index} or any(p % al for p in ps)):
                 return False
         if dense is not None and len(dense) != self.ndense:
@@ -1804,7 +1823,7 @@ class BatchedMX(_ItemGroup):
     record, they replay from a HIP graph (and draw afresh every step); "reference": the quantizer's draw plan (torch.rand(numel)
     per tensor, in parameter order) as given draws; "keyed" / a group without pairs: a fresh seed per call."""
 
-    align = 4
+    align = 4       # the class's default; every instance sets its own from its codecs' dtype (_set_dtype: 2 for bfloat16)
 
     @staticmethod
     def eligible(codec):
@@ -1812,16 +1831,26 @@ class BatchedMX(_ItemGroup):
 
     @staticmethod
     def group_key(codec):
-        return (codec.format, int(codec.random), codec._rng)
+        # (the dtype by name: the keys are sorted.  A model with float32 norms and bfloat16 weights gets two groups.)
+        return (codec.format, int(codec.random), codec._rng, str(codec.dtype))
+
+    def _set_dtype(self, dtype):
+        """The group's tensor-side type (include/gq_mx.h) from its codecs, in front of the layout: 2-byte aligned sources and
+        dense-copy sources and views on multiples of 8 elements in the output buffer for bfloat16, 4 and 4 for float32 -- either
+        way a view starts 16-byte aligned, where a lane's 8 elements are one (two) 16-byte stores."""
+        self.dtype, self._dtypes = dtype, {dtype}
+        self.align = self._dense_align = 2 if dtype == torch.bfloat16 else 4
+        self._out_pad = 16 // self.align
 
     def _layout(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         """The group's tables (host work only; the launch descriptor is __init__'s) -> (tensors, items)."""
         ns = [codecs[i].numel for i in idxs]
         first_draw = list(itertools.accumulate([0] + ns[:-1]))
         self._first_draw, self.ndraws = first_draw, sum(ns)
-        # an item is a run of elements (numel >= 1: never none); 16-byte aligned views in the output buffer: float4 stores
+        # an item is a run of elements (numel >= 1: never none); 16-byte aligned views in the output buffer: 16-byte stores
+        self._set_dtype(codecs[idxs[0]].dtype)
         return self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
-                                lambda cd: -(-cd.numel // native.MX_ITEM_ELEMS), {6: first_draw}, 4)
+                                lambda cd: -(-cd.numel // native.MX_ITEM_ELEMS), {6: first_draw}, self._out_pad)
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         nseg, item = self._layout(codecs, offsets, idxs, device, slots, user_bytes, dense)
@@ -1830,7 +1859,10 @@ class BatchedMX(_ItemGroup):
         self.counter = self.random and c0._rng == "device"      # the quantizer gives such a group its { seed, step } pairs
         self.reference_draws = self.random and c0._rng == "reference"
         self._r = None
-        self._batch = native.MXBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.format)
+        self._batch = self._descriptor(nseg, item)
+
+    def _descriptor(self, nseg, item):
+        return native.MXBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.format, self.dtype)
 
     def graphable(self):
         return not self.random or (self.counter and self.rng_pairs is not None)
@@ -1848,8 +1880,9 @@ class BatchedMX(_ItemGroup):
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False, out=None, seed=None):
-        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
-        feedback in the same launch (t += ef_scale*err before the rounding, err = t - decoded after it, both in place).
+        """Compress `tensors` into one user's wire; out (the group's dtype [out_floats]): also their dense decode.  With `errs`
+        (float32): error feedback in the same launch (t += ef_scale*err before the rounding, err = t - decoded after it, both in
+        place; a bfloat16 t is stored narrowed, err comes from the unrounded sum).
         draws (given uniforms, see _given_draws): required for gq_rng "reference", taken in any stochastic mode when handed in.
         seed: the device generator's seed for this call.  graph_header, table_current: see _choose_header; dense, rng_slot: see
         BatchedHSQ.encode."""
@@ -1892,14 +1925,9 @@ class BatchedMXR(BatchedMX):
     def group_key(codec):
         return BatchedMX.group_key(codec) + tuple(codec.signs)
 
-    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
-        nseg, item = self._layout(codecs, offsets, idxs, device, slots, user_bytes, dense)
-        c0 = self.codecs[0]
-        self.format, self.random, self.signs = c0.format, c0.random, c0.signs
-        self.counter = self.random and c0._rng == "device"      # the quantizer gives such a group its { seed, step } pairs
-        self.reference_draws = self.random and c0._rng == "reference"
-        self._r = None
-        self._batch = native.MXRBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.format, self.signs)
+    def _descriptor(self, nseg, item):
+        self.signs = self.codecs[0].signs
+        return native.MXRBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.format, self.signs, self.dtype)
 
 
 MXRCodec.GROUP = BatchedMXR

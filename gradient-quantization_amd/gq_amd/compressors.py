@@ -565,7 +565,8 @@ class MXCompressor(object):
     per element, unbiased under stochastic rounding, relative precision inside a block (include/gq_mx.h defines it to the bit).
     args.mx_format: 'fp4' (the default), 'fp6_e2m3', 'fp6_e3m2' or 'fp8' ('fp6' alone names no format); args.random: stochastic rounding (otherwise to nearest, ties to the even code); gq_rng: where
     the draws come from (MXCodec).  compress returns the decoded tensor -- the wire carries it exactly -- and decompress is the
-    identity, as for SignSGDCompressor.  HIP kernels only (libgq_mx.so): a float32 tensor on the device.
+    identity, as for SignSGDCompressor.  HIP kernels only (libgq_mx.so): a float32 or bfloat16 tensor on the device (a bfloat16
+    tensor is widened exactly, compressed to the same wire, and returned as bfloat16).
     args.mx_rotate: None / 'none' (the default) or 'hadamard' -- a randomized 256-point Hadamard rotation in front of the
     quantiser and its inverse behind the decode (include/gq_mxr.h, libgq_mxr.so): one large entry no longer sets the grid of its
     31 neighbours, at the same bits on the same wire.  args.mx_rotate_seed (default 1) gives the four sign words, outputs
@@ -605,16 +606,16 @@ class MXCompressor(object):
 
     def compress(self, vec):
         from .codecs import MXCodec, MXRCodec      # (codecs imports this module)
-        if vec.device.type != "cuda" or vec.dtype != torch.float32:
-            raise TypeError("MXCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), got %s on %s"
+        if vec.device.type != "cuda" or vec.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("MXCompressor: the kernels take float32 or bfloat16 tensors on the HIP device (there is no CPU path), got %s on %s"
                             % (vec.dtype, vec.device))
         n = vec.numel()
         if n == 0:
             return vec.clone()
         codecs = self.__dict__.setdefault("_codecs", {})
-        codec = codecs.get(n)
-        if codec is None:
-            codec = codecs[n] = (MXRCodec if self.rotate else MXCodec)(self, n, (n,))
+        codec = codecs.get((n, vec.dtype))
+        if codec is None:      # (a bfloat16 tensor comes back as bfloat16: include/gq_mx.h, TENSOR-SIDE TYPE)
+            codec = codecs[(n, vec.dtype)] = (MXRCodec if self.rotate else MXCodec)(self, n, (n,), vec.dtype)
         return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
 
     def decompress(self, signature):

@@ -177,6 +177,9 @@ def build_parser():
                         'decode (lower error on heavy-tailed gradients, the same bits per element; not in ring mode)')
     p.add_argument('--mx-rotate-seed', dest='mx_rotate_seed', type=int, default=1,
                    help='--mx-rotate hadamard: the seed of the four sign words (every rank must use the same)')
+    p.add_argument('--param-dtype', dest='param_dtype', type=str, default='float32', choices=['float32', 'bfloat16'],
+                   help='the dtype the model is cast to.  bfloat16 needs --quantizer mx: its kernels read bfloat16 gradients and write '
+                        'bfloat16 means in place (the wire is the float32 one); no other compressor takes them')
     p.add_argument('--seed', type=int, default=1)
     p.add_argument('--train-size', type=int, default=4096, help='synthetic samples per epoch')
     p.add_argument('--log-interval', type=int, default=8, help='iterations between JSON log lines')
@@ -203,8 +206,9 @@ def test(model, loss_func, test_data, test_batch_size):
     model.eval()
     test_loss, correct = 0.0, 0
     with torch.no_grad():
+        dtype = next(model.parameters()).dtype
         for data, target in test_data.batches(test_batch_size, 0, shuffle=False):
-            output = model(data)
+            output = model(data.to(dtype)).float()
             test_loss += loss_func(output, target).sum().item()
             pred = output.argmax(dim=1, keepdim=True)
             correct += pred.eq(target.view_as(pred)).sum().item()
@@ -238,8 +242,18 @@ def one_iter(model, loss_func, optimizer, quantizer, train_data, epoch, spans=No
     return torch.stack(losses).mean()
 
 
+def check_param_dtype(args):
+    """--param-dtype bfloat16 with a quantizer whose kernels take float32 only: refused before anything is built."""
+    dtype = getattr(args, "param_dtype", None) or "float32"
+    if dtype == "bfloat16" and args.quantizer != "mx":
+        raise ValueError("--param-dtype bfloat16 needs --quantizer mx: the %s compressor's kernels take float32 gradients only"
+                         % args.quantizer)
+    return {"float32": torch.float32, "bfloat16": torch.bfloat16}[dtype]
+
+
 def train(args, log=None):
     import torch.distributed as dist
+    param_dtype = check_param_dtype(args)
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank() if world > 1 else 0
     if args.no_cuda or not torch.cuda.is_available():
@@ -249,6 +263,8 @@ def train(args, log=None):
     torch.manual_seed(args.seed)
     num_classes = 10
     model = network_choices[args.network](num_classes=num_classes).to(device)
+    if param_dtype != torch.float32:
+        model = model.to(param_dtype)
     quantizer = Quantizer(quantizer_choices[args.quantizer], model.parameters(), args)
     # --momentum-correction: the velocity lives in the quantizer (per user, in front of the select); the optimizer adds none
     opt_momentum = args.momentum if getattr(args, "momentum_correction", None) is None else 0.0
@@ -281,6 +297,8 @@ def train(args, log=None):
         # (a last batch too short to give every user of EVERY rank a sample is dropped by the loader on all ranks alike:
         # the reference would average an empty batch, and ranks that disagreed would leave one another alone in a collective)
         for x, y in data.batches(args.batch_size * args.num_users, 1000 * args.seed + epoch, rank, world, min_share=args.num_users):
+            if param_dtype != torch.float32:
+                x = x.to(param_dtype)
             ub = x.shape[0] // args.num_users
             users = [(x[u * ub:(u + 1) * ub], y[u * ub:(u + 1) * ub]) for u in range(args.num_users - 1)]
             users.append((x[(args.num_users - 1) * ub:], y[(args.num_users - 1) * ub:]))
@@ -320,7 +338,12 @@ def train(args, log=None):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    try:
+        check_param_dtype(args)
+    except ValueError as e:
+        parser.error(str(e))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch.distributed as dist
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")

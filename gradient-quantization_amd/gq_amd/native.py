@@ -616,6 +616,7 @@ class _ItemBatch(_Tables):
     its ctypes struct (STRUCT), hands its scratch buffers to this constructor and has a compress of its own."""
 
     LIBRARY = STRUCT = None
+    dtype, _suffix = torch.float32, ""      # the type of `out` and the suffix of the entry points that take it (MXBatch: _MX_SUFFIX)
 
     def __init__(self, seg_table, item_seg, nseg, nitems, scratch=(), **sizes):
         """scratch: ((field of the struct, int32 / float tensor or None, its dtype), ...); sizes: further integer fields."""
@@ -628,7 +629,7 @@ class _ItemBatch(_Tables):
             if t is not None:
                 setattr(self.s, name, _dev_ptr(t, dtype, name).value)
         self.ref = ctypes.byref(self.s)
-        self._decode_name = self.LIBRARY.prefix + "decode_sum_batched"
+        self._decode_name = self.LIBRARY.prefix + "decode_sum_batched" + self._suffix
         self._decode = getattr(self.L, self._decode_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
@@ -640,7 +641,7 @@ class _ItemBatch(_Tables):
         assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
         stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
         rc = self._decode(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R),
-                          _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0), _stream())
+                          _dev_ptr(out, self.dtype, "out"), ctypes.c_int(1 if plain else 0), _stream())
         _check(rc, self._decode_name, self.LIBRARY)
 
 
@@ -961,13 +962,26 @@ class MaureyBatch(_ItemBatch):
 
 # ---- block-scaled small floats (MXFP4 / MXFP6 / MXFP8): libgq_mx.so (include/gq_mx.h) ---------------------------------------------------
 MX_ABI_VERSION = 2
-MX_EXPORTS = ["gq_mx_abi_version", "gq_mx_last_error", "gq_mx_compress_batched", "gq_mx_decode_sum_batched"]
+MX_EXPORTS = ["gq_mx_abi_version", "gq_mx_last_error", "gq_mx_compress_batched", "gq_mx_decode_sum_batched",
+              "gq_mx_compress_batched_bf16", "gq_mx_decode_sum_batched_bf16"]
 MX_BLOCK = 32               # GQ_MX_BLOCK: elements that share a scale byte
 MX_ITEM_ELEMS = 4096        # GQ_MX_ITEM_ELEMS: elements per item
 MX_FP4, MX_FP8 = 0, 1       # GQ_MX_FP4 / GQ_MX_FP8
 MX_FP6_E2M3, MX_FP6_E3M2 = 0x23, 0x32      # GQ_MX_FP6_E2M3 / GQ_MX_FP6_E3M2: exponent bits, mantissa bits as hex digits
 MX_FORMATS = {"fp4": MX_FP4, "fp8": MX_FP8, "fp6_e2m3": MX_FP6_E2M3, "fp6_e3m2": MX_FP6_E3M2}
 MX_CODE_BITS = {MX_FP4: 4, MX_FP8: 8, MX_FP6_E2M3: 6, MX_FP6_E3M2: 6}
+# the tensor-side element types (include/gq_mx.h): the dtype of the sources, of both launches' `out` and of the dense-copy sources
+# -> the suffix of the entry points that serve it.  The ABI number did not move when the bf16 entry points came: a library from
+# before them fails at the loader's accessor check (MX_EXPORTS / MXR_EXPORTS list them).
+_MX_SUFFIX = {torch.float32: "", torch.bfloat16: "_bf16"}
+MX_DTYPES = tuple(_MX_SUFFIX)
+
+
+def _mx_suffix(dtype, who):
+    try:
+        return _MX_SUFFIX[dtype]
+    except KeyError:
+        raise TypeError("%s: the kernels take float32 or bfloat16 tensors, got %s" % (who, dtype))
 
 MX_LIBRARY = Library("libgq_mx.so", "GQ_MX_LIB_PATH", "gq_mx_", MX_ABI_VERSION, MX_EXPORTS)
 MX_LIB_PATH = MX_LIBRARY.path
@@ -989,28 +1003,33 @@ class MXBatch(_ItemBatch):
 
     LIBRARY, STRUCT = MX_LIBRARY, _MXBatchStruct
 
-    def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4):
+    def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4, dtype=torch.float32):
+        """dtype: torch.float32 or torch.bfloat16 -- the tensor-side type (sources, `out`, dense-copy sources); it selects the entry points."""
+        self.dtype, self._suffix = dtype, _mx_suffix(dtype, "MXBatch")
         _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt))
+        self._compress_name = "gq_mx_compress_batched" + self._suffix
+        self._compress = getattr(self.L, self._compress_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
-        return type(self)(seg_table, item_seg, nseg, nitems, self.s.format)
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.dtype)
 
     def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
         """random_mode: RANDOM_OFF (nearest, ties to even), RANDOM_GIVEN (r: float32, element i of tensor s reads
         r[first draw + i]), RANDOM_DEVICE (seed) or RANDOM_DEVICE_COUNTER (seed = the address of a { seed, step } pair).
-        out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers)."""
-        rc = self.L.gq_mx_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
-                                           _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
-                                           ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                           ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                           _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_mx_compress_batched", MX_LIBRARY)
+        out: the dense decoded tensors (the batch's dtype, at the table's out offsets); ef_scale given: error feedback in the same
+        launch (seg_table[:, 7] = error buffers, float32 whatever the dtype)."""
+        rc = self._compress(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
+                            _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
+                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                            _dev_ptr(out, self.dtype, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, self._compress_name, MX_LIBRARY)
 
 
 # ---- the same behind a randomized Hadamard rotation: libgq_mxr.so (include/gq_mxr.h) ----------------------------------------------
 MXR_ABI_VERSION = 2
-MXR_EXPORTS = ["gq_mxr_abi_version", "gq_mxr_last_error", "gq_mxr_compress_batched", "gq_mxr_decode_sum_batched"]
+MXR_EXPORTS = ["gq_mxr_abi_version", "gq_mxr_last_error", "gq_mxr_compress_batched", "gq_mxr_decode_sum_batched",
+               "gq_mxr_compress_batched_bf16", "gq_mxr_decode_sum_batched_bf16"]
 MXR_BLOCK = 256             # GQ_MXR_BLOCK: elements of a rotation block
 
 MXR_LIBRARY = Library("libgq_mxr.so", "GQ_MXR_LIB_PATH", "gq_mxr_", MXR_ABI_VERSION, MXR_EXPORTS)
@@ -1031,23 +1050,26 @@ class MXRBatch(_ItemBatch):
 
     LIBRARY, STRUCT = MXR_LIBRARY, _MXRBatchStruct
 
-    def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4, signs=(0, 0, 0, 0)):
+    def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4, signs=(0, 0, 0, 0), dtype=torch.float32):
         signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
         assert len(signs) == 4
+        self.dtype, self._suffix = dtype, _mx_suffix(dtype, "MXRBatch")
         _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt), signs=(ctypes.c_uint64 * 4)(*signs))
         self.signs = signs
+        self._compress_name = "gq_mxr_compress_batched" + self._suffix
+        self._compress = getattr(self.L, self._compress_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
-        return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.signs)
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.signs, self.dtype)
 
     def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
         """MXBatch.compress; out and the residual of error feedback are inverse-rotated (include/gq_mxr.h)."""
-        rc = self.L.gq_mxr_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
-                                            _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
-                                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_mxr_compress_batched", MXR_LIBRARY)
+        rc = self._compress(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
+                            _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
+                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                            _dev_ptr(out, self.dtype, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, self._compress_name, MXR_LIBRARY)
 
 
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------

@@ -193,10 +193,17 @@ class PSQuantizer(object):
             self.codecs.append(factory(comp, param_size, param.shape))
             if self.aggregate_fma and isinstance(self.codecs[-1], HSQCodec):
                 self.codecs[-1].fma = True
+            # A bfloat16 parameter (MXCompressor only: include/gq_mx.h, TENSOR-SIDE TYPE): its codec reads bfloat16 gradients and
+            # returns bfloat16 means; its residuals stay float32, whatever the parameter's dtype -- the launches compute them
+            # from the unrounded sum.
+            mx = isinstance(self.codecs[-1], MXCodec)
+            if mx and param.dtype != torch.float32:
+                self.codecs[-1].set_dtype(param.dtype)
+            err_like = (lambda: torch.zeros(param.shape, dtype=torch.float32, device=param.device)) if mx else (lambda: torch.zeros_like(param))
             if self.error_feedback:
-                param.error = [torch.zeros_like(param) for _ in range(args.num_users)]
+                param.error = [err_like() for _ in range(args.num_users)]
             if self.error_feedback and self.two_phase:
-                param.server_error = torch.zeros_like(param)
+                param.server_error = err_like()
             if self.dgc_m is not None and isinstance(comp, TopKSparsificationCompressor):
                 param.dgc_u = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
                 param.dgc_v = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
@@ -215,6 +222,15 @@ class PSQuantizer(object):
             off += self.codecs[i].nbytes
         self.dense_bytes = off - self.dense_off
         self._dense_mean, self._dense_views, self._dense_turn = [None, None], [None, None], 0
+        # The identity-compressed tensors travel as float32 in the wire whatever their parameters' dtype; the mean of a parameter
+        # that is not float32 is narrowed by ONE torch cast of the whole region on the device (_dense_cast: a few thousand
+        # elements, round to nearest even, capturable), and its view is a view of that copy.
+        self._dtypes = [p.dtype for p in self.parameters]
+        self._all_f32 = set(self._dtypes) <= _F32_ONLY
+        dense_dtypes = set(self._dtypes[i] for i in self.dense_idx)
+        self._dense_dtype = next(iter(dense_dtypes)) if len(dense_dtypes) == 1 else None      # (None: none, or mixed -- no launch copies them)
+        self._dense_cast_dtypes = sorted(dense_dtypes - _F32_ONLY, key=str)
+        self._dense_cast = [None, None]
         self._dense_in = {}                 # (wire pointer, slot) -> views of the slot's dense region
         self.user_bytes = _up(off)          # one user's payload (all tensors)
         # tensors served by multi-tensor kernels: (class, parameter indices), built at the first record()
@@ -475,6 +491,7 @@ class PSQuantizer(object):
         """Can _replay_known_step ever apply to this quantizer?  (False: decided for good; None: not yet -- the groups are built by
         the first record.)"""
         if (_HOST is None or not hasattr(_HOST, "scan_key") or not self.use_graphs or not self._fuse_steps or self.error_feedback
+                or not self._all_f32      # (the helper's key vouches for plain float32 gradients only: record()'s long way checks the others)
                 or self.dgc_m is not None or self.two_phase or self._draw_total or self.capacity != 1 or not self._groups):
             self._fast_ok = False
             return False
@@ -549,7 +566,10 @@ class PSQuantizer(object):
                 state = tuple(t.data_ptr() for p in self.parameters if hasattr(p, "dgc_u") for t in (p.dgc_u[user], p.dgc_v[user]))
                 graph_key += (state,)
                 generic_key += (state,)
-            plain_f32 = scan[2] if scan is not None else (all(map(_IS_CONTIGUOUS, all_grads)) and set(map(_DTYPE_OF, all_grads)) == _F32_ONLY)
+            if not self._all_f32:      # (every gradient contiguous and of its parameter's dtype: what the groups' uploads were checked with)
+                plain_f32 = all(map(_IS_CONTIGUOUS, all_grads)) and list(map(_DTYPE_OF, all_grads)) == self._dtypes
+            else:
+                plain_f32 = scan[2] if scan is not None else (all(map(_IS_CONTIGUOUS, all_grads)) and set(map(_DTYPE_OF, all_grads)) == _F32_ONLY)
             ent = self._rec_graphs.get(graph_key) if plain_f32 else None
             tied = ent is not None and ent[1] is not None
             if plain_f32 and not tied:
@@ -596,6 +616,13 @@ class PSQuantizer(object):
             grad = param.grad.data
             if self.dgc_m is not None and isinstance(codec, TopKCodec):
                 self._record_dgc_single(i, grad, wire, user)
+            elif self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
+                # a bfloat16 gradient: the sum and the residual in the compress launch itself, which keeps them unrounded (a torch
+                # add_ would narrow grad + scale*error before the residual is taken)
+                flat = grad if grad.is_contiguous() else grad.contiguous()
+                codec.encode_into(flat, wire, off, salt, err=param.error[user], ef_scale=scale, **self._slice(draws, i))
+                if flat is not grad:
+                    grad.copy_(flat)
             elif self.error_feedback:
                 # ps_quantizer.py:35-39:  grad += scale*error ; error = grad - decoded
                 if grad.device.type == "cuda" and grad.is_contiguous() and grad.dtype == torch.float32:
@@ -654,8 +681,10 @@ class PSQuantizer(object):
         that decodes before it has encoded anything): dense copy table, draws' { seed, step } pairs, aggregate form."""
         cls, idxs = grp[0], grp[1]
         # the first group's compress launch also copies the identity-compressed tensors into the wire
+        # (a launch reads them in its own tensors' dtype: dense tensors of another dtype, or of several, keep the torch copy)
         dense = ([(self.offsets[i], self.codecs[i].numel) for i in self.dense_idx]
-                 if (grp is self._groups[0] and len(self.dense_idx) >= 2) else None)
+                 if (grp is self._groups[0] and len(self.dense_idx) >= 2
+                     and self._dense_dtype == getattr(self.codecs[idxs[0]], "dtype", torch.float32)) else None)
         obj = grp[2] = cls(self.codecs, self.offsets, idxs, dev, self.capacity, self.user_bytes, dense=dense)
         obj.fma = bool(self.aggregate_fma and cls is BatchedHSQ)
         if dev.type == "cuda":
@@ -853,12 +882,13 @@ class PSQuantizer(object):
             self._dense_turn ^= 1
             if self._dense_mean[k] is None or self._dense_mean[k].device != rows.device:
                 mean = torch.empty(rows.shape[1], dtype=torch.float32, device=rows.device)
+                cast = {dt: torch.empty(rows.shape[1], dtype=dt, device=rows.device) for dt in self._dense_cast_dtypes}
                 views, o = [], 0
                 for i in self.dense_idx:
                     n = self.codecs[i].numel
-                    views.append(mean[o:o + n].view(self.codecs[i].shape))
+                    views.append(cast.get(self._dtypes[i], mean)[o:o + n].view(self.codecs[i].shape))
                     o += n
-                self._dense_mean[k], self._dense_views[k] = mean, views
+                self._dense_mean[k], self._dense_views[k], self._dense_cast[k] = mean, views, cast
                 self._dense_gen += 1
             dense_job = (rows, k)
         tail, tail_group = None, -1
@@ -938,6 +968,8 @@ class PSQuantizer(object):
                 step_rng = False
             else:
                 torch.mean(rows, dim=0, out=self._dense_mean[k])   # stack().mean(0) of the reference, all at once
+            for dst in self._dense_cast[k].values():      # (parameters that are not float32: the mean narrowed, one cast)
+                dst.copy_(self._dense_mean[k])
             sources.append((self.dense_idx, self._dense_views[k]))
         if step_rng:        # no identity-compressed tensors to average (or the ring's plain hop): a launch of its own
             native.rng_step(self._rng_state, reset=resets.pop(0) if resets else None)
@@ -962,13 +994,24 @@ class PSQuantizer(object):
         for idxs, vs in sources:
             for i, v in zip(idxs, vs):
                 done[i] = v
+        if not self._all_f32:      # a per-tensor decode that came back as float32 (a lone identity-compressed tensor): narrowed here
+            for i in single:
+                if done[i].dtype != self._dtypes[i]:
+                    done[i] = done[i].to(self._dtypes[i])
         if two_phase:
             for i in single:
                 # ps_quantizer.py:52-61 -- identical on every rank (salt 0, the ranks' shared seed stream)
                 param, codec, g = self.parameters[i], self.codecs[i], done[i]
                 kw = self._slice(draws2, i)
                 with shared_seeds(self._second_phase_seed):
-                    if self.error_feedback:
+                    if self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
+                        # (a bfloat16 mean: sum and residual inside the launch, unrounded -- see record())
+                        g = g.contiguous()
+                        out = torch.empty(codec.numel, dtype=codec.dtype, device=g.device)
+                        tmp = torch.empty(codec._wire_bytes(), dtype=torch.uint8, device=g.device)
+                        codec.encode_into(g, tmp, 0, 0, out=out, err=param.server_error, ef_scale=1.0, **kw)
+                        g = out.view(codec.shape)
+                    elif self.error_feedback:
                         g = g + param.server_error
                         decoded = codec.roundtrip(g, 0, **kw)
                         param.server_error = g - decoded

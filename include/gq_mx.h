@@ -66,6 +66,32 @@
  *              which ldexp gives as +-inf (a block whose maximum is within half a grid step of 2^128 can round up to it).
  *              Scale byte 0xFF: the NaN 0x7fc00000 for every element of the block, whatever its codes are.  A decode reads
  *              the FP8 magnitude code 127, which no compress writes, by the same formula (480 * 2^e).
+ *
+ * TENSOR-SIDE TYPE  T is float (the entry points above all) or bf16 (the *_bf16 entry points; an f16 could follow, none exists).  T is
+ *              the type of four things: the sources, the compress launch's `out`, the decode-mean's `out` and the dense-copy
+ *              sources.  Error buffers, given draws r and the wire stay f32, f32 and bytes: THE WIRE DOES NOT CHANGE -- the payload
+ *              of a bf16 source is, byte for byte, the payload of the f32 launch on the widened tensor, and a bf16 rank and an
+ *              f32 rank exchange payloads freely.
+ *     widen(h)   the f32 with the bits h << 16: exact, NaNs and signed zeros included.  Everything above that is defined on w
+ *              (block exponent, element code, draws, error feedback w = g + ef_scale * err) is computed on widened values,
+ *              unchanged.
+ *     narrow(x)  round to nearest even onto bf16, in integers on b = bits(x):
+ *                  (b & 0x7fffffff) > 0x7f800000 (a NaN):  0x7FC0
+ *                  otherwise:                              (b + 0x7FFF + ((b >> 16) & 1)) >> 16
+ *              The second rule carries into the exponent, reaches +-inf at the top and rounds f32 subnormals onto bf16's grid as
+ *              they are (what a CPU float32 -> bfloat16 cast of torch does).
+ *     narrow applies at every store of an f32 value into a T location: the compress launch's `out`, the source written back
+ *              under error feedback, the decode-mean's `out`.  Under error feedback the residual keeps full precision:
+ *              err = w - decoded from the UNROUNDED w; only the copy written back into the source is narrowed.  The decode-mean
+ *              computes its f32 result exactly as above and narrows once, at the store.
+ *     Exactness: every value ONE payload decodes to has a significand of at most 2 (FP4) or 4 (both FP6, E4M3) bits, which fits
+ *              bf16's 8: a plain decode is exact in bf16 unless the value has a bit below 2^-133 (bf16's smallest subnormal),
+ *              where bf16's subnormal grid rounds it -- possible only below 2^-130 (FP4: 2^-132), under the scale bytes 0 ... 6.
+ *              A mean of several payloads is rounded like any f32.
+ *     Alignment: T locations need the alignment of T only (2 bytes).  A lane's 8 elements are ONE 16-byte access where they are
+ *              16-byte aligned and scalar accesses otherwise -- the f32 rule, where they are two.  The segment table's out
+ *              offset counts elements of T.  The dense-copy table of a bf16 compress launch names bf16 sources (2-byte
+ *              aligned), which it widens into the wire's f32 dense region.
  */
 #ifndef GQ_MX_H
 #define GQ_MX_H
@@ -125,6 +151,15 @@ int gq_mx_compress_batched(const gq_mx_batch *b, uint8_t *wire, int random_mode,
  */
 int gq_mx_decode_sum_batched(const gq_mx_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
                              void *stream);
+
+/*
+ * The two launches over bf16 tensors (TENSOR-SIDE TYPE above): sources, `out` and dense-copy sources are bf16, every other
+ * argument, the wire and the refusals are the f32 twin's -- except that `out` may be 2-byte aligned.
+ */
+int gq_mx_compress_batched_bf16(const gq_mx_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
+                                uint16_t *out, void *stream);
+int gq_mx_decode_sum_batched_bf16(const gq_mx_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, uint16_t *out,
+                                  int plain, void *stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,13 @@
  * DECODE-MEAN  m = the value gq_mx_decode_sum_batched defines (+0 start, payloads ascending, a true division by (float)R; plain
  *              with R == 1 leaves d_0 as it is); `out` receives the inverse transform of m -- the mean first, then ONE inverse
  *              rotation, whatever R is.
+ *
+ * TENSOR-SIDE TYPE  gq_mx.h's, for the *_bf16 entry points: bf16 sources are widened (exact) in front of the forward transform, and
+ *              everything above runs on the widened values.  narrow (gq_mx.h, to the bit) applies at the same three stores, and
+ *              what it rounds is the INVERSE TRANSFORM's f32 output: D into the compress launch's `out`, the inverse transform
+ *              of m into the decode-mean's `out`; under error feedback w goes back into the source narrowed and err = w - D
+ *              from the unrounded w.  The inverse transform's output is a sum of 256 terms and fits no 8-bit significand in
+ *              general: with rotation a plain decode is rounded like any f32.  The wire is the f32 twin's, byte for byte.
  */
 #ifndef GQ_MXR_H
 #define GQ_MXR_H
@@ -83,6 +90,12 @@ int gq_mxr_compress_batched(const gq_mxr_batch *b, uint8_t *wire, int random_mod
 /* gq_mx_decode_sum_batched, then one inverse rotation of the mean (arguments and refusals as there). */
 int gq_mxr_decode_sum_batched(const gq_mxr_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
                               void *stream);
+
+/* The two launches over bf16 tensors (TENSOR-SIDE TYPE above; arguments and refusals as the f32 twins', `out` 2-byte aligned). */
+int gq_mxr_compress_batched_bf16(const gq_mxr_batch *b, uint8_t *wire, int random_mode, const float *r, uint64_t seed, float ef_scale,
+                                 uint16_t *out, void *stream);
+int gq_mxr_decode_sum_batched_bf16(const gq_mxr_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, uint16_t *out,
+                                   int plain, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """Time the microscaling kernels (libgq_mx.so) on one MI355X, next to signSGD and QSGD in the same process:
 
-    python tools/mx_time.py [--out FILE] [--parent-lib libgq_mx.so]      (default: profiles/mx_time.jsonl)
+    python tools/mx_time.py [--out FILE] [--parent-lib libgq_mx.so] [--dtype bf16]      (default: profiles/mx_time.jsonl)
 
 Rows (one JSON line each):
   resnet50_step   PSQuantizer record + apply over the ResNet-50 parameter list (tests/golden/resnet50_cifar_shapes.json), one
@@ -16,6 +16,12 @@ Rows (one JSON line each):
                   --parent-lib: an older build of libgq_mx.so (say the parent commit's) loaded next to the in-tree one, its fp4 /
                   fp8 launches alternated with the in-tree ones in the same rounds (parent_mx_*); *_over_parent_fp8: a launch of
                   this build over the parent's fp8 launch of the same kind, *_over_parent: over the parent's same launch.
+  bf16_25m        (--dtype bf16: this row alone is measured, and replaces the row of that case in FILE, whose other rows stay) one
+                  25 M-element tensor, fp4 and fp8: the four launches -- compress stochastic, compress nearest, decode-mean R = 1 and
+                  R = 8 -- over bf16 tensors, over float32 tensors, and (--parent-lib) the parent build's float32 launches, alternated
+                  round by round in this process; eager and as ten launches replayed from one HIP graph.  *_bf16_over_parent and
+                  *_f32_over_parent: the ratio to the PARENT's float32 launch of the same format and kind (graphed; *_eager_* the
+                  eager ones); `bar` is 1.03 and `missed` lists every ratio above it.
 Times: HIP events around a window of back-to-back calls after untimed ones, median of the windows, microseconds per call; the
 paths of a row are alternated round by round and the minimum over the rounds is reported next to every round."""
 import argparse
@@ -115,15 +121,100 @@ def library(path):
     if path is None:
         yield
         return
+    with other_library(path, native.MXBatch, "libgq_mx.so", "gq_mx_", native.MX_EXPORTS):
+        yield
+
+
+@contextlib.contextmanager
+def other_library(path, batch_cls, name, prefix, exports):
+    """library() for either descriptor class (native.MXBatch / native.MXRBatch).  An older build has no bf16 entry points: only
+    the float32 ones are asked of it (the loader would otherwise refuse it), and no environment variable overrides its path --
+    the one difference to what library() did before the bf16 entry points were listed in native.MX_EXPORTS."""
     probe = ctypes.CDLL(path)
-    probe.gq_mx_abi_version.restype = ctypes.c_int
-    other = native.Library("libgq_mx.so", "GQ_MX_LIB_PATH", "gq_mx_", probe.gq_mx_abi_version(), native.MX_EXPORTS)
+    version = getattr(probe, prefix + "abi_version")
+    version.restype = ctypes.c_int
+    other = native.Library(name, "GQ_NO_SUCH_VARIABLE", prefix, version(), [e for e in exports if not e.endswith("_bf16")])
     other.path = path
-    saved, native.MXBatch.LIBRARY = native.MXBatch.LIBRARY, other      # (a descriptor takes its library when it is built)
+    saved, batch_cls.LIBRARY = batch_cls.LIBRARY, other      # (a descriptor takes its library when it is built)
     try:
         yield
     finally:
-        native.MXBatch.LIBRARY = saved
+        batch_cls.LIBRARY = saved
+
+
+BAR = 1.03      # a launch of this build over the parent's float32 launch: the spread between identical instruction streams in one run
+
+
+def dtype_rows(dev, parent_lib=None, rotated=False, n=25_000_000):
+    """The bf16_25m row (see the module's text); rotated: libgq_mxr.so's launches (tools/mxr_time.py)."""
+    from gq_amd.codecs import BatchedMXR, MXRCodec
+    torch.manual_seed(1)
+    t16 = torch.randn(n, device=dev).to(torch.bfloat16)
+    t32 = t16.float()      # the same values: the wire of the two is the same, byte for byte
+    group_cls, codec_cls, batch_cls = (BatchedMXR, MXRCodec, native.MXRBatch) if rotated else (BatchedMX, MXCodec, native.MXBatch)
+    lib_name, prefix, exports = (("libgq_mxr.so", "gq_mxr_", native.MXR_EXPORTS) if rotated else ("libgq_mx.so", "gq_mx_", native.MX_EXPORTS))
+    groups, wires, src = {}, {}, {}
+    for fmt in ("fp4", "fp8"):
+        for random in (1, 0):
+            comp = MXCompressor(n, (n,), _args(mx_format=fmt, random=random, mx_rotate="hadamard" if rotated else "none"))
+            for tag, dt, lib in (("bf16", torch.bfloat16, None), ("f32", torch.float32, None), ("parent_f32", torch.float32, parent_lib)):
+                if tag == "parent_f32" and not parent_lib:
+                    continue
+                name = "%s_%s_%s" % (fmt, "stochastic" if random else "nearest", tag)
+                cd = codec_cls(comp, n, (n,), dt)
+                with (other_library(lib, batch_cls, lib_name, prefix, exports) if lib else contextlib.nullcontext()):
+                    g = group_cls([cd], [0], [0], dev, 1, cd.nbytes)
+                wire = torch.zeros((8, cd.nbytes), dtype=torch.uint8, device=dev)
+                src[name] = t16 if dt == torch.bfloat16 else t32
+                assert g.encode([src[name]], wire[0], 0, 0, seed=7)
+                for r in range(1, 8):
+                    wire[r].copy_(wire[0])
+                groups[name], wires[name] = g, wire
+    for fmt in ("fp4", "fp8"):      # (the claim the ratios rest on: the same bytes leave all three)
+        for mode in ("stochastic", "nearest"):
+            same = [wires["%s_%s_%s" % (fmt, mode, tag)][0] for tag in ("bf16", "f32", "parent_f32") if "%s_%s_%s" % (fmt, mode, tag) in wires]
+            assert all(torch.equal(same[0], w) for w in same[1:]), "the wires of %s %s differ" % (fmt, mode)
+    times, outs = {}, {}
+    for rnd in range(3):
+        for name, g in groups.items():
+            w, t = wires[name], src[name]
+            times.setdefault(name + "_compress_eager", []).append(timed(lambda: g.encode([t], w[0], 0, 0)))
+            times.setdefault(name + "_compress", []).append(graphed(lambda: g.encode([t], w[0], 0, 0)))
+            if "_stochastic_" in name:
+                for R in (1, 8):
+                    key = name.replace("_stochastic_", "_") + "_decode_mean_R%d" % R
+                    out = outs.setdefault(name, torch.empty(g.out_floats, dtype=g.dtype, device=dev))
+                    times.setdefault(key + "_eager", []).append(timed(lambda: g._batch.decode(w[:R], R, out)))
+                    times.setdefault(key, []).append(graphed(lambda: g._batch.decode(w[:R], R, out)))
+    row = {"case": "bf16_25m", "library": lib_name, "elements": n, "bar": BAR, "parent_lib": bool(parent_lib)}
+    for key, ts in times.items():
+        row[key + "_us_rounds"] = [round(x, 2) for x in ts]
+        row[key + "_us"] = round(min(ts), 2)
+    missed = []
+    if parent_lib:
+        for fmt in ("fp4", "fp8"):
+            for kind in ("stochastic_%s_compress", "nearest_%s_compress", "%s_decode_mean_R1", "%s_decode_mean_R8"):
+                for eager in ("", "_eager"):
+                    base = row["%s_%s%s_us" % (fmt, kind % "parent_f32", eager)]
+                    for tag in ("bf16", "f32"):
+                        field = "%s_%s%s_over_parent" % (fmt, kind % tag, eager)
+                        row[field] = round(row["%s_%s%s_us" % (fmt, kind % tag, eager)] / base, 3)
+                        if not eager and row[field] > BAR:
+                            missed.append(field)
+        row["missed"] = missed
+    return [row]
+
+
+def write_rows(path, rows, replace_case=None):
+    """rows as JSON lines into `path`; replace_case: the file's other rows stay, only the rows of that case are replaced."""
+    lines = [json.dumps(r) for r in rows]
+    print("\n".join(lines))
+    kept = []
+    if replace_case is not None and os.path.exists(path):
+        with open(path) as f:
+            kept = [ln.rstrip("\n") for ln in f if ln.strip() and json.loads(ln).get("case") != replace_case]
+    with open(path, "w") as f:
+        f.write("\n".join(kept + lines) + "\n")
 
 
 def single_rows(dev, n=25_000_000, parent_lib=None):
@@ -205,13 +296,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx_time.jsonl"))
     ap.add_argument("--parent-lib", default=None, help="an older libgq_mx.so to time next to the in-tree one (parent_mx_* fields)")
+    ap.add_argument("--dtype", default=None, choices=["bf16"], help="the bf16_25m row alone: bf16 launches next to the float32 ones")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    rows = single_rows(dev, parent_lib=a.parent_lib) + resnet50_rows(dev)
-    lines = [json.dumps(r) for r in rows]
-    print("\n".join(lines))
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    if a.dtype == "bf16":
+        write_rows(a.out, dtype_rows(dev, a.parent_lib), replace_case="bf16_25m")
+        return
+    write_rows(a.out, single_rows(dev, parent_lib=a.parent_lib) + resnet50_rows(dev))
 
 
 if __name__ == "__main__":

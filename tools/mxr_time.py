@@ -1,6 +1,6 @@
 """Time the rotated microscaling kernels (libgq_mxr.so) against the plain ones (libgq_mx.so) on one MI355X, in one process:
 
-    python tools/mxr_time.py [--out FILE]      (default: profiles/mxr_time.jsonl)
+    python tools/mxr_time.py [--out FILE] [--dtype bf16 [--parent-lib libgq_mxr.so]]      (default: profiles/mxr_time.jsonl)
 
 Rows (one JSON line each):
   resnet50_step   PSQuantizer record + apply over the ResNet-50 parameter list (tests/golden/resnet50_cifar_shapes.json), one
@@ -10,6 +10,9 @@ Rows (one JSON line each):
                   fp4 / fp6_e2m3 / fp6_e3m2 / fp8, stochastic (device generator) and nearest, eager and as ten launches replayed from one HIP graph;
                   the decode-mean at R = 1 and R = 8.  *_over_plain: the ratio to the plain MX launch of the same run -- the
                   plain launch is the yardstick, not this code.
+  bf16_25m        (--dtype bf16) tools/mx_time.py's row of that name over libgq_mxr.so: the rotated launches over bf16 tensors, over
+                  float32 tensors and (--parent-lib, an older libgq_mxr.so) the parent's float32 launches; only this row is measured,
+                  and it replaces the row of that case in FILE.
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -23,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gradient-quantization_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from mx_time import FORMATS, _args, graphed, timed  # noqa: E402
+from mx_time import FORMATS, _args, dtype_rows, graphed, timed, write_rows  # noqa: E402
 from gq_amd.codecs import BatchedMX, BatchedMXR, MXCodec, MXRCodec  # noqa: E402
 from gq_amd.compressors import MXCompressor  # noqa: E402
 from gq_amd.quantizers import PSQuantizer  # noqa: E402
@@ -115,13 +118,14 @@ def single_rows(dev, n=25_000_000):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mxr_time.jsonl"))
+    ap.add_argument("--parent-lib", default=None, help="--dtype bf16: an older libgq_mxr.so whose float32 launches are the yardstick")
+    ap.add_argument("--dtype", default=None, choices=["bf16"], help="the bf16_25m row alone: bf16 launches next to the float32 ones")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    rows = single_rows(dev) + resnet50_rows(dev)
-    lines = [json.dumps(r) for r in rows]
-    print("\n".join(lines))
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    if a.dtype == "bf16":
+        write_rows(a.out, dtype_rows(dev, a.parent_lib, rotated=True), replace_case="bf16_25m")
+        return
+    write_rows(a.out, single_rows(dev) + resnet50_rows(dev))
 
 
 if __name__ == "__main__":
