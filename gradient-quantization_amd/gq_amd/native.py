@@ -1005,9 +1005,13 @@ class MXBatch(_ItemBatch):
 
     def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4, dtype=torch.float32):
         """dtype: torch.float32 or torch.bfloat16 -- the tensor-side type (sources, `out`, dense-copy sources); it selects the entry points."""
-        self.dtype, self._suffix = dtype, _mx_suffix(dtype, "MXBatch")
-        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt))
-        self._compress_name = "gq_mx_compress_batched" + self._suffix
+        self._bind(seg_table, item_seg, nseg, nitems, fmt, dtype)
+
+    def _bind(self, seg_table, item_seg, nseg, nitems, fmt, dtype, **fields):
+        """fields: what a subclass's descriptor holds behind gq_mx_batch's own fields."""
+        self.dtype, self._suffix = dtype, _mx_suffix(dtype, type(self).__name__)
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt), **fields)
+        self._compress_name = self.LIBRARY.prefix + "compress_batched" + self._suffix
         self._compress = getattr(self.L, self._compress_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
@@ -1023,7 +1027,7 @@ class MXBatch(_ItemBatch):
                             ctypes.c_uint64(seed & (2 ** 64 - 1)),
                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
                             _dev_ptr(out, self.dtype, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, self._compress_name, MX_LIBRARY)
+        _check(rc, self._compress_name, self.LIBRARY)
 
 
 # ---- the same behind a randomized Hadamard rotation: libgq_mxr.so (include/gq_mxr.h) ----------------------------------------------
@@ -1044,8 +1048,9 @@ class _MXRBatchStruct(ctypes.Structure):      # gq_mxr_batch (include/gq_mxr.h):
     _fields_ = _MXBatchStruct._fields_ + [("signs", ctypes.c_uint64 * 4)]
 
 
-class MXRBatch(_ItemBatch):
-    """The two launches of libgq_mxr.so: MXBatch's calls over tensors rotated in blocks of 256 by H * diag(signs) / 16.
+class MXRBatch(MXBatch):
+    """The two launches of libgq_mxr.so: MXBatch's calls over tensors rotated in blocks of 256 by H * diag(signs) / 16 (compress:
+    out and the residual of error feedback are inverse-rotated; include/gq_mxr.h).
     signs: the four 64-bit sign words (element j of a rotation block owns bit j & 63 of word j >> 6)."""
 
     LIBRARY, STRUCT = MXR_LIBRARY, _MXRBatchStruct
@@ -1053,23 +1058,11 @@ class MXRBatch(_ItemBatch):
     def __init__(self, seg_table, item_seg, nseg, nitems, fmt=MX_FP4, signs=(0, 0, 0, 0), dtype=torch.float32):
         signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
         assert len(signs) == 4
-        self.dtype, self._suffix = dtype, _mx_suffix(dtype, "MXRBatch")
-        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt), signs=(ctypes.c_uint64 * 4)(*signs))
+        self._bind(seg_table, item_seg, nseg, nitems, fmt, dtype, signs=(ctypes.c_uint64 * 4)(*signs))
         self.signs = signs
-        self._compress_name = "gq_mxr_compress_batched" + self._suffix
-        self._compress = getattr(self.L, self._compress_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.signs, self.dtype)
-
-    def compress(self, wire, random_mode, seed=0, r=None, out=None, ef_scale=None):
-        """MXBatch.compress; out and the residual of error feedback are inverse-rotated (include/gq_mxr.h)."""
-        rc = self._compress(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
-                            _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
-                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                            _dev_ptr(out, self.dtype, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, self._compress_name, MXR_LIBRARY)
 
 
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------

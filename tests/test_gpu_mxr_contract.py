@@ -16,7 +16,10 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import mx_contract as mx  # noqa: E402
 import mxr_contract as mxr  # noqa: E402
+import mx6_contract as m6  # noqa: E402
+import mx_bf16_contract as bx  # noqa: E402
 import test_gpu_mx_contract as base  # noqa: E402  (the harness: compress, decode, _split)
+import test_gpu_z_mx_bf16_contract as zb  # noqa: E402  (the same harness over either tensor type and all four formats)
 
 pytestmark = pytest.mark.gpu
 
@@ -282,6 +285,46 @@ def test_launches_replay_from_a_graph_with_counter_draws(fmt):
         seen.append(res.wire.copy())
         pairs[0, 1] += 1
     assert not np.array_equal(seen[0], seen[1]), "two replays drew the same numbers"
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("fmt", bx.FMTS)
+def test_what_is_not_rotated_is_the_plain_librarys_bytes(fmt, dtype):
+    """The two libraries are two instantiations of one kernel body (csrc/mx_kernels.hpp), held against each other here with no
+    restatement in between.  A tensor shorter than a rotation block (n = 1, 31, 255, one tensor each) is `the tail as it is`:
+    libgq_mxr.so with the seeded sign words writes the wire, `out` and, under error feedback, w and err that libgq_mx.so writes,
+    byte for byte.  n = 256 + 255 has one rotated block: the scale bytes from block 8 on, the code bytes, `out`, w and err from
+    element 256 on agree likewise.  Nearest rounding and given draws, with and without error feedback; then the decode-mean of
+    the same payloads at R = 1 (plain and not) and R = 3."""
+    torch_dtype = torch.float32 if dtype == "f32" else torch.bfloat16
+    bits = {m6.FP4: 4, m6.FP8: 8}.get(fmt, 6)
+
+    def tail(res, n, nb_pad, k):
+        """What of a launch's results belongs to the elements from k on: scale bytes, code bytes, out, source, residual."""
+        sec = res.wire[:m6.section_bytes(n, fmt)]
+        parts = [sec[k // 32:nb_pad], sec[nb_pad + k * bits // 8:], res.out[k:n], res.src[0][k:]]
+        return parts + ([res.err[0][k:]] if res.err else [])
+
+    for n, k in ((1, 0), (31, 0), (255, 0), (mxr.RBLOCK + 255, mxr.RBLOCK)):
+        nb_pad = mx._up(-(-n // 32))
+        v = mxr.gradients(n, 1100 + n) if dtype == "f32" else bx.randn16(n, 1100 + n)
+        e = mxr.gradients(n, 1200 + n)
+        r = np.random.RandomState(n).rand(n).astype(f32)
+        payloads = []
+        for mode in ("off", "given"):
+            groups = {x: zb.make_group([n], fmt, dtype=torch_dtype, random=mode != "off", signs=mxr.SEEDED if x else None) for x in (False, True)}
+            for errs in (None, [e]):
+                plain, rot = (zb.compress(groups[x], [v], mode, r, errs=errs, s=0.5 if errs else None) for x in (False, True))
+                if k == 0:
+                    assert np.array_equal(plain.wire, rot.wire), "n = %d, %s, ef %s: the whole wire" % (n, mode, bool(errs))
+                for name, a, b in zip(("scale bytes", "code bytes", "out", "g <- w", "err"), tail(plain, n, nb_pad, k), tail(rot, n, nb_pad, k)):
+                    assert a.size == b.size and a.tobytes() == b.tobytes(), "n = %d, %s, ef %s: %s from element %d on" % (n, mode, bool(errs), name, k)
+                if len(payloads) < 3:
+                    payloads.append([plain.wire[:m6.section_bytes(n, fmt)].copy()])
+        dec = base.decode if dtype == "f32" else zb.decode
+        for R, is_plain in ((1, True), (1, False), (3, False)):
+            a, b = (dec(groups[x], payloads, R, plain=is_plain)[k:n] for x in (False, True))
+            assert a.size == n - k and a.tobytes() == b.tobytes(), "n = %d: the decode-mean, R = %d%s" % (n, R, ", plain" if is_plain else "")
 
 
 def test_refusals():

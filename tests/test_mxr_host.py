@@ -113,10 +113,11 @@ def test_mxr_library_is_built_and_exports_its_abi():
     assert native.MX_ITEM_ELEMS % native.MXR_BLOCK == 0
     assert ctypes.sizeof(native._MXRBatchStruct) == 80      # (mxr.hip static_asserts the same size)
     assert native._MXRBatchStruct._fields_[:-1] == native._MXBatchStruct._fields_ and native._MXRBatchStruct.signs.offset == 48
-    # mx.hip and mxr.hip share their device functions through one header
+    # mx.hip and mxr.hip share their device functions through one header, their kernels and host path through another
     csrc = os.path.join(os.path.dirname(HERE), "gradient-quantization_amd", "csrc")
     for f in ("mx.hip", "mxr.hip"):
-        assert '#include "mx_common.hpp"' in open(os.path.join(csrc, f)).read()
+        text = open(os.path.join(csrc, f)).read()
+        assert '#include "mx_common.hpp"' in text and '#include "mx_kernels.hpp"' in text and "__global__" not in text
 
 
 def test_descriptor_needs_a_device_table():

@@ -1,0 +1,116 @@
+"""The compiled code of libgq_mx.so's and libgq_mxr.so's kernels, this tree against another checkout (the parent commit), kernel
+by kernel.
+
+    python tools/mx_isa_compare.py --parent DIR [--out profiles/mx_refactor_isa.txt]
+
+DIR is a checkout of the commit to compare with (`git worktree add DIR HEAD~1`, or `git archive` unpacked).  Both trees' csrc/mx.hip
+and csrc/mxr.hip are compiled with build.py's flags + --save-temps into scratch directories (no GPU needed); the 2 x 56 kernels are
+matched by library, kind (compress / decode), format, draw mode, error feedback and tensor type, read off the template arguments
+in their mangled names.  Per kernel: the instruction count (the .s text of the function, labels, directives and comments
+dropped), the registers and the scratch / LDS bytes of the kernel's metadata, both sides, and whether the instruction text is the
+same once the labels are renumbered.  Whole texts and numbers are compared; no instruction is looked for.
+Exit status 1 if a kernel has scratch or LDS, or if its VGPR count falls into a lower waves-per-SIMD class than the other tree's.
+"""
+import argparse
+import importlib.util
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "gradient-quantization_amd"
+FILES = ("mx.hip", "mxr.hip")
+FMT = {0: "fp4", 1: "fp8", 0x23: "fp6_e2m3", 0x32: "fp6_e3m2"}
+MODE = {0: "off", 1: "given", 2: "device"}
+TT = {0: "f32", 1: "bf16"}
+META = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+def build_asm(root, name):
+    """The gfx950 assembly of root's csrc/<name>, compiled with root's own build flags."""
+    spec = importlib.util.spec_from_file_location("gq_build_" + str(abs(hash(root))), os.path.join(root, PKG, "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    d = tempfile.mkdtemp(prefix="gq_mx_isa_")
+    flags = [f for f in b.FLAGS if f != "-shared"] + b.EXTRA.get(name, [])
+    subprocess.check_call([b.hipcc()] + flags + ["--save-temps", "-c", os.path.join(root, PKG, "csrc", name), "-o", os.path.join(d, "x.o")],
+                          cwd=d, stderr=subprocess.DEVNULL)
+    return open(os.path.join(d, [f for f in os.listdir(d) if f.endswith("gfx950.s")][0])).read()
+
+
+def key_of(symbol):
+    """(kind, format, mode, ef, tensor type) from the integer template arguments of a kernel's mangled name."""
+    kind = "compress" if "compress_kernel" in symbol else "decode"
+    args = [int(v) for v in re.findall(r"L[ib](\d+)E", symbol[:symbol.index("EEv")] + "E")]
+    if kind == "compress":
+        fmt, mode, ef, tt = args
+        return kind, FMT[fmt], MODE[mode], "ef" if ef else "-", TT[tt]
+    fmt, tt = args
+    return kind, FMT[fmt], "-", "-", TT[tt]
+
+
+def kernels(txt):
+    """key -> (instruction lines with the labels renumbered, the kernel's metadata numbers)."""
+    out = {}
+    for m in re.finditer(r"^(_Z\w+_kernel\w+):", txt, re.M):
+        sym = m.group(1)
+        body = txt[m.end():txt.index(".Lfunc_end", m.end())]
+        lines = [ln.split(";")[0].strip() for ln in body.split("\n")]
+        lines = [ln for ln in lines if ln and not ln.startswith(".") or re.match(r"\.LBB\d+_\d+:", ln)]
+        order = {}
+        for ln in lines:                                   # labels by order of definition: the function's number drops out
+            lab = re.match(r"(\.LBB\d+_\d+):", ln)
+            if lab:
+                order[lab.group(1)] = "L%d" % len(order)
+        text = [re.sub(r"\.LBB\d+_\d+", lambda g: order.get(g.group(0), g.group(0)), ln) for ln in lines]
+        k = txt.index(".name:           " + sym + "\n", txt.index("amdhsa.kernels:"))
+        start = txt.rindex("\n  - ", 0, k)
+        end = txt.find("\n  - ", k)
+        entry = txt[start:end if end > 0 else len(txt)]
+        meta = {f: int(re.search(r"^\s+%s:\s+(\d+)" % re.escape(f), entry, re.M).group(1)) for f in META}
+        meta["instructions"] = sum(1 for ln in text if not ln.endswith(":"))
+        out[key_of(sym)] = (text, meta)
+    return out
+
+
+def waves_per_simd(vgprs):
+    """gfx950: 512 VGPRs per SIMD lane, handed out in blocks of 8, at most 8 waves."""
+    return min(8, 512 // max(8, (vgprs + 7) // 8 * 8))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent", required=True, help="a checkout of the commit to compare with")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx_refactor_isa.txt"))
+    a = ap.parse_args()
+    rows, bad, differ = [], [], 0
+    for name in FILES:
+        old, new = kernels(build_asm(os.path.abspath(a.parent), name)), kernels(build_asm(ROOT, name))
+        assert sorted(old) == sorted(new) and len(new) == 56, "%s: %d kernels against %d" % (name, len(old), len(new))
+        for key in sorted(new):
+            (t0, m0), (t1, m1) = old[key], new[key]
+            same = t0 == t1
+            differ += not same
+            rows.append("%-4s %-8s %-8s %-6s %-2s %-4s  %5d %5d  %3d %3d  %3d %3d  %d %d  %d %d  %s"
+                        % ((name[:-4],) + key + (m0["instructions"], m1["instructions"], m0[".vgpr_count"], m1[".vgpr_count"],
+                                                 m0[".sgpr_count"], m1[".sgpr_count"], m0[".private_segment_fixed_size"],
+                                                 m1[".private_segment_fixed_size"], m0[".group_segment_fixed_size"],
+                                                 m1[".group_segment_fixed_size"], "identical" if same else "DIFFERS")))
+            if m1[".private_segment_fixed_size"] or m1[".group_segment_fixed_size"]:
+                bad.append("%s %s: scratch or LDS" % (name, key))
+            if waves_per_simd(m1[".vgpr_count"]) < waves_per_simd(m0[".vgpr_count"]):
+                bad.append("%s %s: %d VGPRs against %d: fewer waves per SIMD" % (name, key, m1[".vgpr_count"], m0[".vgpr_count"]))
+    head = ["# tools/mx_isa_compare.py: the kernels of mx.hip and mxr.hip, the parent commit against this tree (gfx950, build.py's flags).",
+            "# columns: library kind format mode ef type | instructions parent new | VGPRs parent new | SGPRs parent new |",
+            "#          scratch bytes parent new | LDS bytes parent new | instruction text with labels renumbered",
+            "# %d kernels, %d with other instruction text than the parent's" % (len(rows), differ)]
+    with open(a.out, "w") as f:
+        f.write("\n".join(head + rows) + "\n")
+    print("\n".join(head[3:] + bad))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

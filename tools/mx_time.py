@@ -18,10 +18,12 @@ Rows (one JSON line each):
                   this build over the parent's fp8 launch of the same kind, *_over_parent: over the parent's same launch.
   bf16_25m        (--dtype bf16: this row alone is measured, and replaces the row of that case in FILE, whose other rows stay) one
                   25 M-element tensor, fp4 and fp8: the four launches -- compress stochastic, compress nearest, decode-mean R = 1 and
-                  R = 8 -- over bf16 tensors, over float32 tensors, and (--parent-lib) the parent build's float32 launches, alternated
-                  round by round in this process; eager and as ten launches replayed from one HIP graph.  *_bf16_over_parent and
-                  *_f32_over_parent: the ratio to the PARENT's float32 launch of the same format and kind (graphed; *_eager_* the
-                  eager ones); `bar` is 1.03 and `missed` lists every ratio above it.
+                  R = 8 -- over bf16 tensors, over float32 tensors, and (--parent-lib) the parent build's float32 launches and, where
+                  it exports the _bf16 entry points, its bf16 launches (tag parent_bf16), alternated round by round in this
+                  process; eager and as ten launches replayed from one HIP graph.  *_bf16_over_parent and *_f32_over_parent: the
+                  ratio to the PARENT's float32 launch of the same format and kind (graphed; *_eager_* the eager ones);
+                  *_bf16_over_parent_bf16: a bf16 launch over the parent's bf16 launch of the same format and kind; `bar` is 1.03
+                  and `missed` lists every ratio above it.
 Times: HIP events around a window of back-to-back calls after untimed ones, median of the windows, microseconds per call; the
 paths of a row are alternated round by round and the minimum over the rounds is reported next to every round."""
 import argparse
@@ -127,13 +129,13 @@ def library(path):
 
 @contextlib.contextmanager
 def other_library(path, batch_cls, name, prefix, exports):
-    """library() for either descriptor class (native.MXBatch / native.MXRBatch).  An older build has no bf16 entry points: only
-    the float32 ones are asked of it (the loader would otherwise refuse it), and no environment variable overrides its path --
-    the one difference to what library() did before the bf16 entry points were listed in native.MX_EXPORTS."""
+    """library() for either descriptor class (native.MXBatch / native.MXRBatch).  An older build may have no bf16 entry points:
+    only those it exports are asked of it (the loader would otherwise refuse it), and no environment variable overrides its path
+    -- the one difference to what library() did before the bf16 entry points were listed in native.MX_EXPORTS."""
     probe = ctypes.CDLL(path)
     version = getattr(probe, prefix + "abi_version")
     version.restype = ctypes.c_int
-    other = native.Library(name, "GQ_NO_SUCH_VARIABLE", prefix, version(), [e for e in exports if not e.endswith("_bf16")])
+    other = native.Library(name, "GQ_NO_SUCH_VARIABLE", prefix, version(), [e for e in exports if not e.endswith("_bf16") or exports_bf16(path, prefix)])
     other.path = path
     saved, batch_cls.LIBRARY = batch_cls.LIBRARY, other      # (a descriptor takes its library when it is built)
     try:
@@ -142,7 +144,12 @@ def other_library(path, batch_cls, name, prefix, exports):
         batch_cls.LIBRARY = saved
 
 
-BAR = 1.03      # a launch of this build over the parent's float32 launch: the spread between identical instruction streams in one run
+def exports_bf16(path, prefix):
+    """Does the build of the library at `path` have the bf16 entry points?"""
+    return hasattr(ctypes.CDLL(path), prefix + "compress_batched_bf16")
+
+
+BAR = 1.03      # a launch of this build over the parent's launch: the spread between identical instruction streams in one run
 
 
 def dtype_rows(dev, parent_lib=None, rotated=False, n=25_000_000):
@@ -153,12 +160,14 @@ def dtype_rows(dev, parent_lib=None, rotated=False, n=25_000_000):
     t32 = t16.float()      # the same values: the wire of the two is the same, byte for byte
     group_cls, codec_cls, batch_cls = (BatchedMXR, MXRCodec, native.MXRBatch) if rotated else (BatchedMX, MXCodec, native.MXBatch)
     lib_name, prefix, exports = (("libgq_mxr.so", "gq_mxr_", native.MXR_EXPORTS) if rotated else ("libgq_mx.so", "gq_mx_", native.MX_EXPORTS))
+    parent_bf16 = bool(parent_lib) and exports_bf16(parent_lib, prefix)
     groups, wires, src = {}, {}, {}
     for fmt in ("fp4", "fp8"):
         for random in (1, 0):
             comp = MXCompressor(n, (n,), _args(mx_format=fmt, random=random, mx_rotate="hadamard" if rotated else "none"))
-            for tag, dt, lib in (("bf16", torch.bfloat16, None), ("f32", torch.float32, None), ("parent_f32", torch.float32, parent_lib)):
-                if tag == "parent_f32" and not parent_lib:
+            for tag, dt, lib in (("bf16", torch.bfloat16, None), ("f32", torch.float32, None), ("parent_f32", torch.float32, parent_lib),
+                                 ("parent_bf16", torch.bfloat16, parent_lib)):
+                if lib is None and tag.startswith("parent_") or tag == "parent_bf16" and not parent_bf16:
                     continue
                 name = "%s_%s_%s" % (fmt, "stochastic" if random else "nearest", tag)
                 cd = codec_cls(comp, n, (n,), dt)
@@ -170,9 +179,9 @@ def dtype_rows(dev, parent_lib=None, rotated=False, n=25_000_000):
                 for r in range(1, 8):
                     wire[r].copy_(wire[0])
                 groups[name], wires[name] = g, wire
-    for fmt in ("fp4", "fp8"):      # (the claim the ratios rest on: the same bytes leave all three)
+    for fmt in ("fp4", "fp8"):      # (the claim the ratios rest on: the same bytes leave all of them)
         for mode in ("stochastic", "nearest"):
-            same = [wires["%s_%s_%s" % (fmt, mode, tag)][0] for tag in ("bf16", "f32", "parent_f32") if "%s_%s_%s" % (fmt, mode, tag) in wires]
+            same = [wires["%s_%s_%s" % (fmt, mode, tag)][0] for tag in ("bf16", "f32", "parent_f32", "parent_bf16") if "%s_%s_%s" % (fmt, mode, tag) in wires]
             assert all(torch.equal(same[0], w) for w in same[1:]), "the wires of %s %s differ" % (fmt, mode)
     times, outs = {}, {}
     for rnd in range(3):
@@ -186,7 +195,7 @@ def dtype_rows(dev, parent_lib=None, rotated=False, n=25_000_000):
                     out = outs.setdefault(name, torch.empty(g.out_floats, dtype=g.dtype, device=dev))
                     times.setdefault(key + "_eager", []).append(timed(lambda: g._batch.decode(w[:R], R, out)))
                     times.setdefault(key, []).append(graphed(lambda: g._batch.decode(w[:R], R, out)))
-    row = {"case": "bf16_25m", "library": lib_name, "elements": n, "bar": BAR, "parent_lib": bool(parent_lib)}
+    row = {"case": "bf16_25m", "library": lib_name, "elements": n, "bar": BAR, "parent_lib": bool(parent_lib), "parent_bf16": parent_bf16}
     for key, ts in times.items():
         row[key + "_us_rounds"] = [round(x, 2) for x in ts]
         row[key + "_us"] = round(min(ts), 2)
@@ -199,6 +208,11 @@ def dtype_rows(dev, parent_lib=None, rotated=False, n=25_000_000):
                     for tag in ("bf16", "f32"):
                         field = "%s_%s%s_over_parent" % (fmt, kind % tag, eager)
                         row[field] = round(row["%s_%s%s_us" % (fmt, kind % tag, eager)] / base, 3)
+                        if not eager and row[field] > BAR:
+                            missed.append(field)
+                    if parent_bf16:      # bf16 against the parent's OWN bf16 launch
+                        field = "%s_%s%s_over_parent_bf16" % (fmt, kind % "bf16", eager)
+                        row[field] = round(row["%s_%s%s_us" % (fmt, kind % "bf16", eager)] / row["%s_%s%s_us" % (fmt, kind % "parent_bf16", eager)], 3)
                         if not eager and row[field] > BAR:
                             missed.append(field)
         row["missed"] = missed

@@ -11,8 +11,8 @@ Rows (one JSON line each):
                   the decode-mean at R = 1 and R = 8.  *_over_plain: the ratio to the plain MX launch of the same run -- the
                   plain launch is the yardstick, not this code.
   bf16_25m        (--dtype bf16) tools/mx_time.py's row of that name over libgq_mxr.so: the rotated launches over bf16 tensors, over
-                  float32 tensors and (--parent-lib, an older libgq_mxr.so) the parent's float32 launches; only this row is measured,
-                  and it replaces the row of that case in FILE.
+                  float32 tensors and (--parent-lib, an older libgq_mxr.so) the parent's float32 and, where it has them, bf16 launches;
+                  only this row is measured, and it replaces the row of that case in FILE.
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -118,7 +118,7 @@ def single_rows(dev, n=25_000_000):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mxr_time.jsonl"))
-    ap.add_argument("--parent-lib", default=None, help="--dtype bf16: an older libgq_mxr.so whose float32 launches are the yardstick")
+    ap.add_argument("--parent-lib", default=None, help="--dtype bf16: an older libgq_mxr.so whose launches are the yardstick")
     ap.add_argument("--dtype", default=None, choices=["bf16"], help="the bf16_25m row alone: bf16 launches next to the float32 ones")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
