@@ -1,8 +1,9 @@
 // The microscaling compressor behind a randomized Hadamard rotation, multi-tensor (segment table) form -- libgq_mxr.so
 // (include/gq_mxr.h: the contract, to the bit; tests/mxr_contract.py restates it in numpy).
 //
-// The kernels and the host path are csrc/mx_kernels.hpp's, shared with mx.hip; this file is the rotation -- the policy the kernels
-// are instantiated with, and what it calls -- the descriptor and the exported names.
+// The kernels and the host path are csrc/mx_kernels.hpp's, shared with mx.hip; the rotation -- the policy the kernels are
+// instantiated with, and what it calls -- is csrc/hadamard.hpp's, shared with drive.hip; this file is the descriptor and the
+// exported names.
 // The kernels' shape: one workgroup per item of GQ_MX_ITEM_ELEMS elements, two steps of 2048, a lane owns eight
 // consecutive elements and a quad an MX block.  32 lanes therefore own a rotation block of 256: the 256-point Walsh-Hadamard
 // transform is three butterfly stages inside the lane (strides 1, 2, 4) and five across lanes (strides 8 ... 128 = lane xor
@@ -16,6 +17,7 @@
 // decode    the accumulation over the R payloads and the division, then ONE inverse transform, then the store.
 // A lane's eight sign bits are one byte of the descriptor's sign words (passed by value), extracted once per kernel.
 #include "gq_mxr.h"
+#include "hadamard.hpp"
 #include "mx_common.hpp"
 #include "mx_kernels.hpp"
 
@@ -25,90 +27,7 @@ namespace gqx {
 
 static_assert(GQ_MXR_BLOCK == 32 * PER_LANE && STEP % GQ_MXR_BLOCK == 0, "a 32-lane half owns a rotation block");
 static_assert(sizeof(gq_mxr_batch) == 80, "gq_mxr_batch: the layout the ctypes binding declares (gq_amd/native.py)");
-
-struct Signs {
-    uint64_t w[4];
-};
-
-// this lane's byte of the sign words: bit k belongs to its element k (element j of the block: bit j & 63 of word j >> 6)
-__device__ __forceinline__ uint32_t sign_byte(const Signs &s) {
-    const uint32_t l = threadIdx.x & 31u;
-    const uint32_t q = l >> 3;
-    const uint64_t word = q == 0 ? s.w[0] : q == 1 ? s.w[1] : q == 2 ? s.w[2] : s.w[3];      // (selects: no indexed kernel argument)
-    return (uint32_t)(word >> (8 * (l & 7u))) & 0xffu;
-}
-
-// the value of lane ^ M, M = 1, 2, 4, 8 or 16 (all inside a 32-lane half)
-template <int M>
-__device__ __forceinline__ float lane_xor(float v) {
-    const int x = __float_as_int(v);
-    if (M == 1) return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));      // quad_perm [1, 0, 3, 2]
-    if (M == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));      // quad_perm [2, 3, 0, 1]
-    return __int_as_float(__builtin_amdgcn_ds_swizzle(x, (M << 10) | 0x1F));                         // bit mode: and 0x1f, or 0, xor M
-}
-
-// one cross-lane stage, stride 8 M: the lane with bit M clear takes mine + other, its partner other - mine
-template <int M>
-__device__ __forceinline__ void cross_stage(float (&x)[PER_LANE]) {
-    const uint32_t neg = (threadIdx.x & M) ? 0x80000000u : 0u;
-#pragma unroll
-    for (int k = 0; k < PER_LANE; ++k) {
-        const float other = lane_xor<M>(x[k]);
-        x[k] = other + __uint_as_float(__float_as_uint(x[k]) ^ neg);
-    }
-}
-
-// the eight stages t = 0 ... 7 in this order, then * 2^-4 (include/gq_mxr.h)
-__device__ __forceinline__ void stages_and_scale(float (&x)[PER_LANE]) {
-#pragma unroll
-    for (int h = 1; h < PER_LANE; h <<= 1) {
-#pragma unroll
-        for (int j = 0; j < PER_LANE; ++j) {
-            if (!(j & h)) {
-                const float a = x[j], b = x[j + h];
-                x[j] = a + b;
-                x[j + h] = a - b;
-            }
-        }
-    }
-    cross_stage<1>(x);
-    cross_stage<2>(x);
-    cross_stage<4>(x);
-    cross_stage<8>(x);
-    cross_stage<16>(x);
-#pragma unroll
-    for (int k = 0; k < PER_LANE; ++k) x[k] = x[k] * 0.0625f;
-}
-
-__device__ __forceinline__ float flip(float v, uint32_t sbyte, int k) { return __uint_as_float(__float_as_uint(v) ^ (((sbyte >> k) & 1u) << 31)); }
-
-// The rotation policy of csrc/mx_kernels.hpp: blocks of 256 by H * diag(signs) / 16; it carries the lane's sign byte.
-struct Hadamard {
-    using Args = Signs;
-    static constexpr int BLOCK = GQ_MXR_BLOCK;    // a 32-lane half owns one: `rot` is uniform over the half
-    static constexpr bool EVERY_LANE = true;      // the cross-lane stages: every lane executes them and selects afterwards
-    uint32_t sbyte;
-    __device__ __forceinline__ explicit Hadamard(const Signs &s) : sbyte(sign_byte(s)) {}
-    // w -> x' (rot; otherwise x' = w)
-    __device__ __forceinline__ const Lane8 &forward(const Lane8 &w, Lane8 &x, bool rot) const {
-#pragma unroll
-        for (int k = 0; k < PER_LANE; ++k) x[k] = flip(w[k], sbyte, k);
-        stages_and_scale(x);
-#pragma unroll
-        for (int k = 0; k < PER_LANE; ++k) x[k] = rot ? x[k] : w[k];
-        return x;
-    }
-    // y -> its inverse transform, in place
-    __device__ __forceinline__ void inverse(Lane8 &y, bool rot) const {
-        float t[PER_LANE];
-#pragma unroll
-        for (int k = 0; k < PER_LANE; ++k) t[k] = y[k];
-        stages_and_scale(t);
-#pragma unroll
-        for (int k = 0; k < PER_LANE; ++k) y[k] = rot ? flip(t[k], sbyte, k) : y[k];
-    }
-    static Args args(const gq_mxr_batch *b) { return Signs{{b->signs[0], b->signs[1], b->signs[2], b->signs[3]}}; }
-};
+static_assert(HAD_BLOCK == GQ_MXR_BLOCK && HAD_PER_LANE == PER_LANE, "csrc/hadamard.hpp rotates the blocks, and over the lanes, of csrc/mx_kernels.hpp");
 
 }  // namespace gqx
 

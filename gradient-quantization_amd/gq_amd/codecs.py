@@ -11,7 +11,9 @@ device memory, through gq_amd.native).
     SignCodec                  SignSGDCompressor: one 2-bit code per element (+0, +1, -1), 16 to a uint32 word
     MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
     MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP6 / FP8 code per element
-    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR
+    DriveCodec                 DriveCompressor: one sign bit per element of the rotated 256-element blocks, then an f32 scale per block
+    BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR /
+    BatchedDrive
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -25,7 +27,7 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (DriveCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
@@ -738,6 +740,39 @@ class MXRCodec(MXCodec):
     def __init__(self, compressor, numel, shape, dtype=torch.float32):
         MXCodec.__init__(self, compressor, numel, shape, dtype)
         self.signs = tuple(int(w) for w in compressor.rotate_signs)
+
+
+def drive_section_bytes(numel):
+    """Bytes of one tensor's section of the DRIVE wire (include/gq_drive.h): ceil(numel / 256) blocks of 32 code bytes, then one f32
+    scale per block, zero bytes up to a multiple of 16."""
+    nb = -(-numel // native.DRIVE_BLOCK)
+    return nb * (native.DRIVE_BLOCK // 8) + _up(4 * nb)
+
+
+class DriveCodec(_SparseCodec):
+    """DriveCompressor on the HIP kernels (libgq_drive.so).  Wire per tensor: the sign bit of every coordinate of the rotated
+    256-element blocks (the last block zero-padded), then one f32 scale per block -- drive_section_bytes, 1.125 bits per element.
+    The decode ends with an inverse rotation, so the wire does not carry the decoded tensor itself.  No draws.  Every call is a
+    one-tensor BatchedDrive; roundtrip / encode_decode_into return the compress launch's own dense decode."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        if numel < 1:
+            raise ValueError("DriveCodec: a tensor of %d elements" % numel)
+        self.scale_mode = native.DRIVE_SCALES[compressor.scale]
+        self.signs = tuple(int(w) for w in compressor.signs)
+        self.nbytes = drive_section_bytes(numel)
+
+    def _wire_bytes(self):
+        return self.nbytes      # (never empty: numel >= 1)
+
+    def encode_into(self, grad, wire_user, off, salt, out=None, err=None, ef_scale=None):
+        """err, ef_scale: error feedback in the same launch -- grad <- w = grad + ef_scale * err, err <- w - decoded.  err: float32,
+        contiguous, of grad's size; grad must then be contiguous itself."""
+        if err is not None and not grad.is_contiguous():
+            raise ValueError("DriveCodec: error feedback updates the gradient in place and needs a contiguous one")
+        _SparseCodec.encode_into(self, grad, wire_user, off, salt, out=out, errs=[err.view(-1)] if err is not None else None,
+                                 ef_scale=ef_scale)
 
 
 _DATA_PTR = torch.Tensor.data_ptr
@@ -1933,6 +1968,46 @@ class BatchedMXR(BatchedMX):
 MXRCodec.GROUP = BatchedMXR
 
 
+class BatchedDrive(_ItemGroup):
+    """All DriveCompressor tensors of one scale mode and set of sign words in ONE gq_drive_compress_batched launch and ONE
+    gq_drive_decode_sum_batched launch (include/gq_drive.h).  No draws and no scratch: both replay from a HIP graph with nothing
+    to step.  The compress also writes the dense decode where a caller asks for it (the two-phase re-compress returns it); with
+    error feedback it updates the gradient and the residual in the same launch.  The decode-mean adds the payloads in the rotated
+    domain and rotates the mean back once -- which is why one group, and every user of it, has one set of sign words."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is DriveCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.scale_mode,) + tuple(codec.signs)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        # an item is a run of elements (numel >= 1: never none); 16-byte aligned views in the output buffer: the launches store float4 there
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                      lambda cd: -(-cd.numel // native.MX_ITEM_ELEMS), {}, 4)
+        c0 = self.codecs[0]
+        self.random = False
+        self.scale_mode, self.signs = c0.scale_mode, c0.signs
+        self._batch = native.DriveBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.scale_mode, self.signs)
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None):
+        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error feedback
+        in the same launch (t += ef_scale*err before the rotation, err = t - decoded after it, both in place).
+        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
+        if wire_user.data_ptr() % 16:
+            return False
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
+            return False
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None)
+        return True
+
+
+DriveCodec.GROUP = BatchedDrive
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -1950,6 +2025,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return MaureyCodec(compressor, numel, shape)
     if isinstance(compressor, MXCompressor):
         return (MXRCodec if getattr(compressor, "rotate", None) else MXCodec)(compressor, numel, shape)
+    if isinstance(compressor, DriveCompressor):
+        return DriveCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

@@ -622,6 +622,47 @@ class MXCompressor(object):
         return signature
 
 
+class DriveCompressor(object):
+    """The rotated 1-bit compressor (DRIVE, Vargaftik et al. 2021; no counterpart in the reference's catalogue): a block of 256
+    elements is rotated by a randomized Hadamard matrix, the sign of every rotated coordinate is kept and one f32 scale per block --
+    1.125 bits per element, no draws (include/gq_drive.h defines it to the bit).
+    args.drive_scale: 'unbiased' (the default) -- S = |x|^2 / |Rx|_1: the decode is unbiased over the rotation's randomness and
+    exact in the direction of x, so the mean over users averages out -- or 'mse' -- S = |Rx|_1 / 256: the least single-shot error,
+    what error feedback wants.  args.drive_seed (default 1) gives the four sign words (MXCompressor.sign_words: every rank with
+    the same arguments has the same signs; one decode-mean needs every payload under the same signs).
+    compress returns the dense decode and decompress is the identity, as for MXCompressor.  HIP kernels only (libgq_drive.so): a
+    float32 tensor on the device."""
+
+    SCALES = ("unbiased", "mse")
+
+    def __init__(self, size, shape, args):
+        scale = getattr(args, "drive_scale", None) or "unbiased"
+        if scale not in self.SCALES:
+            raise ValueError("drive_scale must be 'unbiased' or 'mse', got %r" % (scale,))
+        self.scale = scale
+        seed = getattr(args, "drive_seed", None)
+        self.seed = 1 if seed is None else int(seed)
+        self.signs = MXCompressor.sign_words(self.seed)
+        self.size, self.shape = size, shape
+
+    def compress(self, vec):
+        from .codecs import DriveCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("DriveCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), got %s on %s"
+                            % (vec.dtype, vec.device))
+        n = vec.numel()
+        if n == 0:
+            return vec.clone()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = DriveCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "MXCompressor"]
+           "MaureySparsification", "MXCompressor", "DriveCompressor"]

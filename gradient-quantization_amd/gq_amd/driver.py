@@ -32,7 +32,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (DriveCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
@@ -46,6 +46,7 @@ quantizer_choices = {          # main.py:20-26
     'rq': ResidualCompressor,                  # two stages: hsq, then pvq on what it leaves (not in main.py's table either)
     'maurey': MaureySparsification,            # the unbiased sparsifier: k draws with P(i) = |v_i| / ||v||_1 (likewise)
     'mx': MXCompressor,                        # block-scaled small floats (MXFP4 / MXFP6 / MXFP8, --mx-format): not in the reference at all
+    'drive': DriveCompressor,                  # the rotated 1-bit compressor (--drive-scale, --drive-seed): 1.125 bits per element, likewise
 }
 
 
@@ -177,6 +178,11 @@ def build_parser():
                         'decode (lower error on heavy-tailed gradients, the same bits per element; not in ring mode)')
     p.add_argument('--mx-rotate-seed', dest='mx_rotate_seed', type=int, default=1,
                    help='--mx-rotate hadamard: the seed of the four sign words (every rank must use the same)')
+    p.add_argument('--drive-scale', dest='drive_scale', type=str, default='unbiased', choices=['unbiased', 'mse'],
+                   help="--quantizer drive: the per-block scale -- 'unbiased' averages out over users, 'mse' has the lower single-shot "
+                        "error (what --ef wants); not in ring mode")
+    p.add_argument('--drive-seed', dest='drive_seed', type=int, default=1,
+                   help='--quantizer drive: the seed of the four sign words of its rotation (every rank must use the same)')
     p.add_argument('--param-dtype', dest='param_dtype', type=str, default='float32', choices=['float32', 'bfloat16'],
                    help='the dtype the model is cast to.  bfloat16 needs --quantizer mx: its kernels read bfloat16 gradients and write '
                         'bfloat16 means in place (the wire is the float32 one); no other compressor takes them')

@@ -1065,6 +1065,52 @@ class MXRBatch(MXBatch):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.signs, self.dtype)
 
 
+# ---- the rotated 1-bit compressor (DRIVE): libgq_drive.so (include/gq_drive.h) -----------------------------------------------------
+DRIVE_ABI_VERSION = 1
+DRIVE_EXPORTS = ["gq_drive_abi_version", "gq_drive_last_error", "gq_drive_compress_batched", "gq_drive_decode_sum_batched"]
+DRIVE_BLOCK = 256           # GQ_DRIVE_BLOCK: elements that share a scale (a rotation block); an item is MX_ITEM_ELEMS
+DRIVE_UNBIASED, DRIVE_MSE = 0, 1      # GQ_DRIVE_UNBIASED / GQ_DRIVE_MSE
+DRIVE_SCALES = {"unbiased": DRIVE_UNBIASED, "mse": DRIVE_MSE}
+
+DRIVE_LIBRARY = Library("libgq_drive.so", "GQ_DRIVE_LIB_PATH", "gq_drive_", DRIVE_ABI_VERSION, DRIVE_EXPORTS)
+DRIVE_LIB_PATH = DRIVE_LIBRARY.path
+
+
+def drive_lib():
+    return DRIVE_LIBRARY.handle or _load(DRIVE_LIBRARY)
+
+
+class _DriveBatchStruct(ctypes.Structure):    # gq_drive_batch (include/gq_drive.h): gq_mxr_batch's layout, scale_mode for format
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
+                ("ndense", ctypes.c_int32), ("scale_mode", ctypes.c_int32), ("signs", ctypes.c_uint64 * 4)]
+
+
+class DriveBatch(_ItemBatch):
+    """The two launches of libgq_drive.so: gq_drive_compress_batched (sign bits of the rotated blocks and one f32 scale per block, +
+    the dense decode and the residual) and gq_drive_decode_sum_batched (the mean in the rotated domain, one inverse rotation).
+    No scratch and no draws.  scale_mode: DRIVE_UNBIASED or DRIVE_MSE; signs: the four 64-bit sign words (gq_mxr.h's)."""
+
+    LIBRARY, STRUCT = DRIVE_LIBRARY, _DriveBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, scale_mode=DRIVE_UNBIASED, signs=(0, 0, 0, 0)):
+        signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
+        assert len(signs) == 4
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, scale_mode=int(scale_mode), signs=(ctypes.c_uint64 * 4)(*signs))
+        self.signs = signs
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.scale_mode, self.signs)
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
+        (seg_table[:, 7] = error buffers)."""
+        rc = self.L.gq_drive_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
+                                              ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                              _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_drive_compress_batched", DRIVE_LIBRARY)
+
+
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
 KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]
