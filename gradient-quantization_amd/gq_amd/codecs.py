@@ -12,8 +12,9 @@ device memory, through gq_amd.native).
     MaureyCodec                MaureySparsification: a 16-byte header (scale), then k ascending uint32 words index | sign << 31
     MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP6 / FP8 code per element
     DriveCodec                 DriveCompressor: one sign bit per element of the rotated 256-element blocks, then an f32 scale per block
+    EdenCodec                  EdenCompressor: a 2-, 3- or 4-bit Lloyd-Max code per element of the rotated blocks, then an f32 scale per block
     BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR /
-    BatchedDrive
+    BatchedDrive / BatchedEden
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -27,7 +28,7 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (DriveCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
@@ -773,6 +774,31 @@ class DriveCodec(_SparseCodec):
             raise ValueError("DriveCodec: error feedback updates the gradient in place and needs a contiguous one")
         _SparseCodec.encode_into(self, grad, wire_user, off, salt, out=out, errs=[err.view(-1)] if err is not None else None,
                                  ef_scale=ef_scale)
+
+
+def eden_section_bytes(numel, bits):
+    """Bytes of one tensor's section of the EDEN wire (include/gq_eden.h): ceil(numel / 256) blocks of 32 * bits code bytes, then one
+    f32 scale per block, zero bytes up to a multiple of 16."""
+    if bits not in native.EDEN_BITS:
+        raise ValueError("eden_bits must be 2, 3 or 4, got %r" % (bits,))
+    nb = -(-numel // native.EDEN_BLOCK)
+    return nb * (native.EDEN_BLOCK * bits // 8) + _up(4 * nb)
+
+
+class EdenCodec(DriveCodec):
+    """EdenCompressor on the HIP kernels (libgq_eden.so).  Wire per tensor: a `bits`-bit code (the nearest Lloyd-Max centroid of
+    N(0, 1), sign on top) for every coordinate of the rotated 256-element blocks (the last block zero-padded), then one f32 scale per
+    block -- eden_section_bytes, bits + 0.125 bits per element.  Otherwise DriveCodec: the decode ends with an inverse rotation, no
+    draws, every call is a one-tensor BatchedEden."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        if numel < 1:
+            raise ValueError("EdenCodec: a tensor of %d elements" % numel)
+        self.bits = int(compressor.bits)
+        self.scale_mode = native.EDEN_SCALES[compressor.scale]
+        self.signs = tuple(int(w) for w in compressor.signs)
+        self.nbytes = eden_section_bytes(numel, self.bits)
 
 
 _DATA_PTR = torch.Tensor.data_ptr
@@ -1990,7 +2016,10 @@ class BatchedDrive(_ItemGroup):
         c0 = self.codecs[0]
         self.random = False
         self.scale_mode, self.signs = c0.scale_mode, c0.signs
-        self._batch = native.DriveBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.scale_mode, self.signs)
+        self._batch = self._make_batch(nseg, item)
+
+    def _make_batch(self, nseg, item):
+        return native.DriveBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.scale_mode, self.signs)
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False, out=None):
@@ -2006,6 +2035,26 @@ class BatchedDrive(_ItemGroup):
 
 
 DriveCodec.GROUP = BatchedDrive
+
+
+class BatchedEden(BatchedDrive):
+    """All EdenCompressor tensors of one (bits, scale mode, sign words) in ONE gq_eden_compress_batched launch and ONE
+    gq_eden_decode_sum_batched launch (include/gq_eden.h).  BatchedDrive's host path on libgq_eden.so's descriptor."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is EdenCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.bits, codec.scale_mode) + tuple(codec.signs)
+
+    def _make_batch(self, nseg, item):
+        self.bits = self.codecs[0].bits
+        return native.EdenBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.bits, self.scale_mode, self.signs)
+
+
+EdenCodec.GROUP = BatchedEden
 
 
 def default_codec_factory(compressor, numel, shape, packed6=False):
@@ -2027,6 +2076,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return (MXRCodec if getattr(compressor, "rotate", None) else MXCodec)(compressor, numel, shape)
     if isinstance(compressor, DriveCompressor):
         return DriveCodec(compressor, numel, shape)
+    if isinstance(compressor, EdenCompressor):
+        return EdenCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

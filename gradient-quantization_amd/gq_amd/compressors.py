@@ -663,6 +663,54 @@ class DriveCompressor(object):
         return signature
 
 
+class EdenCompressor(object):
+    """The rotated 2-, 3- or 4-bit compressor (EDEN, Vargaftik et al. 2022, DRIVE's sequel; no counterpart in the reference's
+    catalogue): a block of 256 elements is rotated by a randomized Hadamard matrix, every rotated coordinate is replaced by the
+    nearest of the 2^bits Lloyd-Max centroids of N(0, 1) times the block's spread, and one f32 scale per block is kept --
+    bits + 0.125 bits per element, no draws (include/gq_eden.h defines it to the bit).
+    args.eden_bits: 2, 3 or 4 (the default; one bit is DriveCompressor).  args.eden_scale: 'unbiased' (the default) -- the decode
+    is unbiased over the rotation's randomness and exact in the direction of x -- or 'mse' -- the least-squares scale.
+    args.eden_seed (default 1) gives the four sign words (MXCompressor.sign_words: every rank with the same arguments has the same
+    signs; one decode-mean needs every payload under the same signs).
+    compress returns the dense decode and decompress is the identity, as for DriveCompressor.  HIP kernels only (libgq_eden.so): a
+    float32 tensor on the device."""
+
+    SCALES = ("unbiased", "mse")
+    BITS = (2, 3, 4)
+
+    def __init__(self, size, shape, args):
+        bits = getattr(args, "eden_bits", None)
+        bits = 4 if bits is None else bits
+        if isinstance(bits, bool) or bits not in self.BITS:
+            raise ValueError("eden_bits must be 2, 3 or 4 (one bit is --quantizer drive), got %r" % (bits,))
+        self.bits = int(bits)
+        scale = getattr(args, "eden_scale", None) or "unbiased"
+        if scale not in self.SCALES:
+            raise ValueError("eden_scale must be 'unbiased' or 'mse', got %r" % (scale,))
+        self.scale = scale
+        seed = getattr(args, "eden_seed", None)
+        self.seed = 1 if seed is None else int(seed)
+        self.signs = MXCompressor.sign_words(self.seed)
+        self.size, self.shape = size, shape
+
+    def compress(self, vec):
+        from .codecs import EdenCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("EdenCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), got %s on %s"
+                            % (vec.dtype, vec.device))
+        n = vec.numel()
+        if n == 0:
+            return vec.clone()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = EdenCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "MXCompressor", "DriveCompressor"]
+           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor"]

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (DriveCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
@@ -47,6 +47,7 @@ quantizer_choices = {          # main.py:20-26
     'maurey': MaureySparsification,            # the unbiased sparsifier: k draws with P(i) = |v_i| / ||v||_1 (likewise)
     'mx': MXCompressor,                        # block-scaled small floats (MXFP4 / MXFP6 / MXFP8, --mx-format): not in the reference at all
     'drive': DriveCompressor,                  # the rotated 1-bit compressor (--drive-scale, --drive-seed): 1.125 bits per element, likewise
+    'eden': EdenCompressor,                    # the rotated 2- / 3- / 4-bit compressor (--eden-bits, --eden-scale, --eden-seed): bits + 0.125, likewise
 }
 
 
@@ -183,6 +184,14 @@ def build_parser():
                         "error (what --ef wants); not in ring mode")
     p.add_argument('--drive-seed', dest='drive_seed', type=int, default=1,
                    help='--quantizer drive: the seed of the four sign words of its rotation (every rank must use the same)')
+    p.add_argument('--eden-bits', dest='eden_bits', type=int, default=4, choices=[2, 3, 4],
+                   help='--quantizer eden: bits per element of the rotated blocks (the nearest of 2^bits Lloyd-Max centroids of N(0,1); '
+                        'one bit is --quantizer drive); the wire is bits + 0.125 bits per element')
+    p.add_argument('--eden-scale', dest='eden_scale', type=str, default='unbiased', choices=['unbiased', 'mse'],
+                   help="--quantizer eden: the per-block scale -- 'unbiased' averages out over users, 'mse' is the least-squares one; "
+                        "not in ring mode")
+    p.add_argument('--eden-seed', dest='eden_seed', type=int, default=1,
+                   help='--quantizer eden: the seed of the four sign words of its rotation (every rank must use the same)')
     p.add_argument('--param-dtype', dest='param_dtype', type=str, default='float32', choices=['float32', 'bfloat16'],
                    help='the dtype the model is cast to.  bfloat16 needs --quantizer mx: its kernels read bfloat16 gradients and write '
                         'bfloat16 means in place (the wire is the float32 one); no other compressor takes them')

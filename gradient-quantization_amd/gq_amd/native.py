@@ -1111,6 +1111,56 @@ class DriveBatch(_ItemBatch):
         _check(rc, "gq_drive_compress_batched", DRIVE_LIBRARY)
 
 
+# ---- the rotated 2- / 3- / 4-bit compressor (EDEN): libgq_eden.so (include/gq_eden.h) ----------------------------------------------
+EDEN_ABI_VERSION = 1
+EDEN_EXPORTS = ["gq_eden_abi_version", "gq_eden_last_error", "gq_eden_compress_batched", "gq_eden_decode_sum_batched"]
+EDEN_BLOCK = 256            # GQ_EDEN_BLOCK: elements that share a scale (a rotation block); an item is MX_ITEM_ELEMS
+EDEN_UNBIASED, EDEN_MSE = 0, 1        # GQ_EDEN_UNBIASED / GQ_EDEN_MSE
+EDEN_SCALES = {"unbiased": EDEN_UNBIASED, "mse": EDEN_MSE}
+EDEN_BITS = (2, 3, 4)       # GQ_EDEN_MIN_BITS ... GQ_EDEN_MAX_BITS (one bit is libgq_drive.so)
+
+EDEN_LIBRARY = Library("libgq_eden.so", "GQ_EDEN_LIB_PATH", "gq_eden_", EDEN_ABI_VERSION, EDEN_EXPORTS)
+EDEN_LIB_PATH = EDEN_LIBRARY.path
+
+
+def eden_lib():
+    return EDEN_LIBRARY.handle or _load(EDEN_LIBRARY)
+
+
+class _EdenBatchStruct(ctypes.Structure):     # gq_eden_batch (include/gq_eden.h): gq_drive_batch's fields plus bits, the sign words last
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
+                ("ndense", ctypes.c_int32), ("scale_mode", ctypes.c_int32), ("bits", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("signs", ctypes.c_uint64 * 4)]
+
+
+class EdenBatch(_ItemBatch):
+    """The two launches of libgq_eden.so: gq_eden_compress_batched (b-bit Lloyd-Max codes of the rotated blocks and one f32 scale per
+    block, + the dense decode and the residual) and gq_eden_decode_sum_batched (the mean in the rotated domain, one inverse
+    rotation).  No scratch and no draws.  bits: 2, 3 or 4; scale_mode: EDEN_UNBIASED or EDEN_MSE; signs: the four 64-bit sign
+    words (gq_mxr.h's)."""
+
+    LIBRARY, STRUCT = EDEN_LIBRARY, _EdenBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, bits=4, scale_mode=EDEN_UNBIASED, signs=(0, 0, 0, 0)):
+        signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
+        assert len(signs) == 4
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, scale_mode=int(scale_mode), bits=int(bits),
+                            signs=(ctypes.c_uint64 * 4)(*signs))
+        self.signs = signs
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.bits, self.s.scale_mode, self.signs)
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
+        (seg_table[:, 7] = error buffers)."""
+        rc = self.L.gq_eden_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
+                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_eden_compress_batched", EDEN_LIBRARY)
+
+
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
 KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]

@@ -31,7 +31,7 @@ import warnings
 import torch
 
 from . import exchange, native
-from .compressors import DriveCompressor, IdenticalCompressor, MXCompressor, TopKSparsificationCompressor, _next_seed, shared_seeds
+from .compressors import DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, TopKSparsificationCompressor, _next_seed, shared_seeds
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
 # addresses as one bytes key and the "all plain f32" flag in one pass; `.data =` for all parameters in another.  A step
@@ -46,7 +46,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
-    BatchedDGC, BatchedDrive, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
+    BatchedDGC, BatchedDrive, BatchedEden, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
     MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
@@ -244,7 +244,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -1114,6 +1114,9 @@ class RingQuantizer(PSQuantizer):
                              "longer holds once the decode ends with an inverse rotation")
         if isinstance(Compressor, type) and issubclass(Compressor, DriveCompressor):
             raise ValueError("the drive compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
+                             "which does not hold for a wire whose decode ends with an inverse rotation")
+        if isinstance(Compressor, type) and issubclass(Compressor, EdenCompressor):
+            raise ValueError("the eden compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
                              "which does not hold for a wire whose decode ends with an inverse rotation")
         two_phase = args.two_phase
         args.two_phase = False           # ring_quantizer.py has no second phase and no server residual
