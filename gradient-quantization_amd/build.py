@@ -26,6 +26,7 @@ LIBS = {
     os.path.join(HERE, "libgq_mxr.so"): ["mxr.hip"],              # the same behind a randomized 256-point Hadamard rotation: both instantiate the kernels and the host path of csrc/mx_kernels.hpp (formats and element types: csrc/mx_common.hpp)
     os.path.join(HERE, "libgq_drive.so"): ["drive.hip"],          # the rotated 1-bit compressor (DRIVE): signs of the rotated block and one f32 scale, on mxr.hip's rotation (csrc/hadamard.hpp)
     os.path.join(HERE, "libgq_eden.so"): ["eden.hip"],            # the rotated 2- / 3- / 4-bit compressor (EDEN): Lloyd-Max codes of the rotated block and one f32 scale, on the same rotation
+    os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],     # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean
     os.path.join(HERE, "libgq_maurey.so"): ["maurey.hip"],        # Maurey sparsification: the sampler's six launches and the decode-mean

@@ -4,8 +4,8 @@
 from gq_amd.compressors import (IdenticalCompressor, QSGDCompressor, NearestNeighborCompressor,  # noqa: F401
                                 ProbabilisticScalarCompressor, ProbabilisticVectorCompressor,
                                 ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor,
-                                MaureySparsification, EdenCompressor)
+                                MaureySparsification, EdenCompressor, ThresholdSparsificationCompressor)
 
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "EdenCompressor"]
+           "MaureySparsification", "EdenCompressor", "ThresholdSparsificationCompressor"]

@@ -13,8 +13,9 @@ device memory, through gq_amd.native).
     MXCodec                    MXCompressor: a scale byte per block of 32 elements, then one FP4 / FP6 / FP8 code per element
     DriveCodec                 DriveCompressor: one sign bit per element of the rotated 256-element blocks, then an f32 scale per block
     EdenCodec                  EdenCompressor: a 2-, 3- or 4-bit Lloyd-Max code per element of the rotated blocks, then an f32 scale per block
+    ThrCodec                   ThresholdSparsificationCompressor: a 16-byte header (kept, found, threshold), then cap ascending uint32 indices and cap f32 values
     BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR /
-    BatchedDrive / BatchedEden
+    BatchedDrive / BatchedEden / BatchedThr
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -29,7 +30,7 @@ import torch
 
 from . import exchange, native
 from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
-                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor, _next_seed,
+                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
 
@@ -616,6 +617,42 @@ class TopKCodec(_SparseCodec):
             out.zero_()
             return
         _SparseCodec._decode_rows(self, gathered, off, R, out, plain=plain)
+
+
+def thr_section_bytes(numel, cr, percent=150):
+    """Bytes of one tensor's section of the threshold wire (include/gq_thr.h): a 16-byte header, cap uint32 indices, cap f32 values,
+    zero bytes up to a multiple of 16; cap = min(numel, (k * percent + 99) // 100), k = numel // cr."""
+    k = numel // cr
+    if k < 1:
+        raise ValueError("thr_section_bytes: k = %d // %d is below 1" % (numel, cr))
+    return native.THR_HEADER_BYTES + _up(8 * ThresholdSparsificationCompressor.capacity(numel, k, percent))
+
+
+class ThrCodec(_SparseCodec):
+    """ThresholdSparsificationCompressor on the HIP kernels (libgq_thr.so).  Wire per tensor: a 16-byte header { kept, found,
+    bits(eta), 0 }, cap ascending uint32 indices, cap f32 values, slots from `kept` on holding index 0xffffffff and +0 --
+    thr_section_bytes.  Every call is a one-tensor BatchedThr; roundtrip / encode_decode_into return the compress launches' own
+    dense decode (w * mask), not a decode of the wire."""
+
+    def __init__(self, compressor, numel, shape):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.k = numel // compressor.cr
+        if self.k < 1 or not 1 <= numel < 2 ** 31:
+            raise ValueError("ThrCodec: k = %d // %d = %d for a tensor of %d elements (k must be at least 1)"
+                             % (numel, compressor.cr, self.k, numel))
+        self.cap = compressor.capacity(numel, self.k, compressor.percent)
+        self.stride = compressor.stride_for(numel, compressor.fit_stride)
+        self.stages, self.eta = compressor.stages, compressor.eta
+        self.nbytes = thr_section_bytes(numel, compressor.cr, compressor.percent)
+
+    def _wire_bytes(self):
+        return self.nbytes      # (never empty: the header)
+
+    def header(self, wire_user, off):
+        """(kept, found, eta) of this tensor's section of one user's wire: a read of three words, with a synchronisation."""
+        w = wire_user[off:off + 12].cpu().numpy()
+        kept, found = (int(x) for x in w[:8].view("<u4"))
+        return kept, found, float(w[8:12].view("<f4")[0])
 
 
 def sign_section_bytes(numel):
@@ -2057,6 +2094,56 @@ class BatchedEden(BatchedDrive):
 EdenCodec.GROUP = BatchedEden
 
 
+class BatchedThr(_ItemGroup):
+    """All ThresholdSparsificationCompressor tensors of one (stages, fixed threshold) in ONE gq_thr_compress_batched sequence
+    (`stages` reduce / pick pairs, then count, scan, write -- include/gq_thr.h) and ONE gq_thr_decode_sum_batched launch.  No draws:
+    every launch replays from a HIP graph.  The compress also writes the dense decoded tensors (w * mask) where a caller asks for
+    them: error feedback takes its residual from them, and the two-phase re-compress returns them."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is ThrCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.stages, codec.eta)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        mine = [codecs[i] for i in idxs]
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                      lambda cd: -(-cd.numel // native.THR_CHUNK),
+                                      {4: [cd.k for cd in mine], 6: [cd.cap + (cd.stride << 32) for cd in mine]}, 1)
+        self.random = False
+        self.stages, self.eta = mine[0].stages, mine[0].eta
+        assert all((cd.stages, cd.eta) == (self.stages, self.eta) for cd in mine)
+        # the fit's and the compaction's scratch (include/gq_thr.h): written before it is read, nothing in it has to be zero
+        self._sums = torch.empty(item, dtype=torch.float64, device=device)
+        self._state = torch.empty(nseg * 4, dtype=torch.int32, device=device)
+        self._counts = torch.empty(item * 2, dtype=torch.int32, device=device)
+        self._batch = native.ThrBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self._sums, self._state, self._counts,
+                                      self.stages, min(cd.k for cd in mine), min(cd.cap for cd in mine), min(cd.stride for cd in mine))
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None):
+        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
+        feedback in the same launches (t += ef_scale*err before the fit, err = t - decoded in the write launch, both in place).
+        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
+            return False
+        ef = ef_scale if errs is not None else None
+        if ef is not None and out is None:
+            out = self._ef_buffer(wire_user.device)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef, self.eta)
+        return True
+
+    def kept_counts(self, wire_user):
+        """[(kept, found, eta), ...] of the group's tensors, read from the headers of one user's wire."""
+        return [cd.header(wire_user, int(self._layout[s, 3])) for s, cd in enumerate(self.codecs)]
+
+
+ThrCodec.GROUP = BatchedThr
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -2078,6 +2165,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return DriveCodec(compressor, numel, shape)
     if isinstance(compressor, EdenCompressor):
         return EdenCodec(compressor, numel, shape)
+    if isinstance(compressor, ThresholdSparsificationCompressor):
+        return ThrCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

@@ -23,6 +23,7 @@ call (probabilistic_scalar_compressor.py:23-25).  `args.gq_rng` (or $GQ_RNG) sel
                  its (lb, ub) instead of a per-call seed: nothing in the launch changes from step to step, which is
                  what lets a quantizer step replay from a HIP graph (gq_graph, quantizers.py).
 """
+import math
 import os
 
 import numpy as np
@@ -711,6 +712,76 @@ class EdenCompressor(object):
         return signature
 
 
+class ThresholdSparsificationCompressor(object):
+    """Keep what exceeds a threshold (no counterpart in the reference's catalogue): the elements with |w| > eta, at most
+    cap = min(n, ceil(k * thr_cap_percent / 100)) of them in index order, k = size // cr.  eta is fitted to the tail of |w| in
+    args.thr_stages passes over the tensor (the default 3; a count-adaptive multi-stage exponential fit after SIDCo) or, with
+    thr_stages = 0, is args.thr_value -- a hard threshold (include/gq_thr.h defines both to the bit).  args.thr_fit_stride M fits on
+    every m-th item of 4,096 elements, m the largest power of two <= M that leaves a tensor at least 16 fit items (else 1).
+    compress returns the dense decode and decompress is the identity, as for TopKSparsificationCompressor's device path.  HIP kernels
+    only (libgq_thr.so): a float32 tensor on the device."""
+
+    MIN_FIT_ITEMS = 16
+    FLT_MAX = 3.4028234663852886e38
+
+    def __init__(self, size, shape, args):
+        cr = getattr(args, "cr", None)
+        if isinstance(cr, bool) or not isinstance(cr, int) or cr < 1:
+            raise ValueError("cr must be a positive integer, got %r" % (cr,))
+        stages = getattr(args, "thr_stages", None)
+        stages = 3 if stages is None else stages
+        if isinstance(stages, bool) or not isinstance(stages, int) or not 0 <= stages <= 8:
+            raise ValueError("thr_stages must be 0 (a fixed threshold, thr_value) or 1 ... 8, got %r" % (stages,))
+        value = getattr(args, "thr_value", None)
+        if stages == 0:
+            if value is None:
+                raise ValueError("thr_stages = 0 needs thr_value (the fixed threshold)")
+            value = float(value)
+            if value != value or math.copysign(1.0, value) < 0 or value > self.FLT_MAX:
+                raise ValueError("thr_value must lie in [+0, FLT_MAX], got %r" % (value,))
+            value = torch.tensor(value, dtype=torch.float32).item()      # (the f32 the launches are handed)
+        percent = getattr(args, "thr_cap_percent", None)
+        percent = 150 if percent is None else percent
+        if isinstance(percent, bool) or not isinstance(percent, int) or percent < 1:
+            raise ValueError("thr_cap_percent must be a positive integer, got %r" % (percent,))
+        M = getattr(args, "thr_fit_stride", None)
+        M = 1 if M is None else M
+        if isinstance(M, bool) or not isinstance(M, int) or M < 1:
+            raise ValueError("thr_fit_stride must be a positive integer, got %r" % (M,))
+        self.size, self.shape = size, shape
+        self.cr, self.stages, self.eta, self.percent, self.fit_stride = cr, stages, (value if stages == 0 else 0.0), percent, M
+        self.k = size // cr
+
+    @staticmethod
+    def capacity(numel, k, percent):
+        """cap = min(n, (k * P + 99) // 100) (include/gq_thr.h)."""
+        return min(numel, (k * percent + 99) // 100)
+
+    @classmethod
+    def stride_for(cls, numel, M):
+        """The tensor's fit stride m: the largest power of two <= M that leaves it at least MIN_FIT_ITEMS fit items, else 1."""
+        items = -(-numel // 4096)
+        m = 1
+        while 2 * m <= M and -(-items // (2 * m)) >= cls.MIN_FIT_ITEMS:
+            m *= 2
+        return m
+
+    def compress(self, vec):
+        from .codecs import ThrCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("ThresholdSparsificationCompressor: the kernels take float32 tensors on the HIP device (there is no CPU "
+                            "path), got %s on %s" % (vec.dtype, vec.device))
+        n = vec.numel()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = ThrCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor"]
+           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor"]

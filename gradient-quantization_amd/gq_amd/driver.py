@@ -33,7 +33,7 @@ import torch.optim as optim
 
 from .datasets import OnDiskClassification
 from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
-                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor)
+                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
 quantizer_choices = {          # main.py:20-26
@@ -48,6 +48,7 @@ quantizer_choices = {          # main.py:20-26
     'mx': MXCompressor,                        # block-scaled small floats (MXFP4 / MXFP6 / MXFP8, --mx-format): not in the reference at all
     'drive': DriveCompressor,                  # the rotated 1-bit compressor (--drive-scale, --drive-seed): 1.125 bits per element, likewise
     'eden': EdenCompressor,                    # the rotated 2- / 3- / 4-bit compressor (--eden-bits, --eden-scale, --eden-seed): bits + 0.125, likewise
+    'threshold': ThresholdSparsificationCompressor,      # what exceeds a fitted or a given threshold (--thr-stages, --thr-value, --thr-cap-percent, --thr-fit-stride, --cr), likewise
 }
 
 
@@ -192,6 +193,17 @@ def build_parser():
                         "not in ring mode")
     p.add_argument('--eden-seed', dest='eden_seed', type=int, default=1,
                    help='--quantizer eden: the seed of the four sign words of its rotation (every rank must use the same)')
+    p.add_argument('--thr-stages', dest='thr_stages', type=int, default=3, choices=list(range(9)),
+                   help='--quantizer threshold: passes of the threshold fit (a count-adaptive multi-stage exponential fit of the tail of '
+                        '|g|, aiming at numel // cr kept elements); 0: no fit, the fixed threshold --thr-value')
+    p.add_argument('--thr-value', dest='thr_value', type=float, default=None,
+                   help='--quantizer threshold --thr-stages 0: the hard threshold, in [0, FLT_MAX] (required there)')
+    p.add_argument('--thr-cap-percent', dest='thr_cap_percent', type=int, default=150,
+                   help='--quantizer threshold: the wire holds up to this percentage of numel // cr pairs per tensor (the first in index '
+                        'order when more elements exceed the threshold)')
+    p.add_argument('--thr-fit-stride', dest='thr_fit_stride', type=int, default=1, metavar='M',
+                   help='--quantizer threshold: fit on every m-th chunk of 4,096 elements, m the largest power of two <= M that leaves a '
+                        'tensor at least 16 chunks (else 1)')
     p.add_argument('--param-dtype', dest='param_dtype', type=str, default='float32', choices=['float32', 'bfloat16'],
                    help='the dtype the model is cast to.  bfloat16 needs --quantizer mx: its kernels read bfloat16 gradients and write '
                         'bfloat16 means in place (the wire is the float32 one); no other compressor takes them')
@@ -357,6 +369,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     try:
         check_param_dtype(args)
+        if args.quantizer == "threshold" and args.thr_stages == 0 and args.thr_value is None:
+            raise ValueError("--thr-stages 0 needs --thr-value (the fixed threshold)")
     except ValueError as e:
         parser.error(str(e))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:

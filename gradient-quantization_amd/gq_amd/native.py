@@ -1161,6 +1161,54 @@ class EdenBatch(_ItemBatch):
         _check(rc, "gq_eden_compress_batched", EDEN_LIBRARY)
 
 
+# ---- threshold sparsification with a fitted threshold: libgq_thr.so (include/gq_thr.h) -----------------------------------------
+THR_ABI_VERSION = 1
+THR_EXPORTS = ["gq_thr_abi_version", "gq_thr_last_error", "gq_thr_compress_batched", "gq_thr_decode_sum_batched"]
+THR_CHUNK = 4096            # GQ_THR_CHUNK: elements per item
+THR_HEADER_BYTES = 16       # GQ_THR_HEADER_BYTES: kept, found, bits(eta), 0 in front of a section's indices
+THR_MAX_STAGES = 8          # GQ_THR_MAX_STAGES
+THR_NO_INDEX = 0xffffffff   # GQ_THR_NO_INDEX: the index of a slot that holds no pair
+
+THR_LIBRARY = Library("libgq_thr.so", "GQ_THR_LIB_PATH", "gq_thr_", THR_ABI_VERSION, THR_EXPORTS)
+THR_LIB_PATH = THR_LIBRARY.path
+
+
+def thr_lib():
+    return THR_LIBRARY.handle or _load(THR_LIBRARY)
+
+
+class _ThrBatchStruct(ctypes.Structure):      # gq_thr_batch (include/gq_thr.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("stages", ctypes.c_int32),
+                ("min_k", ctypes.c_int32), ("min_cap", ctypes.c_int32), ("min_stride", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_ThrBatchStruct) == 88      # (csrc/thr.hip asserts the same of gq_thr_batch)
+
+
+class ThrBatch(_ItemBatch):
+    """The launches of libgq_thr.so: gq_thr_compress_batched (`stages` reduce / pick pairs that fit the threshold, then count, scan,
+    write -- + the dense decoded tensors and the residual; stages = 0: the caller's threshold) and gq_thr_decode_sum_batched.  sums
+    (float64 [nitems]), state (int32 [nseg * 4]) and counts (int32 [nitems * 2]) are the caller's scratch: written before they are
+    read.  min_k, min_cap, min_stride: the smallest k, cap and fit stride of the table (the library refuses values below 1)."""
+
+    LIBRARY, STRUCT = THR_LIBRARY, _ThrBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, sums=None, state=None, counts=None, stages=0, min_k=1, min_cap=1, min_stride=1):
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems,
+                            (("sums", sums, torch.float64), ("state", state, torch.int32), ("counts", counts, torch.int32)),
+                            stages=int(stages), min_k=int(min_k), min_cap=int(min_cap), min_stride=int(min_stride))
+
+    def compress(self, wire, out=None, ef_scale=None, eta=0.0):
+        """eta: the threshold of fixed mode (stages = 0; not read otherwise).  out: the dense decoded tensors (float32, at the
+        table's out offsets); ef_scale given: error feedback in the same launches (seg_table[:, 7] = error buffers; needs out)."""
+        rc = self.L.gq_thr_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_float(eta),
+                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_thr_compress_batched", THR_LIBRARY)
+
+
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
 KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]

@@ -31,7 +31,8 @@ import warnings
 import torch
 
 from . import exchange, native
-from .compressors import DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, TopKSparsificationCompressor, _next_seed, shared_seeds
+from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, ThresholdSparsificationCompressor,
+                          TopKSparsificationCompressor, _next_seed, shared_seeds)
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
 # addresses as one bytes key and the "all plain f32" flag in one pass; `.data =` for all parameters in another.  A step
@@ -47,7 +48,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
     BatchedDGC, BatchedDrive, BatchedEden, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
-    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec,
+    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -178,6 +179,12 @@ class PSQuantizer(object):
         # around the top-k select (include/gq_dgc.h).  The velocity u and its accumulation v live here, per parameter and user
         # like param.error: param.dgc_u[user], param.dgc_v[user]; v is the error feedback at scale 1, so --ef is excluded.
         self.dgc_m = self._momentum_correction(Compressor, args)
+        if isinstance(Compressor, type) and issubclass(Compressor, ThresholdSparsificationCompressor):
+            # (include/gq_thr.h: float32 tensors only)
+            odd = sorted(set(str(p.dtype) for p in self.parameters if p.dtype != torch.float32))
+            if odd:
+                raise ValueError("the threshold compressor takes float32 parameters only (its kernels read and write float32 "
+                                 "gradients), got %s" % ", ".join(odd))
         factory = codec_factory or quantizer_codec_factory
         self.aggregate_fma = aggregate_fma(args)     # opt-in fused accumulation of the decode-mean (R >= 2 only)
         self.wire_levels = wire_levels_mode(args, _dist_world(process_group)[0])      # "bytes" | "packed6" (6-bit levels where the configuration allows)
@@ -244,7 +251,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -329,6 +336,9 @@ class PSQuantizer(object):
         if ring:
             raise ValueError("momentum_correction is not available in ring mode: a hop compresses the running sum of the users before "
                              "it, not a gradient")
+        if isinstance(Compressor, type) and issubclass(Compressor, ThresholdSparsificationCompressor):
+            raise ValueError("momentum_correction is not available with the threshold compressor: momentum factor masking is built on "
+                             "the top-k wire (--quantizer topk)")
         if not (isinstance(Compressor, type) and issubclass(Compressor, TopKSparsificationCompressor)):
             raise ValueError("momentum_correction needs TopKSparsificationCompressor (--quantizer topk), got %s"
                              % getattr(Compressor, "__name__", Compressor))
@@ -364,6 +374,15 @@ class PSQuantizer(object):
         if not grp.encode([flat], TopKCodec._at(wire, off), 0, 0, ([param.dgc_u[user]], [param.dgc_v[user]]), self.dgc_m):
             raise native.GQNativeError("momentum correction: the gradient of parameter %d must be a float tensor on the current HIP "
                                        "device (there is no CPU path)" % i)
+
+    def kept_counts(self, slot=0):
+        """How the threshold compressor's estimate did in the last record of wire row `slot` (the user's slot of this rank): one
+        (kept, found, eta) per threshold-compressed parameter, in parameter order, read from the wire headers (include/gq_thr.h:
+        kept = min(found, cap) pairs travel, found elements exceeded eta).  [] before the first record or with another compressor.
+        A read of the device wire: it synchronises."""
+        if self._wire is None or not 0 <= slot < self._wire.shape[0]:
+            return []
+        return [c.header(self._wire[slot], self.offsets[i]) for i, c in enumerate(self.codecs) if isinstance(c, ThrCodec)]
 
     # ---- buffers -------------------------------------------------------------------------
     def _ensure_wire(self, device, slots):
@@ -1118,6 +1137,9 @@ class RingQuantizer(PSQuantizer):
         if isinstance(Compressor, type) and issubclass(Compressor, EdenCompressor):
             raise ValueError("the eden compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
                              "which does not hold for a wire whose decode ends with an inverse rotation")
+        if isinstance(Compressor, type) and issubclass(Compressor, ThresholdSparsificationCompressor):
+            raise ValueError("the threshold compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
+                             "and its wire drops what exceeds the threshold beyond the capacity")
         two_phase = args.two_phase
         args.two_phase = False           # ring_quantizer.py has no second phase and no server residual
         try:
