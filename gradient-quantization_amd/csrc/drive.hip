@@ -19,6 +19,9 @@
 // (blk < nb), uniform over the half, and the steps are left on workgroup-uniform tests only: no exchange sits under divergent
 // control flow.  Loads and stores are masked per lane (e0 + k < n).
 // Every launch's arguments depend on the layout alone, and there are no draws: both replay from a HIP graph as they are.
+// stepped   the *_stepped entry points: the same bodies, with the lane's sign byte made once per launch from a device
+//           { seed, step } pair (gqx::stepped_sign_byte) instead of from four words passed by value.  The pair's ADDRESS is the
+//           launch argument: a replay rotates afresh once the step word has moved.
 #include <math.h>
 
 #include "gq_drive.h"
@@ -32,6 +35,7 @@ namespace gqd {
 using gql::aligned16;
 using gql::copy_dense;
 using gql::err_buf;
+using gql::check_rotation;
 using gql::fail;
 using gqx::Hadamard;
 using gqx::lane_xor;
@@ -76,10 +80,12 @@ __device__ __forceinline__ void store8(float *p, const float (&f)[PER_LANE]) {
     *reinterpret_cast<float4 *>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
 }
 
-template <int SCALE, bool EF>
+// Rot: how the launch is told its rotation -- gqx::Signs (the four words, by value) or gqx::Stepped (the address of a device
+// { seed, step } pair): the only difference between a fixed and a stepped launch is how `rotation` below is built
+template <int SCALE, bool EF, class Rot>
 __global__ __launch_bounds__(THREADS) void drive_compress_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                                  uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
-                                                                 const int64_t *__restrict__ dense_table, int ndense, Signs signs) {
+                                                                 const int64_t *__restrict__ dense_table, int ndense, Rot signs) {
     copy_dense<THREADS>(dense_table, ndense, wire);
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
@@ -189,9 +195,10 @@ __global__ __launch_bounds__(THREADS) void drive_compress_kernel(const int64_t *
     }
 }
 
+template <class Rot>
 __global__ __launch_bounds__(THREADS) void drive_decode_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                                const uint8_t *__restrict__ gathered, int64_t stride, int R,
-                                                               float *__restrict__ out, int plain, Signs signs) {
+                                                               float *__restrict__ out, int plain, Rot signs) {
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
@@ -254,15 +261,64 @@ static int check_batch(const gq_drive_batch *b, const char *what, bool compress)
     return GQ_OK;
 }
 
-template <int SCALE>
-static void launch_compress(const gq_drive_batch *b, uint8_t *wire, float ef_scale, float *out, hipStream_t st) {
+// rot: Hadamard::args(b), the fixed words of the descriptor, or gqx::Stepped: the kernels then do not read them
+template <int SCALE, class Rot>
+static void launch_compress(const gq_drive_batch *b, uint8_t *wire, float ef_scale, float *out, Rot rot, hipStream_t st) {
     const dim3 grid((unsigned)b->nitems), block(THREADS);
     if (!isnan(ef_scale))
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_compress_kernel<SCALE, true>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out, ef_scale,
-                           b->dense_table, b->ndense, Hadamard::args(b));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_compress_kernel<SCALE, true, Rot>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
+                           ef_scale, b->dense_table, b->ndense, rot);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_compress_kernel<SCALE, false>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out, 0.0f,
-                           b->dense_table, b->ndense, Hadamard::args(b));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_compress_kernel<SCALE, false, Rot>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
+                           0.0f, b->dense_table, b->ndense, rot);
+}
+
+template <class Rot>
+static void launch_compress(const gq_drive_batch *b, uint8_t *wire, float ef_scale, float *out, Rot rot, hipStream_t st) {
+    if (b->scale_mode == GQ_DRIVE_UNBIASED)
+        launch_compress<GQ_DRIVE_UNBIASED>(b, wire, ef_scale, out, rot, st);
+    else
+        launch_compress<GQ_DRIVE_MSE>(b, wire, ef_scale, out, rot, st);
+}
+
+// the two entry points of a launch kind; stepped: `rotation` is checked and the descriptor's sign words are not read
+static int compress(const char *what, const gq_drive_batch *b, uint8_t *wire, float ef_scale, float *out, bool stepped, const uint64_t *rotation,
+                    void *stream) {
+    int rc = check_batch(b, what, true);
+    if (rc == GQ_OK && stepped) rc = check_rotation(rotation, what);
+    if (rc != GQ_OK) return rc;
+    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
+        return fail(GQ_ERR_INVALID_ARG, "%s: the wire must be a 16-byte aligned device buffer", what);
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (stepped)
+        launch_compress(b, wire, ef_scale, out, gqx::Stepped{rotation}, st);
+    else
+        launch_compress(b, wire, ef_scale, out, Hadamard::args(b), st);
+    GQL_CHECK_LAUNCH(what);
+    return GQ_OK;
+}
+
+static int decode_sum(const char *what, const gq_drive_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
+                      bool stepped, const uint64_t *rotation, void *stream) {
+    int rc = check_batch(b, what, false);
+    if (rc == GQ_OK && stepped) rc = check_rotation(rotation, what);
+    if (rc != GQ_OK) return rc;
+    if (!gathered || !out) return fail(GQ_ERR_INVALID_ARG, "%s: null pointer", what);
+    if (R < 1 || (R > 1 && user_stride_bytes < 0))
+        return fail(GQ_ERR_INVALID_ARG, "%s: R = %d, user stride %lld", what, R, (long long)user_stride_bytes);
+    if (plain && R != 1) return fail(GQ_ERR_INVALID_ARG, "%s: plain is the decode of ONE payload, R = %d", what, R);
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
+    const dim3 grid((unsigned)b->nitems), block(THREADS);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (stepped)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_decode_kernel<gqx::Stepped>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0, gqx::Stepped{rotation});
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_decode_kernel<Signs>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
+                           user_stride_bytes, R, out, plain ? 1 : 0, Hadamard::args(b));
+    GQL_CHECK_LAUNCH(what);
+    return GQ_OK;
 }
 
 }  // namespace gqd
@@ -272,36 +328,20 @@ GQD_API int gq_drive_abi_version(void) { return GQ_DRIVE_ABI_VERSION; }
 GQD_API const char *gq_drive_last_error(void) { return gqd::err_buf; }
 
 GQD_API int gq_drive_compress_batched(const gq_drive_batch *b, uint8_t *wire, float ef_scale, float *out, void *stream) {
-    using namespace gqd;
-    const char *what = "gq_drive_compress_batched";
-    const int rc = check_batch(b, what, true);
-    if (rc != GQ_OK) return rc;
-    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
-        return fail(GQ_ERR_INVALID_ARG, "%s: the wire must be a 16-byte aligned device buffer", what);
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (b->scale_mode == GQ_DRIVE_UNBIASED)
-        launch_compress<GQ_DRIVE_UNBIASED>(b, wire, ef_scale, out, st);
-    else
-        launch_compress<GQ_DRIVE_MSE>(b, wire, ef_scale, out, st);
-    GQL_CHECK_LAUNCH(what);
-    return GQ_OK;
+    return gqd::compress("gq_drive_compress_batched", b, wire, ef_scale, out, false, nullptr, stream);
+}
+
+GQD_API int gq_drive_compress_batched_stepped(const gq_drive_batch *b, const uint64_t *rotation, uint8_t *wire, float ef_scale, float *out,
+                                              void *stream) {
+    return gqd::compress("gq_drive_compress_batched_stepped", b, wire, ef_scale, out, true, rotation, stream);
 }
 
 GQD_API int gq_drive_decode_sum_batched(const gq_drive_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
                                         void *stream) {
-    using namespace gqd;
-    const char *what = "gq_drive_decode_sum_batched";
-    const int rc = check_batch(b, what, false);
-    if (rc != GQ_OK) return rc;
-    if (!gathered || !out) return fail(GQ_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (R < 1 || (R > 1 && user_stride_bytes < 0))
-        return fail(GQ_ERR_INVALID_ARG, "%s: R = %d, user stride %lld", what, R, (long long)user_stride_bytes);
-    if (plain && R != 1) return fail(GQ_ERR_INVALID_ARG, "%s: plain is the decode of ONE payload, R = %d", what, R);
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
-    const dim3 grid((unsigned)b->nitems), block(THREADS);
-    hipLaunchKernelGGL(drive_decode_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), b->seg_table, b->item_seg, gathered,
-                       user_stride_bytes, R, out, plain ? 1 : 0, Hadamard::args(b));
-    GQL_CHECK_LAUNCH(what);
-    return GQ_OK;
+    return gqd::decode_sum("gq_drive_decode_sum_batched", b, gathered, user_stride_bytes, R, out, plain, false, nullptr, stream);
+}
+
+GQD_API int gq_drive_decode_sum_batched_stepped(const gq_drive_batch *b, const uint64_t *rotation, const uint8_t *gathered,
+                                                int64_t user_stride_bytes, int R, float *out, int plain, void *stream) {
+    return gqd::decode_sum("gq_drive_decode_sum_batched_stepped", b, gathered, user_stride_bytes, R, out, plain, true, rotation, stream);
 }

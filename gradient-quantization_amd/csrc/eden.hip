@@ -20,6 +20,9 @@
 // (blk < nb), uniform over the half, and the steps are left on workgroup-uniform tests only: no exchange sits under divergent
 // control flow.  Loads and stores are masked per lane (e0 + k < n).
 // Every launch's arguments depend on the layout alone, and there are no draws: both replay from a HIP graph as they are.
+// stepped   the *_stepped entry points: the same bodies, with the lane's sign byte made once per launch from a device
+//           { seed, step } pair (gqx::stepped_sign_byte) instead of from four words passed by value.  The pair's ADDRESS is the
+//           launch argument: a replay rotates afresh once the step word has moved.
 #include <math.h>
 
 #include "gq_eden.h"
@@ -33,6 +36,7 @@ namespace gqe {
 using gql::aligned16;
 using gql::copy_dense;
 using gql::err_buf;
+using gql::check_rotation;
 using gql::fail;
 using gqx::Hadamard;
 using gqx::lane_xor;
@@ -104,10 +108,12 @@ __device__ __forceinline__ void store8(float *p, const float (&f)[PER_LANE]) {
     *reinterpret_cast<float4 *>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
 }
 
-template <int B, int SCALE, bool EF>
+// Rot: how the launch is told its rotation -- gqx::Signs (the four words, by value) or gqx::Stepped (the address of a device
+// { seed, step } pair): the only difference between a fixed and a stepped launch is how `rotation` below is built
+template <int B, int SCALE, bool EF, class Rot>
 __global__ __launch_bounds__(THREADS) void eden_compress_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                                 uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
-                                                                const int64_t *__restrict__ dense_table, int ndense, Signs signs) {
+                                                                const int64_t *__restrict__ dense_table, int ndense, Rot signs) {
     using T = Table<B>;
     constexpr int CODE_BYTES = GQ_EDEN_BLOCK * B / 8;      // a block's code bytes: B of them per lane
     copy_dense<THREADS>(dense_table, ndense, wire);
@@ -251,10 +257,10 @@ __global__ __launch_bounds__(THREADS) void eden_compress_kernel(const int64_t *_
     }
 }
 
-template <int B>
+template <int B, class Rot>
 __global__ __launch_bounds__(THREADS) void eden_decode_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
                                                               const uint8_t *__restrict__ gathered, int64_t stride, int R,
-                                                              float *__restrict__ out, int plain, Signs signs) {
+                                                              float *__restrict__ out, int plain, Rot signs) {
     using T = Table<B>;
     constexpr int CODE_BYTES = GQ_EDEN_BLOCK * B / 8;
     const int64_t item = blockIdx.x;
@@ -330,30 +336,88 @@ static int check_batch(const gq_eden_batch *b, const char *what, bool compress) 
     return GQ_OK;
 }
 
-template <int B, int SCALE>
-static void launch_compress(const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, hipStream_t st) {
+// rot: Hadamard::args(b), the fixed words of the descriptor, or gqx::Stepped: the kernels then do not read them
+template <int B, int SCALE, class Rot>
+static void launch_compress(const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, Rot rot, hipStream_t st) {
     const dim3 grid((unsigned)b->nitems), block(THREADS);
     if (!isnan(ef_scale))
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(eden_compress_kernel<B, SCALE, true>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out, ef_scale,
-                           b->dense_table, b->ndense, Hadamard::args(b));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(eden_compress_kernel<B, SCALE, true, Rot>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
+                           ef_scale, b->dense_table, b->ndense, rot);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(eden_compress_kernel<B, SCALE, false>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out, 0.0f,
-                           b->dense_table, b->ndense, Hadamard::args(b));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(eden_compress_kernel<B, SCALE, false, Rot>), grid, block, 0, st, b->seg_table, b->item_seg, wire, out,
+                           0.0f, b->dense_table, b->ndense, rot);
 }
 
-template <int B>
-static void launch_compress(const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, hipStream_t st) {
+template <int B, class Rot>
+static void launch_compress(const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, Rot rot, hipStream_t st) {
     if (b->scale_mode == GQ_EDEN_UNBIASED)
-        launch_compress<B, GQ_EDEN_UNBIASED>(b, wire, ef_scale, out, st);
+        launch_compress<B, GQ_EDEN_UNBIASED>(b, wire, ef_scale, out, rot, st);
     else
-        launch_compress<B, GQ_EDEN_MSE>(b, wire, ef_scale, out, st);
+        launch_compress<B, GQ_EDEN_MSE>(b, wire, ef_scale, out, rot, st);
 }
 
-template <int B>
-static void launch_decode(const gq_eden_batch *b, const uint8_t *gathered, int64_t stride, int R, float *out, int plain, hipStream_t st) {
+template <class Rot>
+static void launch_compress(const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, Rot rot, hipStream_t st) {
+    if (b->bits == 2)
+        launch_compress<2>(b, wire, ef_scale, out, rot, st);
+    else if (b->bits == 3)
+        launch_compress<3>(b, wire, ef_scale, out, rot, st);
+    else
+        launch_compress<4>(b, wire, ef_scale, out, rot, st);
+}
+
+template <int B, class Rot>
+static void launch_decode(const gq_eden_batch *b, const uint8_t *gathered, int64_t stride, int R, float *out, int plain, Rot rot, hipStream_t st) {
     const dim3 grid((unsigned)b->nitems), block(THREADS);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(eden_decode_kernel<B>), grid, block, 0, st, b->seg_table, b->item_seg, gathered, stride, R, out, plain,
-                       Hadamard::args(b));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(eden_decode_kernel<B, Rot>), grid, block, 0, st, b->seg_table, b->item_seg, gathered, stride, R, out, plain,
+                       rot);
+}
+
+template <class Rot>
+static void launch_decode(const gq_eden_batch *b, const uint8_t *gathered, int64_t stride, int R, float *out, int plain, Rot rot, hipStream_t st) {
+    if (b->bits == 2)
+        launch_decode<2>(b, gathered, stride, R, out, plain, rot, st);
+    else if (b->bits == 3)
+        launch_decode<3>(b, gathered, stride, R, out, plain, rot, st);
+    else
+        launch_decode<4>(b, gathered, stride, R, out, plain, rot, st);
+}
+
+// the two entry points of a launch kind; stepped: `rotation` is checked and the descriptor's sign words are not read
+static int compress(const char *what, const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, bool stepped, const uint64_t *rotation,
+                    void *stream) {
+    int rc = check_batch(b, what, true);
+    if (rc == GQ_OK && stepped) rc = check_rotation(rotation, what);
+    if (rc != GQ_OK) return rc;
+    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
+        return fail(GQ_ERR_INVALID_ARG, "%s: the wire must be a 16-byte aligned device buffer", what);
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (stepped)
+        launch_compress(b, wire, ef_scale, out, gqx::Stepped{rotation}, st);
+    else
+        launch_compress(b, wire, ef_scale, out, Hadamard::args(b), st);
+    GQL_CHECK_LAUNCH(what);
+    return GQ_OK;
+}
+
+static int decode_sum(const char *what, const gq_eden_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
+                      bool stepped, const uint64_t *rotation, void *stream) {
+    int rc = check_batch(b, what, false);
+    if (rc == GQ_OK && stepped) rc = check_rotation(rotation, what);
+    if (rc != GQ_OK) return rc;
+    if (!gathered || !out) return fail(GQ_ERR_INVALID_ARG, "%s: null pointer", what);
+    if (R < 1 || (R > 1 && user_stride_bytes < 0))
+        return fail(GQ_ERR_INVALID_ARG, "%s: R = %d, user stride %lld", what, R, (long long)user_stride_bytes);
+    if (plain && R != 1) return fail(GQ_ERR_INVALID_ARG, "%s: plain is the decode of ONE payload, R = %d", what, R);
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (stepped)
+        launch_decode(b, gathered, user_stride_bytes, R, out, plain ? 1 : 0, gqx::Stepped{rotation}, st);
+    else
+        launch_decode(b, gathered, user_stride_bytes, R, out, plain ? 1 : 0, Hadamard::args(b), st);
+    GQL_CHECK_LAUNCH(what);
+    return GQ_OK;
 }
 
 }  // namespace gqe
@@ -363,42 +427,21 @@ GQE_API int gq_eden_abi_version(void) { return GQ_EDEN_ABI_VERSION; }
 GQE_API const char *gq_eden_last_error(void) { return gqe::err_buf; }
 
 GQE_API int gq_eden_compress_batched(const gq_eden_batch *b, uint8_t *wire, float ef_scale, float *out, void *stream) {
-    using namespace gqe;
-    const char *what = "gq_eden_compress_batched";
-    const int rc = check_batch(b, what, true);
-    if (rc != GQ_OK) return rc;
-    if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
-        return fail(GQ_ERR_INVALID_ARG, "%s: the wire must be a 16-byte aligned device buffer", what);
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (b->bits == 2)
-        launch_compress<2>(b, wire, ef_scale, out, st);
-    else if (b->bits == 3)
-        launch_compress<3>(b, wire, ef_scale, out, st);
-    else
-        launch_compress<4>(b, wire, ef_scale, out, st);
-    GQL_CHECK_LAUNCH(what);
-    return GQ_OK;
+    return gqe::compress("gq_eden_compress_batched", b, wire, ef_scale, out, false, nullptr, stream);
+}
+
+GQE_API int gq_eden_compress_batched_stepped(const gq_eden_batch *b, const uint64_t *rotation, uint8_t *wire, float ef_scale, float *out,
+                                             void *stream) {
+    return gqe::compress("gq_eden_compress_batched_stepped", b, wire, ef_scale, out, true, rotation, stream);
 }
 
 GQE_API int gq_eden_decode_sum_batched(const gq_eden_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
                                        void *stream) {
-    using namespace gqe;
-    const char *what = "gq_eden_decode_sum_batched";
-    const int rc = check_batch(b, what, false);
-    if (rc != GQ_OK) return rc;
-    if (!gathered || !out) return fail(GQ_ERR_INVALID_ARG, "%s: null pointer", what);
-    if (R < 1 || (R > 1 && user_stride_bytes < 0))
-        return fail(GQ_ERR_INVALID_ARG, "%s: R = %d, user stride %lld", what, R, (long long)user_stride_bytes);
-    if (plain && R != 1) return fail(GQ_ERR_INVALID_ARG, "%s: plain is the decode of ONE payload, R = %d", what, R);
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (b->bits == 2)
-        launch_decode<2>(b, gathered, user_stride_bytes, R, out, plain ? 1 : 0, st);
-    else if (b->bits == 3)
-        launch_decode<3>(b, gathered, user_stride_bytes, R, out, plain ? 1 : 0, st);
-    else
-        launch_decode<4>(b, gathered, user_stride_bytes, R, out, plain ? 1 : 0, st);
-    GQL_CHECK_LAUNCH(what);
-    return GQ_OK;
+    return gqe::decode_sum("gq_eden_decode_sum_batched", b, gathered, user_stride_bytes, R, out, plain, false, nullptr, stream);
 }
+
+GQE_API int gq_eden_decode_sum_batched_stepped(const gq_eden_batch *b, const uint64_t *rotation, const uint8_t *gathered,
+                                               int64_t user_stride_bytes, int R, float *out, int plain, void *stream) {
+    return gqe::decode_sum("gq_eden_decode_sum_batched_stepped", b, gathered, user_stride_bytes, R, out, plain, true, rotation, stream);
+}
+

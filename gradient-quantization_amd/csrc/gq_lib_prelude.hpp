@@ -23,6 +23,13 @@ static int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+// the { seed, step } pair of a stepped launch (libgq_drive.so, libgq_eden.so: SIGNS, STEPPED of their headers)
+static inline int check_rotation(const uint64_t *rotation, const char *what) {
+    if (!rotation || (reinterpret_cast<uintptr_t>(rotation) & 7) != 0)
+        return fail(GQ_ERR_INVALID_ARG, "%s: rotation must be the 8-byte aligned address of a device { seed, step } pair", what);
+    return GQ_OK;
+}
+
 #define GQL_CHECK_LAUNCH(what)                                                                       \
     do {                                                                                             \
         hipError_t e__ = hipGetLastError();                                                          \

@@ -28,6 +28,33 @@ __device__ __forceinline__ uint32_t sign_byte(const Signs &s) {
     return (uint32_t)(word >> (8 * (l & 7u))) & 0xffu;
 }
 
+// A lane's sign byte, ready made (stepped_sign_byte below): what Hadamard is built from when the words are not a launch argument.
+struct SignByte {
+    uint32_t v;
+};
+
+// SIGNS, STEPPED (include/gq_drive.h, include/gq_eden.h): `rotation` is a device { seed, step } pair, word k of the launch is output
+// 4 * step + k of the splitmix64 stream started at seed.  A lane needs the word of its quarter only: the pair is one plain
+// wave-uniform read, then one finaliser (two 64-bit multiplications) and the lane's byte.  Once per launch: a caller keeps this
+// out of its item loop.
+__device__ __forceinline__ SignByte stepped_sign_byte(const uint64_t *__restrict__ rotation) {
+    constexpr uint64_t G = 0x9E3779B97F4A7C15ull;
+    const uint64_t seed = rotation[0], step = rotation[1];
+    const uint32_t l = threadIdx.x & 31u;
+    const uint32_t q = l >> 3;
+    const uint64_t first = seed + (4 * step + 1) * G;      // (uniform; all of it mod 2^64)
+    uint64_t z = first + (q == 0 ? 0 : q == 1 ? G : q == 2 ? 2 * G : 3 * G);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return SignByte{(uint32_t)(z >> (8 * (l & 7u))) & 0xffu};
+}
+
+// what a stepped launch takes in the place of Signs: the pair's address, which never changes
+struct Stepped {
+    const uint64_t *pair;
+};
+
 // the value of lane ^ M, M = 1, 2, 4, 8 or 16 (all inside a 32-lane half)
 template <int M>
 __device__ __forceinline__ float lane_xor(float v) {
@@ -80,6 +107,8 @@ struct Hadamard {
     static constexpr bool EVERY_LANE = true;      // the cross-lane stages: every lane executes them and selects afterwards
     uint32_t sbyte;
     __device__ __forceinline__ explicit Hadamard(const Signs &s) : sbyte(sign_byte(s)) {}
+    __device__ __forceinline__ explicit Hadamard(const SignByte &b) : sbyte(b.v) {}
+    __device__ __forceinline__ explicit Hadamard(const Stepped &r) : Hadamard(stepped_sign_byte(r.pair)) {}      // (drive.hip / eden.hip)
     // w -> x' (rot; otherwise x' = w)
     __device__ __forceinline__ const HadLane &forward(const HadLane &w, HadLane &x, bool rot) const {
 #pragma unroll

@@ -791,15 +791,29 @@ class DriveCodec(_SparseCodec):
     """DriveCompressor on the HIP kernels (libgq_drive.so).  Wire per tensor: the sign bit of every coordinate of the rotated
     256-element blocks (the last block zero-padded), then one f32 scale per block -- drive_section_bytes, 1.125 bits per element.
     The decode ends with an inverse rotation, so the wire does not carry the decoded tensor itself.  No draws.  Every call is a
-    one-tensor BatchedDrive; roundtrip / encode_decode_into return the compress launch's own dense decode."""
+    one-tensor BatchedDrive; roundtrip / encode_decode_into return the compress launch's own dense decode.
+    stepped (the compressor's rotation is 'step'): `rotation`, the device { seed, step } pair a quantizer hands the codec, goes
+    to every launch (include/gq_drive.h: SIGNS, STEPPED).  Without a pair -- a codec used on its own -- the launches are the fixed
+    ones under the seed's words, which is step 0."""
+
+    rotation = None      # the { seed, step } pair (device int64 [1, 2]) of a stepped codec inside a quantizer
 
     def __init__(self, compressor, numel, shape):
         self.c, self.numel, self.shape = compressor, numel, shape
         if numel < 1:
             raise ValueError("DriveCodec: a tensor of %d elements" % numel)
         self.scale_mode = native.DRIVE_SCALES[compressor.scale]
-        self.signs = tuple(int(w) for w in compressor.signs)
+        self._rotation_of(compressor)
         self.nbytes = drive_section_bytes(numel)
+
+    def _rotation_of(self, compressor):
+        self.signs = tuple(int(w) for w in compressor.signs)
+        self.stepped = getattr(compressor, "rotation", "fixed") == "step"
+
+    def _batched1(self, dev):
+        grp = _SparseCodec._batched1(self, dev)
+        grp.rotation = self.rotation      # (the quantizer's pair, or None: step 0)
+        return grp
 
     def _wire_bytes(self):
         return self.nbytes      # (never empty: numel >= 1)
@@ -834,7 +848,7 @@ class EdenCodec(DriveCodec):
             raise ValueError("EdenCodec: a tensor of %d elements" % numel)
         self.bits = int(compressor.bits)
         self.scale_mode = native.EDEN_SCALES[compressor.scale]
-        self.signs = tuple(int(w) for w in compressor.signs)
+        self._rotation_of(compressor)
         self.nbytes = eden_section_bytes(numel, self.bits)
 
 
@@ -1096,6 +1110,8 @@ class _BatchedBase(object):
         batch = self._batch if part is None else self._range(part[0], part[1])
         if batch is not None:
             kw = {"tail": tail} if tail is not None else {}      # (BatchedHSQ only: see takes_tail)
+            if self.rotation is not None:
+                kw["rotation"] = self.rotation                   # (BatchedDrive / BatchedEden in step mode)
             if getattr(self, "fma", False) and R >= 2 and not plain:
                 batch.decode(gathered, R, out, fma=True, **kw)      # (BatchedHSQ only: the quantizer sets `fma` on its HSQ groups)
             else:
@@ -1103,6 +1119,7 @@ class _BatchedBase(object):
         return views
 
     takes_tail = False      # the group's decode-mean launch can take the aggregate's small per-step work along (native.StepTail)
+    rotation = None         # BatchedDrive / BatchedEden in step mode: the quantizer's { seed, step } pair, read by every launch
 
     def upload_layout(self):
         """Device header with the layout columns only (no tensor pointers): enough for decode_mean,
@@ -1669,7 +1686,10 @@ class _ItemGroup(_BatchedBase):
         """The decode-mean launch into a caller's buffer (_SparseCodec: a one-tensor group, its section at offset 0 of the rows)."""
         if not self.ready:
             self.upload_layout()
-        self._batch.decode(gathered, R, out, plain=plain)
+        if self.rotation is not None:
+            self._batch.decode(gathered, R, out, plain=plain, rotation=self.rotation)
+        else:
+            self._batch.decode(gathered, R, out, plain=plain)
 
     def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
         """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode (the reference's signed
@@ -2036,7 +2056,10 @@ class BatchedDrive(_ItemGroup):
     gq_drive_decode_sum_batched launch (include/gq_drive.h).  No draws and no scratch: both replay from a HIP graph with nothing
     to step.  The compress also writes the dense decode where a caller asks for it (the two-phase re-compress returns it); with
     error feedback it updates the gradient and the residual in the same launch.  The decode-mean adds the payloads in the rotated
-    domain and rotates the mean back once -- which is why one group, and every user of it, has one set of sign words."""
+    domain and rotates the mean back once -- which is why one group, and every user of it, has one set of sign words.
+    Step mode (the codecs' `stepped`): the quantizer sets `rotation`, its { seed, step } pair, and both launches are the *_stepped
+    ones, which read the words of the current step through that address -- still nothing in a launch changes, so the group stays
+    graphable; the quantizer's aggregate moves the step word.  Without a pair the launches are the fixed ones: step 0."""
 
     @staticmethod
     def eligible(codec):
@@ -2044,7 +2067,7 @@ class BatchedDrive(_ItemGroup):
 
     @staticmethod
     def group_key(codec):
-        return (codec.scale_mode,) + tuple(codec.signs)
+        return (codec.scale_mode, int(codec.stepped)) + tuple(codec.signs)
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         # an item is a run of elements (numel >= 1: never none); 16-byte aligned views in the output buffer: the launches store float4 there
@@ -2052,7 +2075,7 @@ class BatchedDrive(_ItemGroup):
                                       lambda cd: -(-cd.numel // native.MX_ITEM_ELEMS), {}, 4)
         c0 = self.codecs[0]
         self.random = False
-        self.scale_mode, self.signs = c0.scale_mode, c0.signs
+        self.scale_mode, self.signs, self.stepped = c0.scale_mode, c0.signs, c0.stepped
         self._batch = self._make_batch(nseg, item)
 
     def _make_batch(self, nseg, item):
@@ -2067,7 +2090,7 @@ class BatchedDrive(_ItemGroup):
             return False
         if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None, self.rotation)
         return True
 
 
@@ -2084,7 +2107,7 @@ class BatchedEden(BatchedDrive):
 
     @staticmethod
     def group_key(codec):
-        return (codec.bits, codec.scale_mode) + tuple(codec.signs)
+        return (codec.bits, codec.scale_mode, int(codec.stepped)) + tuple(codec.signs)
 
     def _make_batch(self, nseg, item):
         self.bits = self.codecs[0].bits

@@ -623,6 +623,15 @@ class MXCompressor(object):
         return signature
 
 
+def _rotation_mode(args, name):
+    """args.drive_rotation / args.eden_rotation: 'fixed' (also when absent) or 'step'."""
+    mode = getattr(args, name, None)
+    mode = "fixed" if mode is None else mode
+    if mode not in ("fixed", "step"):
+        raise ValueError("%s must be 'fixed' or 'step', got %r" % (name, mode))
+    return mode
+
+
 class DriveCompressor(object):
     """The rotated 1-bit compressor (DRIVE, Vargaftik et al. 2021; no counterpart in the reference's catalogue): a block of 256
     elements is rotated by a randomized Hadamard matrix, the sign of every rotated coordinate is kept and one f32 scale per block --
@@ -631,16 +640,31 @@ class DriveCompressor(object):
     exact in the direction of x, so the mean over users averages out -- or 'mse' -- S = |Rx|_1 / 256: the least single-shot error,
     what error feedback wants.  args.drive_seed (default 1) gives the four sign words (MXCompressor.sign_words: every rank with
     the same arguments has the same signs; one decode-mean needs every payload under the same signs).
+    args.drive_rotation: 'fixed' (the default, also when absent) -- the sign words of the seed at every step: over a run the
+    compressor is a deterministic function of the gradient -- or 'step' -- the words of step t are outputs 4t ... 4t + 3 of the
+    seed's splitmix64 stream (rotation_words; include/gq_drive.h: SIGNS, STEPPED), a fresh rotation every round, which is what
+    makes the 'unbiased' decodes average out over ROUNDS.  The step is a device { seed, step } pair that a quantizer owns and moves
+    once per apply(); a bare DriveCompressor(...).compress() outside a quantizer has no pair and stays at step 0, which is the fixed
+    rotation of the seed.
     compress returns the dense decode and decompress is the identity, as for MXCompressor.  HIP kernels only (libgq_drive.so): a
     float32 tensor on the device."""
 
     SCALES = ("unbiased", "mse")
+    ROTATIONS = ("fixed", "step")
+
+    @staticmethod
+    def rotation_words(seed, step):
+        """The four sign words of (seed, step): outputs 4 step ... 4 step + 3 of splitmix64 started at seed, i.e. sign_words of the
+        seed moved on by 4 step increments.  Step 0: MXCompressor.sign_words(seed)."""
+        M = (1 << 64) - 1
+        return MXCompressor.sign_words(((int(seed) & M) + 4 * (int(step) & M) * 0x9E3779B97F4A7C15) & M)
 
     def __init__(self, size, shape, args):
         scale = getattr(args, "drive_scale", None) or "unbiased"
         if scale not in self.SCALES:
             raise ValueError("drive_scale must be 'unbiased' or 'mse', got %r" % (scale,))
         self.scale = scale
+        self.rotation = _rotation_mode(args, "drive_rotation")
         seed = getattr(args, "drive_seed", None)
         self.seed = 1 if seed is None else int(seed)
         self.signs = MXCompressor.sign_words(self.seed)
@@ -673,11 +697,15 @@ class EdenCompressor(object):
     is unbiased over the rotation's randomness and exact in the direction of x -- or 'mse' -- the least-squares scale.
     args.eden_seed (default 1) gives the four sign words (MXCompressor.sign_words: every rank with the same arguments has the same
     signs; one decode-mean needs every payload under the same signs).
+    args.eden_rotation: 'fixed' (the default, also when absent) or 'step' -- DriveCompressor's drive_rotation, word for word: a
+    fresh rotation every round from a { seed, step } pair the quantizer owns; a bare EdenCompressor(...).compress() stays at step 0.
     compress returns the dense decode and decompress is the identity, as for DriveCompressor.  HIP kernels only (libgq_eden.so): a
     float32 tensor on the device."""
 
     SCALES = ("unbiased", "mse")
     BITS = (2, 3, 4)
+    ROTATIONS = DriveCompressor.ROTATIONS
+    rotation_words = staticmethod(DriveCompressor.rotation_words)
 
     def __init__(self, size, shape, args):
         bits = getattr(args, "eden_bits", None)
@@ -689,6 +717,7 @@ class EdenCompressor(object):
         if scale not in self.SCALES:
             raise ValueError("eden_scale must be 'unbiased' or 'mse', got %r" % (scale,))
         self.scale = scale
+        self.rotation = _rotation_mode(args, "eden_rotation")
         seed = getattr(args, "eden_seed", None)
         self.seed = 1 if seed is None else int(seed)
         self.signs = MXCompressor.sign_words(self.seed)

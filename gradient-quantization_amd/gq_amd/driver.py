@@ -185,6 +185,14 @@ def build_parser():
                         "error (what --ef wants); not in ring mode")
     p.add_argument('--drive-seed', dest='drive_seed', type=int, default=1,
                    help='--quantizer drive: the seed of the four sign words of its rotation (every rank must use the same)')
+    p.add_argument('--drive-rotation', dest='drive_rotation', type=str, default='fixed', choices=['fixed', 'step'],
+                   help="--quantizer drive: 'fixed' -- the sign words of --drive-seed at every step -- or 'step' -- a fresh rotation every "
+                        "step, drawn from the seed's stream by a step counter all ranks share.  'step' is what the 'unbiased' scale wants "
+                        "(its errors then average out over steps as well as users); 'mse' with --ef does not need it.  --ef works with either")
+    p.add_argument('--eden-rotation', dest='eden_rotation', type=str, default='fixed', choices=['fixed', 'step'],
+                   help="--quantizer eden: 'fixed' -- the sign words of --eden-seed at every step -- or 'step' -- a fresh rotation every "
+                        "step, drawn from the seed's stream by a step counter all ranks share.  'step' is what the 'unbiased' scale wants "
+                        "(its errors then average out over steps as well as users); 'mse' with --ef does not need it.  --ef works with either")
     p.add_argument('--eden-bits', dest='eden_bits', type=int, default=4, choices=[2, 3, 4],
                    help='--quantizer eden: bits per element of the rotated blocks (the nearest of 2^bits Lloyd-Max centroids of N(0,1); '
                         'one bit is --quantizer drive); the wire is bits + 0.125 bits per element')

@@ -636,13 +636,19 @@ class _ItemBatch(_Tables):
         """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
         return type(self)(seg_table, item_seg, nseg, nitems)
 
-    def decode(self, gathered, R, out, plain=False):
-        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride."""
+    def decode(self, gathered, R, out, plain=False, rotation=None):
+        """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride.
+        rotation (DriveBatch / EdenBatch only): the { seed, step } pair -- the <prefix>decode_sum_batched_stepped launch."""
         assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
         stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
-        rc = self._decode(self.ref, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R),
-                          _dev_ptr(out, self.dtype, "out"), ctypes.c_int(1 if plain else 0), _stream())
-        _check(rc, self._decode_name, self.LIBRARY)
+        args = (_dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R), _dev_ptr(out, self.dtype, "out"),
+                ctypes.c_int(1 if plain else 0), _stream())
+        if rotation is None:
+            name, rc = self._decode_name, self._decode(self.ref, *args)
+        else:
+            name = self._decode_name + "_stepped"
+            rc = getattr(self.L, name)(self.ref, _rotation_ptr(rotation), *args)
+        _check(rc, name, self.LIBRARY)
 
 
 # ---- top-k sparsification: libgq_topk.so (include/gq_topk.h) ----------------------------------------------------------
@@ -1067,7 +1073,8 @@ class MXRBatch(MXBatch):
 
 # ---- the rotated 1-bit compressor (DRIVE): libgq_drive.so (include/gq_drive.h) -----------------------------------------------------
 DRIVE_ABI_VERSION = 1
-DRIVE_EXPORTS = ["gq_drive_abi_version", "gq_drive_last_error", "gq_drive_compress_batched", "gq_drive_decode_sum_batched"]
+DRIVE_EXPORTS = ["gq_drive_abi_version", "gq_drive_last_error", "gq_drive_compress_batched", "gq_drive_decode_sum_batched",
+                 "gq_drive_compress_batched_stepped", "gq_drive_decode_sum_batched_stepped"]
 DRIVE_BLOCK = 256           # GQ_DRIVE_BLOCK: elements that share a scale (a rotation block); an item is MX_ITEM_ELEMS
 DRIVE_UNBIASED, DRIVE_MSE = 0, 1      # GQ_DRIVE_UNBIASED / GQ_DRIVE_MSE
 DRIVE_SCALES = {"unbiased": DRIVE_UNBIASED, "mse": DRIVE_MSE}
@@ -1080,6 +1087,25 @@ def drive_lib():
     return DRIVE_LIBRARY.handle or _load(DRIVE_LIBRARY)
 
 
+def _rotation_ptr(rotation):
+    """The { seed, step } pair of a stepped launch: a device int64 [1, 2] tensor (include/gq_drive.h: SIGNS, STEPPED)."""
+    if not (isinstance(rotation, torch.Tensor) and rotation.dtype == torch.int64 and tuple(rotation.shape) == (1, 2)):
+        raise TypeError("rotation must be a device int64 [1, 2] tensor, the { seed, step } pair")
+    return _dev_ptr(rotation, torch.int64, "rotation")
+
+
+def _rotated_compress(batch, name, wire, out, ef_scale, rotation):
+    """DriveBatch.compress / EdenBatch.compress: the entry point `name`, or with a rotation pair `name`_stepped."""
+    args = (_dev_ptr(wire, torch.uint8, "wire"), ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+    if rotation is None:
+        rc = getattr(batch.L, name)(batch.ref, *args)
+    else:
+        name += "_stepped"
+        rc = getattr(batch.L, name)(batch.ref, _rotation_ptr(rotation), *args)
+    _check(rc, name, batch.LIBRARY)
+
+
 class _DriveBatchStruct(ctypes.Structure):    # gq_drive_batch (include/gq_drive.h): gq_mxr_batch's layout, scale_mode for format
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
                 ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
@@ -1089,7 +1115,9 @@ class _DriveBatchStruct(ctypes.Structure):    # gq_drive_batch (include/gq_drive
 class DriveBatch(_ItemBatch):
     """The two launches of libgq_drive.so: gq_drive_compress_batched (sign bits of the rotated blocks and one f32 scale per block, +
     the dense decode and the residual) and gq_drive_decode_sum_batched (the mean in the rotated domain, one inverse rotation).
-    No scratch and no draws.  scale_mode: DRIVE_UNBIASED or DRIVE_MSE; signs: the four 64-bit sign words (gq_mxr.h's)."""
+    No scratch and no draws.  scale_mode: DRIVE_UNBIASED or DRIVE_MSE; signs: the four 64-bit sign words (gq_mxr.h's).
+    compress / decode with rotation= (a device int64 [1, 2] tensor, the { seed, step } pair of include/gq_drive.h's SIGNS, STEPPED):
+    the *_stepped entry points, which take the words of the step they find in the pair and do not read `signs`."""
 
     LIBRARY, STRUCT = DRIVE_LIBRARY, _DriveBatchStruct
 
@@ -1102,18 +1130,16 @@ class DriveBatch(_ItemBatch):
     def part(self, seg_table, item_seg, nseg, nitems):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.scale_mode, self.signs)
 
-    def compress(self, wire, out=None, ef_scale=None):
+    def compress(self, wire, out=None, ef_scale=None, rotation=None):
         """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers)."""
-        rc = self.L.gq_drive_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
-                                              ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                              _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_drive_compress_batched", DRIVE_LIBRARY)
+        (seg_table[:, 7] = error buffers); rotation: see the class."""
+        _rotated_compress(self, "gq_drive_compress_batched", wire, out, ef_scale, rotation)
 
 
 # ---- the rotated 2- / 3- / 4-bit compressor (EDEN): libgq_eden.so (include/gq_eden.h) ----------------------------------------------
 EDEN_ABI_VERSION = 1
-EDEN_EXPORTS = ["gq_eden_abi_version", "gq_eden_last_error", "gq_eden_compress_batched", "gq_eden_decode_sum_batched"]
+EDEN_EXPORTS = ["gq_eden_abi_version", "gq_eden_last_error", "gq_eden_compress_batched", "gq_eden_decode_sum_batched",
+                "gq_eden_compress_batched_stepped", "gq_eden_decode_sum_batched_stepped"]
 EDEN_BLOCK = 256            # GQ_EDEN_BLOCK: elements that share a scale (a rotation block); an item is MX_ITEM_ELEMS
 EDEN_UNBIASED, EDEN_MSE = 0, 1        # GQ_EDEN_UNBIASED / GQ_EDEN_MSE
 EDEN_SCALES = {"unbiased": EDEN_UNBIASED, "mse": EDEN_MSE}
@@ -1138,7 +1164,7 @@ class EdenBatch(_ItemBatch):
     """The two launches of libgq_eden.so: gq_eden_compress_batched (b-bit Lloyd-Max codes of the rotated blocks and one f32 scale per
     block, + the dense decode and the residual) and gq_eden_decode_sum_batched (the mean in the rotated domain, one inverse
     rotation).  No scratch and no draws.  bits: 2, 3 or 4; scale_mode: EDEN_UNBIASED or EDEN_MSE; signs: the four 64-bit sign
-    words (gq_mxr.h's)."""
+    words (gq_mxr.h's).  rotation= on compress / decode: DriveBatch's, on gq_eden_*_stepped."""
 
     LIBRARY, STRUCT = EDEN_LIBRARY, _EdenBatchStruct
 
@@ -1152,13 +1178,10 @@ class EdenBatch(_ItemBatch):
     def part(self, seg_table, item_seg, nseg, nitems):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.bits, self.s.scale_mode, self.signs)
 
-    def compress(self, wire, out=None, ef_scale=None):
+    def compress(self, wire, out=None, ef_scale=None, rotation=None):
         """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers)."""
-        rc = self.L.gq_eden_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
-                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_eden_compress_batched", EDEN_LIBRARY)
+        (seg_table[:, 7] = error buffers); rotation: see DriveBatch."""
+        _rotated_compress(self, "gq_eden_compress_batched", wire, out, ef_scale, rotation)
 
 
 # ---- threshold sparsification with a fitted threshold: libgq_thr.so (include/gq_thr.h) -----------------------------------------

@@ -271,6 +271,13 @@ class PSQuantizer(object):
         # words.  The launches' arguments never change -- they replay from a HIP graph -- and the draws are fresh every
         # step whatever the gradients are (the reference draws per call: probabilistic_scalar_compressor.py:22-26).
         self._rng_state = None
+        # drive_rotation / eden_rotation = 'step' (include/gq_drive.h: SIGNS, STEPPED): ONE { seed, step } pair for the whole parameter
+        # list -- the compressor's seed, step 0, no rank in it: every rank rotates alike -- which IS the quantizer's _rng_state (these
+        # compressors draw nothing else), so the launches that step the draws' words move it once per aggregate: the decode's step
+        # tail, gq_mean_rows, or rng_step when there is neither.  Every group and every per-tensor codec reads it through its address.
+        stepped = [c for c in self.compressors if getattr(c, "rotation", None) == "step"]
+        self._rotation_seed = int(stepped[0].seed) if stepped else None
+        self._rotation_start = 0      # the step word a pair is made with (set_rotation_step before the first record)
         self._ticket = None          # gq_hsq_levels_decode_batched's last-workgroup counter (one device word, zero between launches)
         self._rec_graphs = _GraphCache(self.MAX_ADDRESS_GRAPHS)    # (slot, user, wire, gradient addresses) -> [sightings, graph or None, headers]
         self._apply_graphs = _GraphCache()   # (users recorded, wire, output-buffer turns) -> [sightings, graph or None, decoded list]
@@ -407,6 +414,43 @@ class PSQuantizer(object):
 
     def wire_bytes_per_user(self):
         return self.user_bytes
+
+    def _rotation_pair(self, device):
+        """Step mode: the quantizer's { seed, step } pair on `device` (int64 [1, 2]; made by the first eager record, never under
+        stream capture: its address is baked into every graph), handed to every Drive / Eden codec and group."""
+        if self._rng_state is None or self._rng_state.device != device:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the rotation pair is made by the first eager record, not under stream capture")
+            signed = lambda w: (int(w) & (2 ** 64 - 1)) - (2 ** 64 if int(w) & 2 ** 63 else 0)
+            step = self.rotation_step()      # (a pair that moves to another device keeps its step)
+            self._rng_state = torch.tensor([[signed(self._rotation_seed), signed(step)]], dtype=torch.int64).to(device)
+            for c in self.codecs:
+                if getattr(c, "stepped", False):
+                    c.rotation = self._rng_state
+            for g in self._groups:
+                if g[2] is not None and getattr(g[2], "stepped", False):
+                    g[2].rotation = self._rng_state
+        return self._rng_state
+
+    def rotation_step(self):
+        """Step mode: the step word of the rotation pair, i.e. the aggregates so far (+ what set_rotation_step set).  A read of
+        device memory: it synchronises."""
+        if self._rotation_seed is None:
+            raise ValueError("rotation_step: the compressor's rotation is fixed (drive_rotation / eden_rotation = 'step' steps it)")
+        if self._rng_state is None:
+            return self._rotation_start
+        return int(self._rng_state[0, 1].item()) & (2 ** 64 - 1)
+
+    def set_rotation_step(self, t):
+        """Step mode: set the step word (a resume: every rank must set the same).  The pair keeps its address, so captured graphs
+        go on replaying and rotate by the words of step t next."""
+        if self._rotation_seed is None:
+            raise ValueError("set_rotation_step: the compressor's rotation is fixed (drive_rotation / eden_rotation = 'step' steps it)")
+        t = int(t) & (2 ** 64 - 1)
+        if self._rng_state is None:
+            self._rotation_start = t
+        else:
+            self._rng_state[0, 1] = t - (2 ** 64 if t & 2 ** 63 else 0)
 
     RNG_SLOTS = 17      # { seed, step } pairs per group: 16 user slots + the two-phase re-compress (the last one)
     TWO_PHASE_RNG_SLOT = RNG_SLOTS - 1
@@ -615,6 +659,8 @@ class PSQuantizer(object):
                         self._capture_step(fent, ent[2], all_grads, wire, slot, user, salt, scale, dev)
                 return
         self.record_paths["eager"] += 1
+        if self._rotation_seed is not None and dev.type == "cuda":
+            self._rotation_pair(dev)      # (step mode: the per-tensor route reads it too)
         skip = self._record_launches(all_grads, wire, slot, user, salt, scale, draws, dev)
         if len(skip) == self.num_layers:     # the usual case: everything went through the multi-tensor launches
             self.recorded += 1
@@ -710,6 +756,8 @@ class PSQuantizer(object):
             self._ticket_for(dev)      # (allocated and zeroed HERE, eagerly: a first use under stream capture would put it in a graph's pool)
         if getattr(obj, "counter", False) and len(self._groups) * self.RNG_SLOTS <= 256:
             obj.rng_pairs = self._rng_pairs_for(dev, self._groups.index(grp))
+        if getattr(obj, "stepped", False) and dev.type == "cuda":
+            obj.rotation = self._rotation_pair(dev)
         return obj
 
     def _ticket_for(self, dev):
@@ -864,11 +912,13 @@ class PSQuantizer(object):
         o = self._draw_off[i]
         return {"r": draws[0][o:o + self.codecs[i].draw_count()]}
 
-    def _decode_all(self, gathered, two_phase, pending=(), plain=False, resets=None, fused_levels=False, phase2_headers=None):
+    def _decode_all(self, gathered, two_phase, pending=(), plain=False, resets=None, fused_levels=False, phase2_headers=None,
+                    hold_step=False):
         """Mean of the R = gathered.shape[0] user payloads for every parameter (ps_quantizer.py:47-61),
         as a list of tensors in parameter order.  `pending`: the transfers that fill `gathered`
         (exchange.WireExchange.start) -- one, or one per byte range for a split / pipelined exchange, in which case the
-        tensors of a range are decoded while the ranges behind it are still in flight."""
+        tensors of a range are decoded while the ranges behind it are still in flight.
+        hold_step: leave the { seed, step } words where they are (a trial decode of payloads that will be decoded again)."""
         R = gathered.shape[0]
         done = {}
         pending = list(pending)
@@ -892,7 +942,7 @@ class PSQuantizer(object):
         # that can take it (native.StepTail: gq_hsq_decode_sum_batched_tail): one kernel and one boundary less per step.
         # Not with a chunked exchange (several decode launches per group), not with two-phase (its re-compress draws from
         # the step words and folds into the accumulators AFTER this decode).
-        step_rng = self._rng_state is not None and on_gpu     # one step of the device draws per aggregate (GQ_RANDOM_DEVICE_COUNTER)
+        step_rng = self._rng_state is not None and on_gpu and not hold_step     # one step of the device draws per aggregate (GQ_RANDOM_DEVICE_COUNTER)
         dense_job = None
         if len(self.dense_idx) >= 2:
             # identity tensors: two-phase / error feedback leave them unchanged (roundtrip == clone)
@@ -974,6 +1024,11 @@ class PSQuantizer(object):
                     continue
                 gs = dec
             sources.append((idxs, gs))
+        # step mode: the rotation moves behind the LAST launch that reads it.  A per-tensor second phase (below: `single` is complete
+        # by now) comes after every other launch of the aggregate, so the step is then a launch of its own behind it.
+        late_step = step_rng and self._rotation_seed is not None and two_phase and bool(single)
+        if late_step:
+            step_rng = False
         if dense_job is not None:
             rows, k = dense_job
             if rows is None:
@@ -1038,6 +1093,8 @@ class PSQuantizer(object):
                     else:
                         g = codec.roundtrip(g, 0, **kw)
                 done[i] = g
+        if late_step:       # (step mode: behind the per-tensor second phase)
+            native.rng_step(self._rng_state)
         return [done[i] for i in range(self.num_layers)]
 
     def apply(self, refresh_grads=False):
@@ -1051,7 +1108,7 @@ class PSQuantizer(object):
             if self.exchange_mode == "auto":
                 def step(mode):
                     buf, pend = ex.start(mode, self.recorded, self.cut)
-                    self._decode_all(buf, False, pend)
+                    self._decode_all(buf, False, pend, hold_step=self._rotation_seed is not None)      # (step mode: the real decode is still to come)
                 self.exchange_mode = ex.autotune(
                     step, preflight=lambda mode: ex.start(mode, self.recorded, self.cut, dry_run=True))
             gathered, pending = ex.start(self.exchange_mode, self.recorded, self.cut, cuts=self.cuts)

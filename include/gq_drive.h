@@ -23,6 +23,18 @@
  *                  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  output = z ^ (z >> 31)
  *              The library takes the words as they are (all-zero: the pure Hadamard transform).
  *
+ * SIGNS, STEPPED   The *_stepped entry points take no words: `rotation` is the address of a device uint64[2] = { seed, step }, and
+ *              word k (k = 0 ... 3) of a launch is output number 4 * step + k of the splitmix64 stream started at `seed`:
+ *                  z = seed + (4 * step + k + 1) * 0x9E3779B97F4A7C15,  then the finaliser above (the two multiplications and
+ *                  the three xor-shifts);  all arithmetic on uint64, mod 2^64.
+ *              Step 0 gives exactly the fixed words of that seed.  Step t of seed s is step 0 of seed s + 4 t * 0x9E3779B97F4A7C15.
+ *              The words repeat after 2^62 steps.  gq_drive_batch.signs is not read.  The launch reads the pair and never writes it:
+ *              whoever owns it moves the step word between launches (gq_mean_rows and the step tails of libgq_hsq.so add one to
+ *              the step word of every pair they are given), and a launch replayed from a HIP graph -- its argument is the pair's
+ *              ADDRESS, which does not change -- rotates by the words of the step it finds.  The wire does not carry the step and
+ *              does not change by a byte: every payload of one decode-mean must have been compressed at the same (seed, step), and
+ *              the decode-mean must run at that (seed, step).  Everything below is the same, word for word, in both forms.
+ *
  * FORWARD TRANSFORM of a block of w (w is g, or under error feedback w = g + ef_scale * err: the product rounded, then the sum,
  *              as in gq_mx.h) -- gq_mxr.h's, word for word:
  *     1. x_j = w_j with its sign bit xor-ed with the element's sign bit.  A bit operation.
@@ -122,6 +134,16 @@ int gq_drive_compress_batched(const gq_drive_batch *b, uint8_t *wire, float ef_s
  */
 int gq_drive_decode_sum_batched(const gq_drive_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
                                 void *stream);
+
+/*
+ * The same two launches under SIGNS, STEPPED: `rotation` is the device { seed, step } pair (8-byte aligned), b->signs is not read.
+ * ONE launch per call, no scratch, every launch argument depends on the layout alone.  Refused: everything the calls above
+ * refuse, and a null or misaligned rotation.
+ */
+int gq_drive_compress_batched_stepped(const gq_drive_batch *b, const uint64_t *rotation, uint8_t *wire, float ef_scale, float *out,
+                                      void *stream);
+int gq_drive_decode_sum_batched_stepped(const gq_drive_batch *b, const uint64_t *rotation, const uint8_t *gathered,
+                                        int64_t user_stride_bytes, int R, float *out, int plain, void *stream);
 
 #ifdef __cplusplus
 }

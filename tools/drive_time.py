@@ -13,6 +13,8 @@ Rows (one JSON line each):
                   read and the same transform, about four times the wire bytes, no block reductions.  Eager, and as ten launches
                   replayed from one HIP graph (the device's own time).  *_over_parent_mxr_fp4: the ratio of the graphed times;
                   `bar` is 1.05 for each of the three launches and `missed` lists every ratio above it.
+--rotation step: the rot_step rows alone -- the stepped launches against the fixed ones of --parent-lib, then an older libgq_drive.so
+(tools/rot_step_time.py).
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -117,7 +119,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "drive_time.jsonl"))
     ap.add_argument("--parent-lib", default=None, help="an older libgq_mxr.so whose fp4 launches are the yardstick (without it: the in-tree one)")
+    ap.add_argument("--rotation", default=None, choices=["step"],
+                    help="the rot_step rows alone (tools/rot_step_time.py): the stepped launches against the fixed ones of --parent-lib, here "
+                         "an older libgq_drive.so")
     a = ap.parse_args()
+    if a.rotation == "step":
+        import rot_step_time
+        return rot_step_time.main("drive", a.out, a.parent_lib)
     dev = torch.device("cuda:0")
     write_rows(a.out, single_rows(dev, a.parent_lib) + resnet50_rows(dev))
 

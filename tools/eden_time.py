@@ -126,7 +126,15 @@ def main():
     ap.add_argument("--parent-lib", nargs="*", default=[],
                     help="an older libgq_mxr.so (its fp4 launches are the yardstick) and an older libgq_drive.so (the bracket), told apart "
                          "by their file names; without them the in-tree ones")
+    ap.add_argument("--rotation", default=None, choices=["step"],
+                    help="the rot_step rows alone (tools/rot_step_time.py): the stepped launches against the fixed ones of --parent-lib, here "
+                         "ONE older libgq_eden.so")
     a = ap.parse_args()
+    if a.rotation == "step":
+        import rot_step_time
+        if len(a.parent_lib) > 1:
+            ap.error("--rotation step takes one --parent-lib, an older libgq_eden.so")
+        return rot_step_time.main("eden", a.out, os.path.abspath(a.parent_lib[0]) if a.parent_lib else None)
     parent = {"mxr": None, "drive": None}
     for p in a.parent_lib:
         kind = [k for k in parent if k in os.path.basename(p)]
