@@ -181,6 +181,15 @@ __global__ __launch_bounds__(ENC_THREADS, 2) void hsq_encode_d16k256_kernel(cons
                 sawnan = sawnan || (bvv != bvv);
             }
         }
+        // a zero projection: the signed zero of the reference's chain (see hsq_encode_lds_kernel; the running best starts from +0)
+        if (__ballot(sv < M && val == 0.0f)) {
+            if (sv < M && val == 0.0f) {
+                const float *row = grad + sv * 16, *c = cb + idx * 16;
+                float acc = 0.0f;
+                for (int e = 0; e < 16; ++e) acc = __fmaf_rn(c[e], row[e], acc);
+                val = acc;
+            }
+        }
         if (sv < M) {
             codes[sv] = (CodeT)idx;
             u[sv] = val;
@@ -196,8 +205,10 @@ __global__ __launch_bounds__(ENC_THREADS, 2) void hsq_encode_d16k256_kernel(cons
 // ------------------------------------------------------------------------------------
 // Generic (d, K): same MFMA formulation; A/B fragments are fetched per MFMA from
 // global memory (the codebook and the 64-subvector tile stay L1/L2 resident).
-// k beyond d and codewords beyond K are fed as zeros: fma(0,0,acc) == acc exactly
-// (acc is never -0 in this chain), and padded codewords are excluded from the argmax.
+// k beyond d (odd d: the last k-step's upper half) and codewords beyond K are fed as zeros: fma(0,0,acc) == acc
+// for every acc but -0 (fmaf(0, 0, -0) == +0, and a product that underflows makes -0), so |p| and the codes are
+// the reference's; padded codewords are excluded from the argmax.  The SIGN of a zero projection comes from the
+// re-evaluation behind the argmax (as in hsq_encode_lds_kernel and the d16 kernel above; tests/hsq_zero_contract.py).
 // ------------------------------------------------------------------------------------
 template <typename CodeT>
 __global__ __launch_bounds__(ENC_THREADS) void hsq_encode_generic_kernel(const float *__restrict__ grad,
@@ -274,6 +285,15 @@ __global__ __launch_bounds__(ENC_THREADS) void hsq_encode_generic_kernel(const f
                 sawnan = sawnan || (bvv != bvv);
             }
         }
+        // a zero projection: the signed zero of the chain over the row's d real elements (see hsq_encode_lds_kernel)
+        if (__ballot(sv < M && val == 0.0f)) {
+            if (sv < M && val == 0.0f) {
+                const float *row = grad + sv * (int64_t)d, *c = cb + (int64_t)idx * d;
+                float acc = 0.0f;
+                for (int e = 0; e < d; ++e) acc = __fmaf_rn(c[e], row[e], acc);
+                val = acc;
+            }
+        }
         if (sv < M) {
             codes[sv] = (CodeT)idx;
             u[sv] = val;
@@ -293,8 +313,10 @@ __global__ __launch_bounds__(ENC_THREADS) void hsq_encode_generic_kernel(const f
 // so that lane (j, h) of v_mfma_f32_32x32x2_f32 finds its operands a[ks] = row[2ks + h] as ONE
 // contiguous run and fetches four k-steps per ds_read_b128.  Rows are dpad + 4 floats apart:
 // (dpad+4)/4 is odd, so the 16 lanes of a b128 phase hit 16 different bank groups.
-// Zero padding is exact: fma(0, 0, acc) == acc (acc is never -0 in this chain); padded codewords
-// are excluded from the argmax.  Two independent accumulator chains (the tile's two 32-column
+// Zero padding leaves every |p| as it is: fma(0, 0, acc) == acc for every acc but -0 (a product that
+// underflows rounds to -0, and fma(0, 0, -0) == +0), so the codes are the reference's; a projection that
+// compares equal to zero is re-evaluated over the row's d real elements behind the argmax, which gives it the
+// reference's sign.  Padded codewords are excluded from the argmax.  Two independent accumulator chains (the tile's two 32-column
 // blocks) share every A fragment.  When the codebook is chunked the workgroup re-stages the next
 // chunk between barriers and each wave carries its tile's running (best, index) in registers.
 // ------------------------------------------------------------------------------------
@@ -525,6 +547,21 @@ __global__ __launch_bounds__(ENC_THREADS) void hsq_encode_lds_kernel(const float
                 }
             }
         }
+        // A projection that compares equal to zero: every |p| is zero, and what stands in `val` is the +0 the running best
+        // started from (or a chain that went on over the padding, where fmaf(0, 0, -0) == +0) -- not the SIGNED zero the
+        // reference's chain over the row's d real elements ends at (a product that underflows rounds to -0).  Such a lane
+        // re-evaluates its chosen row unpadded: subvector from the staged tile, codebook row from global memory (it may be
+        // chunked in LDS).  Rare (zero rows; the lanes behind a tensor's last row hold staged +0 rows, keep their +0 and do not
+        // ask for it) and skipped by the whole wave otherwise.
+        const bool row_here = BATCHED ? seg_sv0 + lane < seg_m : t * 64 + lane < M;
+        if (__ballot(row_here && val == 0.0f)) {
+            if (row_here && val == 0.0f) {
+                const float *row = s_v + lane * stride, *c = cb + (int64_t)idx * d;
+                float acc = 0.0f;
+                for (int e = 0; e < d; ++e) acc = __fmaf_rn(c[e], row[(e & 1) * half + (e >> 1)], acc);
+                val = acc;
+            }
+        }
         if (BATCHED) {
             if (seg != cur_seg) {
                 flush_minmax(lmin, lmax);
@@ -615,12 +652,10 @@ __global__ __launch_bounds__(ENC_THREADS) void hsq_encode_valu_kernel(const floa
             float acc = 0.0f;
 #pragma unroll
             for (int jj = 0; jj < D; ++jj) acc = __fmaf_rn(s_cb[k * D + jj], v[jj], acc);
-            if (odd) {
-                if (k == 0) {
-                    best_v = acc;
-                } else {
-                    take_if_greater_nan(best_v, best_i, acc, k);
-                }
+            if (k == 0) {
+                best_v = acc;      // (row 0's projection as it is: a signed zero stays when every |p| is zero)
+            } else if (odd) {
+                take_if_greater_nan(best_v, best_i, acc, k);
             } else {
                 take_if_greater(best_v, best_i, acc, k);
             }

@@ -188,8 +188,11 @@ static void pf_split(PfArgs &a, int64_t ntiles, int64_t blocks) {
 // the two sources turns the record pointer into a flat pointer (see tile_info).
 // DR (round 6): the tensors' REAL sub-dimension when the reference repaired it to one this kernel has no shape for
 // (nearest_neighbor_compressor.py:23-29: 16 -> 24, 8 -> 12): rows of DR floats in memory (gradient, error buffer, codebook), D = the
-// next of 16 / 32 everywhere else -- the missing elements are zeros in the fragments, in the LDS image and in the lane's subvector,
-// and fmaf(0, 0, acc) == acc bit for bit (acc starts at +0 and can never become -0), so scores, codes and u are the exact kernels'.
+// next of 16 / 32 everywhere else -- the missing elements are zeros in the fragments, in the LDS image and in the lane's subvector.
+// The f16 scores and the keys see the padding (it adds +0 to |s~|: codes are decided on |p|); the EXACT chains -- the rescoring, the
+// second pass's rescoring and the scan -- end behind element DR - 1 (exact_score_quad<D, DR>): a product that underflows rounds
+// to -0, the chain can stand at -0 there, and one padded step fmaf(0, 0, -0) would turn the projection into +0
+// (tests/hsq_zero_contract.py).  So codes and u are the exact chain's over the DR real elements, the sign of a zero included.
 // NRB (round 6): row blocks of 32 codewords that are scored -- 8 for K = 256 (and any K above 64), 2 for K <= 64, 1 for K <= 32
 // (--k-bit 5 / 6, and K == dim: nearest_neighbor_compressor.py:40-47): 2 NRB chains per tile instead of 16.  Rows K .. 32 NRB - 1
 // are zeros (image and fragments): their scores are +0 for every finite subvector, so they lose every comparison against a real
@@ -475,7 +478,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void hsq_encode_pf_kernel(const PfAr
         const int i = threadIdx.x + n * PF_THREADS, k = i / DR, jj = i % DR;
         s_cb[(k >> 2) * QS + 4 * jj + (k & 3)] = cbv[n];
     }
-    if constexpr (DR != D) {      // the image's padding columns: zeros (the rescoring multiplies them with the subvector's zeros)
+    if constexpr (DR != D) {      // the image's padding columns: zeros (no exact chain reads them: exact_score_quad<D, DR> ends at DR)
 #pragma unroll
         for (int n = 0; n < 256 * (D - DR) / PF_THREADS; ++n) {
             const int i = threadIdx.x + n * PF_THREADS, k = i / (D - DR), jj = DR + i % (D - DR);
@@ -598,7 +601,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void hsq_encode_pf_kernel(const PfAr
                 w[4 * q + 3] = x[3];
             }
         }
-        f32x4 p = exact_score_quad<D>(s_cb + lane * QS, w);
+        f32x4 p = exact_score_quad<D, DR>(s_cb + lane * QS, w);
         if (4 * lane >= K) p = f32x4{0.0f, 0.0f, 0.0f, 0.0f};   // rows behind the codebook (K is a multiple of 4): +0, whatever 0 x inf gave -- never the first maximum
         float bv = p[0];
         int bi = 4 * lane;
@@ -762,7 +765,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void hsq_encode_pf_kernel(const PfAr
             vf[4 * q + 2] = x[2];
             vf[4 * q + 3] = x[3];
         }
-        const f32x4 p4 = exact_score_quad<D>(s_cb + (kc >> 2) * QS, vf);
+        const f32x4 p4 = exact_score_quad<D, DR>(s_cb + (kc >> 2) * QS, vf);
         float val = p4[0];
         int idx = kc;
         take_if_greater(val, idx, p4[1], kc + 1);
@@ -944,7 +947,7 @@ __global__ __launch_bounds__(PF_THREADS, 1) void hsq_encode_pf_kernel(const PfAr
         const bool pick1 = (bk[1] & KEY_MASK) > (bk[0] & KEY_MASK);
         const int kc = pick1 ? k1[1] : k1[0];
         const unsigned rest = max3u(s2[0], s2[1], (pick1 ? bk[0] : bk[1]) | 31u);
-        const f32x4 p4 = exact_score_quad<D>(s_cb + (kc >> 2) * QS, vf);   // kc is a multiple of 4: one quad
+        const f32x4 p4 = exact_score_quad<D, DR>(s_cb + (kc >> 2) * QS, vf);   // kc is a multiple of 4: one quad
         float val = p4[0];
         int idx = kc;
         take_if_greater(val, idx, p4[1], kc + 1);

@@ -111,24 +111,32 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef GQ_RESCORE_BATCH
 #define GQ_RESCORE_BATCH 8
 #endif
-template <int D>
+// DR <= D: the chain ends behind the row's DR REAL elements (hsq_encode_pf.hip's padded shapes, 12 in 16 and 24 in 32).  A step over
+// a padding element is NOT a no-op: a product that underflows rounds to -0, so the chain can stand at -0, and
+// fmaf(0, 0, -0) == +0 -- the sign of a zero projection travels (u_flat, seg_minmax, (lb, ub), the decode's zeros).
+template <int D, int DR = D>
 __device__ __forceinline__ f32x4 exact_score_quad(const float *__restrict__ quad, const float (&v)[D]) {
+    static_assert(DR >= 1 && DR <= D, "the real elements are the row's first DR");
     float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
     // the rows are fetched in batches of 8 (the accumulators of the prefilter are dead by now, there is room): with
     // the reads issued one by one beside their FMAs the group cost 16 LDS round trips in a row
-    constexpr int B = D < GQ_RESCORE_BATCH ? D : GQ_RESCORE_BATCH;
+    constexpr int B = DR < GQ_RESCORE_BATCH ? DR : GQ_RESCORE_BATCH;
 #pragma unroll
-    for (int j0 = 0; j0 < D; j0 += B) {
+    for (int j0 = 0; j0 < DR; j0 += B) {
+        const int nb = DR - j0 < B ? DR - j0 : B;   // the last batch of a padded shape is short (12 = 8 + 4); a constant once unrolled
         f32x4 c[B];
 #pragma unroll
-        for (int jj = 0; jj < B; ++jj) c[jj] = *reinterpret_cast<const f32x4 *>(quad + 4 * (j0 + jj));
+        for (int jj = 0; jj < B; ++jj)
+            if (jj < nb) c[jj] = *reinterpret_cast<const f32x4 *>(quad + 4 * (j0 + jj));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int jj = 0; jj < B; ++jj) {
-            asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a0) : "v"(c[jj][0]), "v"(v[j0 + jj]));
-            asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a1) : "v"(c[jj][1]), "v"(v[j0 + jj]));
-            asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a2) : "v"(c[jj][2]), "v"(v[j0 + jj]));
-            asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a3) : "v"(c[jj][3]), "v"(v[j0 + jj]));
+            if (jj < nb) {
+                asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a0) : "v"(c[jj][0]), "v"(v[j0 + jj]));
+                asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a1) : "v"(c[jj][1]), "v"(v[j0 + jj]));
+                asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a2) : "v"(c[jj][2]), "v"(v[j0 + jj]));
+                asm("v_fma_f32 %0, %1, %2, %0" : "+v"(a3) : "v"(c[jj][3]), "v"(v[j0 + jj]));
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
     }
