@@ -108,7 +108,7 @@ __global__ __launch_bounds__(PV_THREADS) void pvq_encode_kernel(const float *__r
 // (l1 has to be complete before the walk); the code is the number of terms whose running sum stayed below the
 // threshold (the sums never decrease, so "first k with cum >= thr" == that count; NaN -- an all-zero
 // subvector -- counts every term and lands on K-1 like the oracle); the selected projection is recomputed as
-// one explicit fmaf chain.  Padded codewords (K not a multiple of 32) score +0 and change neither sum.
+// one explicit fmaf chain.  Padded codewords (K not a multiple of 32) enter both sums as +0, whatever they score.
 
 // ------------------------------------------------------------------------------------
 // Second stage of the ResidualCompressor (residual_compressor.py:15-24) without a residual tensor: the tile is
@@ -299,26 +299,37 @@ __global__ __launch_bounds__(ENC_THREADS) void pvq_encode_lds_kernel(const float
                         yv[q] = acc1[q];
                         swap32(x[q], yv[q]);
                     }
+                    // A padded codeword (the last row block of a K that is no multiple of 32) scores +0 only against finite
+                    // elements: 0 * inf is a NaN, which would turn the l1 = inf of a subvector with an infinite element into
+                    // NaN.  Its term is +0 by definition; whole row blocks (always, in the quick form) take the loop without the test.
+                    const int valid = K - (row0 + rb * 32);   // wave-uniform
+                    auto terms = [&](auto ragged) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) {
+                        for (int g = 0; g < 4; ++g) {
 #pragma unroll
-                        for (int part = 0; part < 2; ++part) {
+                            for (int part = 0; part < 2; ++part) {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float a = fabsf(part ? yv[4 * g + e] : x[4 * g + e]);   // codeword 32 rb + 8 g + 4 part + e
-                                if (decltype(first)::value) {
-                                    l1 = l1 + a;
-                                    if (e & 1) amin = fminf(fminf(amin, a), fabsf(part ? yv[4 * g + e - 1] : x[4 * g + e - 1]));
-                                } else if (decltype(quick)::value) {
-                                    cum = cum + (double)shared_quotient(a, l1, y);
-                                    count += (cum >= T) ? 0 : 1;
-                                } else {
-                                    cum = cum + (double)(a / l1);   // the reference divides first (:49,:57)
-                                    count += ((float)cum >= thr) ? 0 : 1;
+                                for (int e = 0; e < 4; ++e) {
+                                    float a = fabsf(part ? yv[4 * g + e] : x[4 * g + e]);   // codeword 32 rb + 8 g + 4 part + e
+                                    if (decltype(ragged)::value && 8 * g + 4 * part + e >= valid) a = 0.0f;
+                                    if (decltype(first)::value) {
+                                        l1 = l1 + a;
+                                        if (e & 1) amin = fminf(fminf(amin, a), fabsf(part ? yv[4 * g + e - 1] : x[4 * g + e - 1]));
+                                    } else if (decltype(quick)::value) {
+                                        cum = cum + (double)shared_quotient(a, l1, y);
+                                        count += (cum >= T) ? 0 : 1;
+                                    } else {
+                                        cum = cum + (double)(a / l1);   // the reference divides first (:49,:57)
+                                        count += ((float)cum >= thr) ? 0 : 1;
+                                    }
                                 }
                             }
                         }
-                    }
+                    };
+                    if (decltype(quick)::value || valid >= 32)
+                        terms(std::false_type{});
+                    else
+                        terms(std::true_type{});
                 }
             }
         };

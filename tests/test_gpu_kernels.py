@@ -436,8 +436,8 @@ def test_full_size_properties(nat, oracle):
 def test_pvq_encode_on_the_matrix_cores_matches_the_oracle(nat, oracle, d, K, M):
     """ProbabilisticVectorCompressor encode (intended semantics; parity with the reference unpinned): the MFMA
     kernel (any d <= 104, any K; whole and chunked codebooks, K no multiple of 32, ragged tiles) against the CPU
-    restatement for the same draws r -- codes, u and the (min,max) of u bit for bit; and against the VALU
-    cross-check kernel where that one is built."""
+    restatement for the same draws r -- codes, u and the (min,max) of u bit for bit.  (The VALU cross-check kernel runs in
+    tests/test_gpu_zz_pvq_contract.py, in a child process with $GQ_PVQ_VALU.)"""
     rng = np.random.RandomState(d * 131 + K)
     cdag = rng.standard_normal((K, d)).astype(np.float32) * 0.3
     x = (rng.standard_normal(M * d) * 0.05).astype(np.float32)
