@@ -22,6 +22,13 @@
 // stepped   the *_stepped entry points: the same bodies, with the lane's sign byte made once per launch from a device
 //           { seed, step } pair (gqx::stepped_sign_byte) instead of from four words passed by value.  The pair's ADDRESS is the
 //           launch argument: a replay rotates afresh once the step word has moved.
+// streams   the *_streams entry points (SIGNS, PER STREAM).  compress is the stepped kernel with one more step in its prelude:
+//           pair -> the stream's seed (one 64-bit multiply-add and one finaliser, on uniform values) -> the lane's sign byte.
+//           decode-mean is a body of its own: payload r was rotated by stream first + r, so it goes through its OWN inverse
+//           transform and the mean is taken in the gradient's domain -- R transforms per block.  The payload loop is the outer
+//           one and the item's two steps the inner one, so a stream's sign byte is derived once per workgroup and payload (never
+//           once per block) whatever R is, with nothing kept in an R-sized array; across payloads a lane keeps its 2 x 8
+//           accumulators and nothing else.
 #include <math.h>
 
 #include "gq_drive.h"
@@ -250,6 +257,74 @@ __global__ __launch_bounds__(THREADS) void drive_decode_kernel(const int64_t *__
     }
 }
 
+// SIGNS, PER STREAM: payload r under stream first + r.  Every lane of the workgroup runs every exchange: a block that is not there
+// (blk >= nb) decodes zeros that are never stored; a step that is not there is skipped on a workgroup-uniform test.
+__global__ __launch_bounds__(THREADS) void drive_decode_streams_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
+                                                                       const uint8_t *__restrict__ gathered, int64_t stride, int R,
+                                                                       float *__restrict__ out, int plain, const uint64_t *__restrict__ pair,
+                                                                       uint32_t first) {
+    const int64_t item = blockIdx.x;
+    const int seg = item_seg[item];
+    const int64_t *rec = seg_table + 8 * (int64_t)seg;
+    const int64_t n = rec[1], off = rec[3];
+    const int64_t nb = (n + GQ_DRIVE_BLOCK - 1) / GQ_DRIVE_BLOCK;
+    float *o = out + rec[5];
+    const int64_t base = (item - rec[2]) * GQ_MX_ITEM_ELEMS;
+    const bool direct = plain != 0;      // (the host side: R == 1)
+    const float fR = (float)R;
+    const uint64_t seed = pair[0], step = pair[1];      // (one uniform read per launch)
+    const bool words = ((reinterpret_cast<uintptr_t>(gathered) | (uintptr_t)(R > 1 ? stride : 0)) & 3u) == 0;
+    const int64_t lane0 = base + (int64_t)threadIdx.x * PER_LANE;      // this lane's first element of step 0
+    float acc[STEPS][PER_LANE];
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+#pragma unroll
+        for (int k = 0; k < PER_LANE; ++k) acc[s][k] = 0.0f;
+    }
+    const uint8_t *p = gathered + off;
+    for (int r = 0; r < R; ++r, p += stride) {
+        const Hadamard rotation(gqx::stream_sign_byte(seed, step, first + (uint32_t)r));
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) {
+            if (base + (int64_t)s * STEP < n) {      // (uniform over the workgroup)
+                const int64_t e0 = lane0 + (int64_t)s * STEP;
+                const int64_t blk = e0 / GQ_DRIVE_BLOCK;
+                uint32_t byte = 0, sbits = 0;
+                if (blk < nb) {      // (uniform over the half: loads only, no exchange in here)
+                    byte = p[e0 / PER_LANE];
+                    const uint8_t *sp = p + nb * CODE_BYTES + 4 * blk;
+                    if (words) {
+                        sbits = *reinterpret_cast<const uint32_t *>(sp);
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) sbits |= (uint32_t)sp[k] << (8 * k);
+                    }
+                }
+                float y[PER_LANE];
+#pragma unroll
+                for (int k = 0; k < PER_LANE; ++k) y[k] = __uint_as_float(sbits ^ (((byte >> k) & 1u) << 31));
+                rotation.inverse(y, true);      // this payload's own inverse transform
+#pragma unroll
+                for (int k = 0; k < PER_LANE; ++k) acc[s][k] = direct ? y[k] : acc[s][k] + y[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+        const int64_t e0 = lane0 + (int64_t)s * STEP;
+        if (e0 < n) {
+            float f[PER_LANE];
+#pragma unroll
+            for (int k = 0; k < PER_LANE; ++k) f[k] = direct ? acc[s][k] : acc[s][k] / fR;
+            if (e0 + PER_LANE - 1 < n && aligned16(o + e0)) {
+                store8(o + e0, f);
+            } else {
+                for (int k = 0; k < PER_LANE && e0 + k < n; ++k) o[e0 + k] = f[k];
+            }
+        }
+    }
+}
+
 static int check_batch(const gq_drive_batch *b, const char *what, bool compress) {
     if (!b || b->struct_bytes != sizeof(gq_drive_batch)) return fail(GQ_ERR_INVALID_ARG, "%s: descriptor missing or of another size", what);
     if (b->scale_mode != GQ_DRIVE_UNBIASED && b->scale_mode != GQ_DRIVE_MSE)
@@ -281,17 +356,28 @@ static void launch_compress(const gq_drive_batch *b, uint8_t *wire, float ef_sca
         launch_compress<GQ_DRIVE_MSE>(b, wire, ef_scale, out, rot, st);
 }
 
-// the two entry points of a launch kind; stepped: `rotation` is checked and the descriptor's sign words are not read
+// SIGNS, PER STREAM: streams first ... first + R - 1 are non-negative int32
+static int check_streams(int32_t first, int R, const char *what) {
+    if (first < 0) return fail(GQ_ERR_INVALID_ARG, "%s: stream %d is negative", what, (int)first);
+    if ((int64_t)first + (int64_t)R > 0x7fffffffll) return fail(GQ_ERR_INVALID_ARG, "%s: first stream %d + R = %d overflows int32", what, (int)first, R);
+    return GQ_OK;
+}
+
+// the two entry points of a launch kind; stepped: `rotation` is checked and the descriptor's sign words are not read;
+// sigma (stepped only): the stream of a *_streams call, null otherwise
 static int compress(const char *what, const gq_drive_batch *b, uint8_t *wire, float ef_scale, float *out, bool stepped, const uint64_t *rotation,
-                    void *stream) {
+                    void *stream, const int32_t *sigma = nullptr) {
     int rc = check_batch(b, what, true);
     if (rc == GQ_OK && stepped) rc = check_rotation(rotation, what);
+    if (rc == GQ_OK && sigma) rc = check_streams(*sigma, 0, what);
     if (rc != GQ_OK) return rc;
     if (!wire || (reinterpret_cast<uintptr_t>(wire) & 15) != 0)
         return fail(GQ_ERR_INVALID_ARG, "%s: the wire must be a 16-byte aligned device buffer", what);
     if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (stepped)
+    if (sigma)
+        launch_compress(b, wire, ef_scale, out, gqx::Streamed{rotation, (uint32_t)*sigma}, st);
+    else if (stepped)
         launch_compress(b, wire, ef_scale, out, gqx::Stepped{rotation}, st);
     else
         launch_compress(b, wire, ef_scale, out, Hadamard::args(b), st);
@@ -300,7 +386,7 @@ static int compress(const char *what, const gq_drive_batch *b, uint8_t *wire, fl
 }
 
 static int decode_sum(const char *what, const gq_drive_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out, int plain,
-                      bool stepped, const uint64_t *rotation, void *stream) {
+                      bool stepped, const uint64_t *rotation, void *stream, const int32_t *first = nullptr) {
     int rc = check_batch(b, what, false);
     if (rc == GQ_OK && stepped) rc = check_rotation(rotation, what);
     if (rc != GQ_OK) return rc;
@@ -309,9 +395,13 @@ static int decode_sum(const char *what, const gq_drive_batch *b, const uint8_t *
         return fail(GQ_ERR_INVALID_ARG, "%s: R = %d, user stride %lld", what, R, (long long)user_stride_bytes);
     if (plain && R != 1) return fail(GQ_ERR_INVALID_ARG, "%s: plain is the decode of ONE payload, R = %d", what, R);
     if ((reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "%s: out must be 4-byte aligned", what);
+    if (first && (rc = check_streams(*first, R, what)) != GQ_OK) return rc;
     const dim3 grid((unsigned)b->nitems), block(THREADS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (stepped)
+    if (first)
+        hipLaunchKernelGGL(drive_decode_streams_kernel, grid, block, 0, st, b->seg_table, b->item_seg, gathered, user_stride_bytes, R, out,
+                           plain ? 1 : 0, rotation, (uint32_t)*first);
+    else if (stepped)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(drive_decode_kernel<gqx::Stepped>), grid, block, 0, st, b->seg_table, b->item_seg, gathered,
                            user_stride_bytes, R, out, plain ? 1 : 0, gqx::Stepped{rotation});
     else
@@ -344,4 +434,15 @@ GQD_API int gq_drive_decode_sum_batched(const gq_drive_batch *b, const uint8_t *
 GQD_API int gq_drive_decode_sum_batched_stepped(const gq_drive_batch *b, const uint64_t *rotation, const uint8_t *gathered,
                                                 int64_t user_stride_bytes, int R, float *out, int plain, void *stream) {
     return gqd::decode_sum("gq_drive_decode_sum_batched_stepped", b, gathered, user_stride_bytes, R, out, plain, true, rotation, stream);
+}
+
+GQD_API int gq_drive_compress_batched_streams(const gq_drive_batch *b, const uint64_t *rotation, int32_t stream, uint8_t *wire, float ef_scale,
+                                              float *out, void *stream_handle) {
+    return gqd::compress("gq_drive_compress_batched_streams", b, wire, ef_scale, out, true, rotation, stream_handle, &stream);
+}
+
+GQD_API int gq_drive_decode_sum_batched_streams(const gq_drive_batch *b, const uint64_t *rotation, int32_t first_stream, const uint8_t *gathered,
+                                                int64_t user_stride_bytes, int R, float *out, int plain, void *stream_handle) {
+    return gqd::decode_sum("gq_drive_decode_sum_batched_streams", b, gathered, user_stride_bytes, R, out, plain, true, rotation, stream_handle,
+                           &first_stream);
 }

@@ -33,26 +33,52 @@ struct SignByte {
     uint32_t v;
 };
 
-// SIGNS, STEPPED (include/gq_drive.h, include/gq_eden.h): `rotation` is a device { seed, step } pair, word k of the launch is output
-// 4 * step + k of the splitmix64 stream started at seed.  A lane needs the word of its quarter only: the pair is one plain
-// wave-uniform read, then one finaliser (two 64-bit multiplications) and the lane's byte.  Once per launch: a caller keeps this
-// out of its item loop.
-__device__ __forceinline__ SignByte stepped_sign_byte(const uint64_t *__restrict__ rotation) {
+// the splitmix64 finaliser: the two multiplications and the three xor-shifts
+__device__ __forceinline__ uint64_t splitmix_fin(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// SIGNS, STEPPED (include/gq_drive.h, include/gq_eden.h): word k of the launch at (seed, step) is output 4 * step + k of the
+// splitmix64 stream started at seed.  A lane needs the word of its quarter only: one finaliser (two 64-bit multiplications) and
+// the lane's byte.
+__device__ __forceinline__ SignByte stepped_sign_byte(uint64_t seed, uint64_t step) {
     constexpr uint64_t G = 0x9E3779B97F4A7C15ull;
-    const uint64_t seed = rotation[0], step = rotation[1];
     const uint32_t l = threadIdx.x & 31u;
     const uint32_t q = l >> 3;
     const uint64_t first = seed + (4 * step + 1) * G;      // (uniform; all of it mod 2^64)
-    uint64_t z = first + (q == 0 ? 0 : q == 1 ? G : q == 2 ? 2 * G : 3 * G);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
+    const uint64_t z = splitmix_fin(first + (q == 0 ? 0 : q == 1 ? G : q == 2 ? 2 * G : 3 * G));
     return SignByte{(uint32_t)(z >> (8 * (l & 7u))) & 0xffu};
+}
+
+// `rotation` is a device { seed, step } pair: one plain wave-uniform read.  Once per launch: a caller keeps this out of its item loop.
+__device__ __forceinline__ SignByte stepped_sign_byte(const uint64_t *__restrict__ rotation) {
+    return stepped_sign_byte(rotation[0], rotation[1]);
 }
 
 // what a stepped launch takes in the place of Signs: the pair's address, which never changes
 struct Stepped {
     const uint64_t *pair;
+};
+
+// SIGNS, PER STREAM (include/gq_drive.h, include/gq_eden.h): the seed of stream sigma >= 0.  Stream 0 keeps the seed, so its words
+// are the stepped ones bit for bit; any other stream's seed is one 64-bit multiply-add and one finaliser away, all of it on values
+// that are uniform over the workgroup.
+__device__ __forceinline__ uint64_t stream_seed(uint64_t seed, uint32_t sigma) {
+    const uint64_t mixed = splitmix_fin(seed + (uint64_t)sigma * 0xD6E8FEB86659FD93ull);
+    return sigma == 0 ? seed : mixed;
+}
+
+// the lane's sign byte of stream sigma at (seed, step): the stepped byte of (seed_sigma, step)
+__device__ __forceinline__ SignByte stream_sign_byte(uint64_t seed, uint64_t step, uint32_t sigma) {
+    return stepped_sign_byte(stream_seed(seed, sigma), step);
+}
+
+// what a compress under one stream takes: the pair's address and the stream, by value (a function of the wire slot)
+struct Streamed {
+    const uint64_t *pair;
+    uint32_t sigma;
 };
 
 // the value of lane ^ M, M = 1, 2, 4, 8 or 16 (all inside a 32-lane half)
@@ -109,6 +135,7 @@ struct Hadamard {
     __device__ __forceinline__ explicit Hadamard(const Signs &s) : sbyte(sign_byte(s)) {}
     __device__ __forceinline__ explicit Hadamard(const SignByte &b) : sbyte(b.v) {}
     __device__ __forceinline__ explicit Hadamard(const Stepped &r) : Hadamard(stepped_sign_byte(r.pair)) {}      // (drive.hip / eden.hip)
+    __device__ __forceinline__ explicit Hadamard(const Streamed &r) : Hadamard(stream_sign_byte(r.pair[0], r.pair[1], r.sigma)) {}
     // w -> x' (rot; otherwise x' = w)
     __device__ __forceinline__ const HadLane &forward(const HadLane &w, HadLane &x, bool rot) const {
 #pragma unroll

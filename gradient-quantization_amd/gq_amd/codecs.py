@@ -794,9 +794,14 @@ class DriveCodec(_SparseCodec):
     one-tensor BatchedDrive; roundtrip / encode_decode_into return the compress launch's own dense decode.
     stepped (the compressor's rotation is 'step'): `rotation`, the device { seed, step } pair a quantizer hands the codec, goes
     to every launch (include/gq_drive.h: SIGNS, STEPPED).  Without a pair -- a codec used on its own -- the launches are the fixed
-    ones under the seed's words, which is step 0."""
+    ones under the seed's words, which is step 0.
+    own (the compressor's user_rotation is 'own'; include/gq_drive.h: SIGNS, PER STREAM): the codec's launches are the *_streams
+    ones -- a compress under `stream` (which the quantizer sets: the payload's place in the mean; 0 on its own), a decode-mean that
+    rotates payload r back under stream r.  They need a pair in either rotation mode: the quantizer's, or on its own one the codec
+    makes at (seed, step 0)."""
 
-    rotation = None      # the { seed, step } pair (device int64 [1, 2]) of a stepped codec inside a quantizer
+    rotation = None      # the { seed, step } pair (device int64 [1, 2]) of a stepped or `own` codec inside a quantizer
+    stream = 0           # own: the stream of the next compress
 
     def __init__(self, compressor, numel, shape):
         self.c, self.numel, self.shape = compressor, numel, shape
@@ -809,10 +814,13 @@ class DriveCodec(_SparseCodec):
     def _rotation_of(self, compressor):
         self.signs = tuple(int(w) for w in compressor.signs)
         self.stepped = getattr(compressor, "rotation", "fixed") == "step"
+        self.own = getattr(compressor, "user_rotation", "shared") == "own"
+        self.seed = getattr(compressor, "seed", None)
 
     def _batched1(self, dev):
         grp = _SparseCodec._batched1(self, dev)
         grp.rotation = self.rotation      # (the quantizer's pair, or None: step 0)
+        grp.stream_base = self.stream     # (a one-tensor group records into slot 0)
         return grp
 
     def _wire_bytes(self):
@@ -1112,6 +1120,8 @@ class _BatchedBase(object):
             kw = {"tail": tail} if tail is not None else {}      # (BatchedHSQ only: see takes_tail)
             if self.rotation is not None:
                 kw["rotation"] = self.rotation                   # (BatchedDrive / BatchedEden in step mode)
+            if self.own:
+                kw["rotation"], kw["first_stream"] = self._pair(), 0      # (payload r of the gather under stream r)
             if getattr(self, "fma", False) and R >= 2 and not plain:
                 batch.decode(gathered, R, out, fma=True, **kw)      # (BatchedHSQ only: the quantizer sets `fma` on its HSQ groups)
             else:
@@ -1120,6 +1130,7 @@ class _BatchedBase(object):
 
     takes_tail = False      # the group's decode-mean launch can take the aggregate's small per-step work along (native.StepTail)
     rotation = None         # BatchedDrive / BatchedEden in step mode: the quantizer's { seed, step } pair, read by every launch
+    own = False             # BatchedDrive / BatchedEden under user_rotation = 'own': the *_streams launches (they read the pair too)
 
     def upload_layout(self):
         """Device header with the layout columns only (no tensor pointers): enough for decode_mean,
@@ -1686,7 +1697,9 @@ class _ItemGroup(_BatchedBase):
         """The decode-mean launch into a caller's buffer (_SparseCodec: a one-tensor group, its section at offset 0 of the rows)."""
         if not self.ready:
             self.upload_layout()
-        if self.rotation is not None:
+        if self.own:
+            self._batch.decode(gathered, R, out, plain=plain, rotation=self._pair(), first_stream=0)
+        elif self.rotation is not None:
             self._batch.decode(gathered, R, out, plain=plain, rotation=self.rotation)
         else:
             self._batch.decode(gathered, R, out, plain=plain)
@@ -2059,7 +2072,14 @@ class BatchedDrive(_ItemGroup):
     domain and rotates the mean back once -- which is why one group, and every user of it, has one set of sign words.
     Step mode (the codecs' `stepped`): the quantizer sets `rotation`, its { seed, step } pair, and both launches are the *_stepped
     ones, which read the words of the current step through that address -- still nothing in a launch changes, so the group stays
-    graphable; the quantizer's aggregate moves the step word.  Without a pair the launches are the fixed ones: step 0."""
+    graphable; the quantizer's aggregate moves the step word.  Without a pair the launches are the fixed ones: step 0.
+    own (the codecs' `own`; SIGNS, PER STREAM): both launches are the *_streams ones.  A record into wire slot s compresses under
+    stream `stream_base` + s -- the quantizer sets stream_base = rank * users per rank, so that the stream is the payload's row of
+    the gather -- and the decode-mean rotates row r back under stream r.  The two-phase re-compress (rng_slot given) is one payload:
+    stream 0.  The stream is a launch argument by value and a function of the slot, as a record graph's key is.  The launches read
+    the quantizer's pair in either rotation mode (under 'fixed' nothing ever steps it); a group on its own makes one at step 0."""
+
+    stream_base = 0
 
     @staticmethod
     def eligible(codec):
@@ -2067,7 +2087,19 @@ class BatchedDrive(_ItemGroup):
 
     @staticmethod
     def group_key(codec):
-        return (codec.scale_mode, int(codec.stepped)) + tuple(codec.signs)
+        return (codec.scale_mode, int(codec.stepped) + 2 * int(getattr(codec, "own", False))) + tuple(codec.signs)
+
+    def _pair(self):
+        """own: the pair the *_streams launches read -- the quantizer's, or (a group on its own) one made here at (seed, step 0)."""
+        if self.rotation is None:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("the rotation pair is made by the first eager launch, not under stream capture")
+            seed = self.codecs[0].seed
+            if seed is None:
+                raise ValueError("user_rotation = 'own' needs the compressor's seed")
+            seed = int(seed) & (2 ** 64 - 1)
+            self.rotation = torch.tensor([[seed - (2 ** 64 if seed & 2 ** 63 else 0), 0]], dtype=torch.int64).to(self.device)
+        return self.rotation
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         # an item is a run of elements (numel >= 1: never none); 16-byte aligned views in the output buffer: the launches store float4 there
@@ -2076,6 +2108,7 @@ class BatchedDrive(_ItemGroup):
         c0 = self.codecs[0]
         self.random = False
         self.scale_mode, self.signs, self.stepped = c0.scale_mode, c0.signs, c0.stepped
+        self.own = bool(getattr(c0, "own", False))
         self._batch = self._make_batch(nseg, item)
 
     def _make_batch(self, nseg, item):
@@ -2090,7 +2123,12 @@ class BatchedDrive(_ItemGroup):
             return False
         if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None, self.rotation)
+        if self.own:
+            stream = 0 if rng_slot is not None else self.stream_base + slot      # (rng_slot: the two-phase re-compress, ONE payload)
+            self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None, self._pair(),
+                         stream)
+        else:
+            self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None, self.rotation)
         return True
 
 
@@ -2107,7 +2145,7 @@ class BatchedEden(BatchedDrive):
 
     @staticmethod
     def group_key(codec):
-        return (codec.bits, codec.scale_mode, int(codec.stepped)) + tuple(codec.signs)
+        return (codec.bits, codec.scale_mode, int(codec.stepped) + 2 * int(getattr(codec, "own", False))) + tuple(codec.signs)
 
     def _make_batch(self, nseg, item):
         self.bits = self.codecs[0].bits

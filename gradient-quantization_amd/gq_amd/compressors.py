@@ -632,6 +632,15 @@ def _rotation_mode(args, name):
     return mode
 
 
+def _user_rotation_mode(args, name):
+    """args.drive_user_rotation / args.eden_user_rotation: 'shared' (also when absent) or 'own'."""
+    mode = getattr(args, name, None)
+    mode = "shared" if mode is None else mode
+    if mode not in ("shared", "own"):
+        raise ValueError("%s must be 'shared' or 'own', got %r" % (name, mode))
+    return mode
+
+
 class DriveCompressor(object):
     """The rotated 1-bit compressor (DRIVE, Vargaftik et al. 2021; no counterpart in the reference's catalogue): a block of 256
     elements is rotated by a randomized Hadamard matrix, the sign of every rotated coordinate is kept and one f32 scale per block --
@@ -646,11 +655,35 @@ class DriveCompressor(object):
     makes the 'unbiased' decodes average out over ROUNDS.  The step is a device { seed, step } pair that a quantizer owns and moves
     once per apply(); a bare DriveCompressor(...).compress() outside a quantizer has no pair and stays at step 0, which is the fixed
     rotation of the seed.
+    args.drive_user_rotation: 'shared' (the default, also when absent) -- every user of one mean rotates by the same words, the
+    payloads are added in the rotated domain and rotated back ONCE -- or 'own' -- every user rotates by a stream of sign words of
+    their own (include/gq_drive.h: SIGNS, PER STREAM; stream_seed), every payload is rotated back by ITS words and the mean is taken
+    in the gradient's domain, one launch still: R inverse transforms against one, which is why 'shared' stays the default.  'own' is
+    what makes the 'unbiased' decodes average out over USERS (the error of the mean of R users with equal gradients falls as
+    1 / sqrt(R); under 'shared' it is one user's).  The wire does not change.  The stream of a payload is its place in the mean,
+    which a quantizer assigns; a bare compress() is stream 0.
     compress returns the dense decode and decompress is the identity, as for MXCompressor.  HIP kernels only (libgq_drive.so): a
     float32 tensor on the device."""
 
     SCALES = ("unbiased", "mse")
     ROTATIONS = ("fixed", "step")
+    USER_ROTATIONS = ("shared", "own")
+
+    @staticmethod
+    def stream_seed(seed, stream):
+        """The seed of a stream (include/gq_drive.h: SIGNS, PER STREAM): stream 0 keeps the seed, stream s >= 1 is the splitmix64
+        finaliser of seed + s * 0xD6E8FEB86659FD93.  The words of (seed, step, stream) are rotation_words(stream_seed(seed, stream),
+        step)."""
+        M = (1 << 64) - 1
+        seed, stream = int(seed) & M, int(stream)
+        if stream < 0:
+            raise ValueError("a stream is a non-negative integer, got %d" % stream)
+        if stream == 0:
+            return seed
+        z = (seed + stream * 0xD6E8FEB86659FD93) & M
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+        return z ^ (z >> 31)
 
     @staticmethod
     def rotation_words(seed, step):
@@ -665,6 +698,7 @@ class DriveCompressor(object):
             raise ValueError("drive_scale must be 'unbiased' or 'mse', got %r" % (scale,))
         self.scale = scale
         self.rotation = _rotation_mode(args, "drive_rotation")
+        self.user_rotation = _user_rotation_mode(args, "drive_user_rotation")
         seed = getattr(args, "drive_seed", None)
         self.seed = 1 if seed is None else int(seed)
         self.signs = MXCompressor.sign_words(self.seed)
@@ -699,13 +733,17 @@ class EdenCompressor(object):
     signs; one decode-mean needs every payload under the same signs).
     args.eden_rotation: 'fixed' (the default, also when absent) or 'step' -- DriveCompressor's drive_rotation, word for word: a
     fresh rotation every round from a { seed, step } pair the quantizer owns; a bare EdenCompressor(...).compress() stays at step 0.
+    args.eden_user_rotation: 'shared' (the default, also when absent) or 'own' -- DriveCompressor's drive_user_rotation, word for
+    word: every user of one mean under a stream of sign words of their own (include/gq_eden.h: SIGNS, PER STREAM).
     compress returns the dense decode and decompress is the identity, as for DriveCompressor.  HIP kernels only (libgq_eden.so): a
     float32 tensor on the device."""
 
     SCALES = ("unbiased", "mse")
     BITS = (2, 3, 4)
     ROTATIONS = DriveCompressor.ROTATIONS
+    USER_ROTATIONS = DriveCompressor.USER_ROTATIONS
     rotation_words = staticmethod(DriveCompressor.rotation_words)
+    stream_seed = staticmethod(DriveCompressor.stream_seed)
 
     def __init__(self, size, shape, args):
         bits = getattr(args, "eden_bits", None)
@@ -718,6 +756,7 @@ class EdenCompressor(object):
             raise ValueError("eden_scale must be 'unbiased' or 'mse', got %r" % (scale,))
         self.scale = scale
         self.rotation = _rotation_mode(args, "eden_rotation")
+        self.user_rotation = _user_rotation_mode(args, "eden_user_rotation")
         seed = getattr(args, "eden_seed", None)
         self.seed = 1 if seed is None else int(seed)
         self.signs = MXCompressor.sign_words(self.seed)

@@ -193,6 +193,18 @@ def build_parser():
                    help="--quantizer eden: 'fixed' -- the sign words of --eden-seed at every step -- or 'step' -- a fresh rotation every "
                         "step, drawn from the seed's stream by a step counter all ranks share.  'step' is what the 'unbiased' scale wants "
                         "(its errors then average out over steps as well as users); 'mse' with --ef does not need it.  --ef works with either")
+    p.add_argument('--drive-user-rotation', dest='drive_user_rotation', type=str, default='shared', choices=['shared', 'own'],
+                   help="--quantizer drive: 'shared' -- every user of one mean rotates by the same sign words; the mean is taken in the "
+                        "rotated domain and rotated back once -- or 'own' -- every user (rank, slot) rotates by a stream of sign words of "
+                        "their own and is rotated back by it, still in one launch.  'own' is what makes the 'unbiased' errors average "
+                        "out over users whose gradients are alike; it costs one inverse rotation per user.  The wire is the same; "
+                        "not in ring mode")
+    p.add_argument('--eden-user-rotation', dest='eden_user_rotation', type=str, default='shared', choices=['shared', 'own'],
+                   help="--quantizer eden: 'shared' -- every user of one mean rotates by the same sign words; the mean is taken in the "
+                        "rotated domain and rotated back once -- or 'own' -- every user (rank, slot) rotates by a stream of sign words of "
+                        "their own and is rotated back by it, still in one launch.  'own' is what makes the 'unbiased' errors average "
+                        "out over users whose gradients are alike; it costs one inverse rotation per user.  The wire is the same; "
+                        "not in ring mode")
     p.add_argument('--eden-bits', dest='eden_bits', type=int, default=4, choices=[2, 3, 4],
                    help='--quantizer eden: bits per element of the rotated blocks (the nearest of 2^bits Lloyd-Max centroids of N(0,1); '
                         'one bit is --quantizer drive); the wire is bits + 0.125 bits per element')

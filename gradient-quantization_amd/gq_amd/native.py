@@ -636,14 +636,18 @@ class _ItemBatch(_Tables):
         """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
         return type(self)(seg_table, item_seg, nseg, nitems)
 
-    def decode(self, gathered, R, out, plain=False, rotation=None):
+    def decode(self, gathered, R, out, plain=False, rotation=None, first_stream=None):
         """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride.
-        rotation (DriveBatch / EdenBatch only): the { seed, step } pair -- the <prefix>decode_sum_batched_stepped launch."""
+        rotation (DriveBatch / EdenBatch only): the { seed, step } pair -- the <prefix>decode_sum_batched_stepped launch; with
+        first_stream (an int, needs the pair) the <prefix>decode_sum_batched_streams launch: payload r under stream first_stream + r."""
         assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
         stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
         args = (_dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R), _dev_ptr(out, self.dtype, "out"),
                 ctypes.c_int(1 if plain else 0), _stream())
-        if rotation is None:
+        if first_stream is not None:
+            name = self._decode_name + "_streams"
+            rc = getattr(self.L, name)(self.ref, _rotation_ptr(rotation), _stream_arg(first_stream), *args)
+        elif rotation is None:
             name, rc = self._decode_name, self._decode(self.ref, *args)
         else:
             name = self._decode_name + "_stepped"
@@ -1074,7 +1078,8 @@ class MXRBatch(MXBatch):
 # ---- the rotated 1-bit compressor (DRIVE): libgq_drive.so (include/gq_drive.h) -----------------------------------------------------
 DRIVE_ABI_VERSION = 1
 DRIVE_EXPORTS = ["gq_drive_abi_version", "gq_drive_last_error", "gq_drive_compress_batched", "gq_drive_decode_sum_batched",
-                 "gq_drive_compress_batched_stepped", "gq_drive_decode_sum_batched_stepped"]
+                 "gq_drive_compress_batched_stepped", "gq_drive_decode_sum_batched_stepped",
+                 "gq_drive_compress_batched_streams", "gq_drive_decode_sum_batched_streams"]
 DRIVE_BLOCK = 256           # GQ_DRIVE_BLOCK: elements that share a scale (a rotation block); an item is MX_ITEM_ELEMS
 DRIVE_UNBIASED, DRIVE_MSE = 0, 1      # GQ_DRIVE_UNBIASED / GQ_DRIVE_MSE
 DRIVE_SCALES = {"unbiased": DRIVE_UNBIASED, "mse": DRIVE_MSE}
@@ -1094,11 +1099,25 @@ def _rotation_ptr(rotation):
     return _dev_ptr(rotation, torch.int64, "rotation")
 
 
-def _rotated_compress(batch, name, wire, out, ef_scale, rotation):
-    """DriveBatch.compress / EdenBatch.compress: the entry point `name`, or with a rotation pair `name`_stepped."""
+def _stream_arg(stream):
+    """The stream of a *_streams launch (include/gq_drive.h: SIGNS, PER STREAM): an int that fits int32, passed by value.  A
+    negative one goes through: the library refuses it."""
+    if isinstance(stream, bool) or not isinstance(stream, int):
+        raise TypeError("stream must be an int, got %r" % (stream,))
+    if not -2 ** 31 <= stream < 2 ** 31:
+        raise ValueError("stream %d does not fit int32" % stream)
+    return ctypes.c_int32(stream)
+
+
+def _rotated_compress(batch, name, wire, out, ef_scale, rotation, stream=None):
+    """DriveBatch.compress / EdenBatch.compress: the entry point `name`, with a rotation pair `name`_stepped, with a pair and a
+    stream `name`_streams."""
     args = (_dev_ptr(wire, torch.uint8, "wire"), ctypes.c_float(_NAN if ef_scale is None else ef_scale),
             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-    if rotation is None:
+    if stream is not None:
+        name += "_streams"
+        rc = getattr(batch.L, name)(batch.ref, _rotation_ptr(rotation), _stream_arg(stream), *args)
+    elif rotation is None:
         rc = getattr(batch.L, name)(batch.ref, *args)
     else:
         name += "_stepped"
@@ -1117,7 +1136,9 @@ class DriveBatch(_ItemBatch):
     the dense decode and the residual) and gq_drive_decode_sum_batched (the mean in the rotated domain, one inverse rotation).
     No scratch and no draws.  scale_mode: DRIVE_UNBIASED or DRIVE_MSE; signs: the four 64-bit sign words (gq_mxr.h's).
     compress / decode with rotation= (a device int64 [1, 2] tensor, the { seed, step } pair of include/gq_drive.h's SIGNS, STEPPED):
-    the *_stepped entry points, which take the words of the step they find in the pair and do not read `signs`."""
+    the *_stepped entry points, which take the words of the step they find in the pair and do not read `signs`.  With stream= /
+    first_stream= beside the pair (SIGNS, PER STREAM): the *_streams entry points -- compress under that stream's words, payload r
+    of the decode-mean through its own inverse rotation under stream first_stream + r, the mean in the gradient's domain."""
 
     LIBRARY, STRUCT = DRIVE_LIBRARY, _DriveBatchStruct
 
@@ -1130,16 +1151,17 @@ class DriveBatch(_ItemBatch):
     def part(self, seg_table, item_seg, nseg, nitems):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.scale_mode, self.signs)
 
-    def compress(self, wire, out=None, ef_scale=None, rotation=None):
+    def compress(self, wire, out=None, ef_scale=None, rotation=None, stream=None):
         """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers); rotation: see the class."""
-        _rotated_compress(self, "gq_drive_compress_batched", wire, out, ef_scale, rotation)
+        (seg_table[:, 7] = error buffers); rotation, stream: see the class."""
+        _rotated_compress(self, "gq_drive_compress_batched", wire, out, ef_scale, rotation, stream)
 
 
 # ---- the rotated 2- / 3- / 4-bit compressor (EDEN): libgq_eden.so (include/gq_eden.h) ----------------------------------------------
 EDEN_ABI_VERSION = 1
 EDEN_EXPORTS = ["gq_eden_abi_version", "gq_eden_last_error", "gq_eden_compress_batched", "gq_eden_decode_sum_batched",
-                "gq_eden_compress_batched_stepped", "gq_eden_decode_sum_batched_stepped"]
+                "gq_eden_compress_batched_stepped", "gq_eden_decode_sum_batched_stepped",
+                "gq_eden_compress_batched_streams", "gq_eden_decode_sum_batched_streams"]
 EDEN_BLOCK = 256            # GQ_EDEN_BLOCK: elements that share a scale (a rotation block); an item is MX_ITEM_ELEMS
 EDEN_UNBIASED, EDEN_MSE = 0, 1        # GQ_EDEN_UNBIASED / GQ_EDEN_MSE
 EDEN_SCALES = {"unbiased": EDEN_UNBIASED, "mse": EDEN_MSE}
@@ -1164,7 +1186,8 @@ class EdenBatch(_ItemBatch):
     """The two launches of libgq_eden.so: gq_eden_compress_batched (b-bit Lloyd-Max codes of the rotated blocks and one f32 scale per
     block, + the dense decode and the residual) and gq_eden_decode_sum_batched (the mean in the rotated domain, one inverse
     rotation).  No scratch and no draws.  bits: 2, 3 or 4; scale_mode: EDEN_UNBIASED or EDEN_MSE; signs: the four 64-bit sign
-    words (gq_mxr.h's).  rotation= on compress / decode: DriveBatch's, on gq_eden_*_stepped."""
+    words (gq_mxr.h's).  rotation= (and stream= / first_stream=) on compress / decode: DriveBatch's, on gq_eden_*_stepped
+    (gq_eden_*_streams)."""
 
     LIBRARY, STRUCT = EDEN_LIBRARY, _EdenBatchStruct
 
@@ -1178,10 +1201,10 @@ class EdenBatch(_ItemBatch):
     def part(self, seg_table, item_seg, nseg, nitems):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.bits, self.s.scale_mode, self.signs)
 
-    def compress(self, wire, out=None, ef_scale=None, rotation=None):
+    def compress(self, wire, out=None, ef_scale=None, rotation=None, stream=None):
         """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers); rotation: see DriveBatch."""
-        _rotated_compress(self, "gq_eden_compress_batched", wire, out, ef_scale, rotation)
+        (seg_table[:, 7] = error buffers); rotation, stream: see DriveBatch."""
+        _rotated_compress(self, "gq_eden_compress_batched", wire, out, ef_scale, rotation, stream)
 
 
 # ---- threshold sparsification with a fitted threshold: libgq_thr.so (include/gq_thr.h) -----------------------------------------

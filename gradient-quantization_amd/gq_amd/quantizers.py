@@ -278,6 +278,14 @@ class PSQuantizer(object):
         stepped = [c for c in self.compressors if getattr(c, "rotation", None) == "step"]
         self._rotation_seed = int(stepped[0].seed) if stepped else None
         self._rotation_start = 0      # the step word a pair is made with (set_rotation_step before the first record)
+        # drive_user_rotation / eden_user_rotation = 'own' (include/gq_drive.h: SIGNS, PER STREAM): a record into wire slot s on rank k
+        # compresses under stream k * users per rank + s -- the payload's row of the gather, rank-major (gq_amd.exchange) -- and the
+        # aggregate rotates row r back under stream r.  The *_streams launches read a pair in either rotation mode: in step mode the
+        # one above; under 'fixed' a pair of the seed at step 0 that is NOT the quantizer's _rng_state, so nothing ever steps it.
+        own = [c for c in self.compressors if getattr(c, "user_rotation", None) == "own"]
+        self._own_seed = int(own[0].seed) if own else None
+        self._own_pair = None         # ('own' under the fixed rotation) the pair nobody steps
+        self._own_users = None        # users per rank the streams of the recorded payloads were numbered with
         self._ticket = None          # gq_hsq_levels_decode_batched's last-workgroup counter (one device word, zero between launches)
         self._rec_graphs = _GraphCache(self.MAX_ADDRESS_GRAPHS)    # (slot, user, wire, gradient addresses) -> [sightings, graph or None, headers]
         self._apply_graphs = _GraphCache()   # (users recorded, wire, output-buffer turns) -> [sightings, graph or None, decoded list]
@@ -418,6 +426,19 @@ class PSQuantizer(object):
     def _rotation_pair(self, device):
         """Step mode: the quantizer's { seed, step } pair on `device` (int64 [1, 2]; made by the first eager record, never under
         stream capture: its address is baked into every graph), handed to every Drive / Eden codec and group."""
+        if self._rotation_seed is None:      # ('own' under the fixed rotation: the seed at step 0, never handed to a stepping launch)
+            if self._own_pair is None or self._own_pair.device != device:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the rotation pair is made by the first eager record, not under stream capture")
+                seed = self._own_seed & (2 ** 64 - 1)
+                self._own_pair = torch.tensor([[seed - (2 ** 64 if seed & 2 ** 63 else 0), 0]], dtype=torch.int64).to(device)
+                for c in self.codecs:
+                    if getattr(c, "own", False):
+                        c.rotation = self._own_pair
+                for g in self._groups:
+                    if g[2] is not None and g[2].own:
+                        g[2].rotation = self._own_pair
+            return self._own_pair
         if self._rng_state is None or self._rng_state.device != device:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("the rotation pair is made by the first eager record, not under stream capture")
@@ -425,10 +446,10 @@ class PSQuantizer(object):
             step = self.rotation_step()      # (a pair that moves to another device keeps its step)
             self._rng_state = torch.tensor([[signed(self._rotation_seed), signed(step)]], dtype=torch.int64).to(device)
             for c in self.codecs:
-                if getattr(c, "stepped", False):
+                if getattr(c, "stepped", False) or getattr(c, "own", False):
                     c.rotation = self._rng_state
             for g in self._groups:
-                if g[2] is not None and getattr(g[2], "stepped", False):
+                if g[2] is not None and (getattr(g[2], "stepped", False) or g[2].own):
                     g[2].rotation = self._rng_state
         return self._rng_state
 
@@ -659,8 +680,9 @@ class PSQuantizer(object):
                         self._capture_step(fent, ent[2], all_grads, wire, slot, user, salt, scale, dev)
                 return
         self.record_paths["eager"] += 1
-        if self._rotation_seed is not None and dev.type == "cuda":
-            self._rotation_pair(dev)      # (step mode: the per-tensor route reads it too)
+        if (self._rotation_seed is not None or self._own_seed is not None) and dev.type == "cuda":
+            self._rotation_pair(dev)      # (step mode, own rotations: the per-tensor route reads it too)
+        stream = self._stream_for(slot, world, rank)      # (own rotations; None otherwise)
         skip = self._record_launches(all_grads, wire, slot, user, salt, scale, draws, dev)
         if len(skip) == self.num_layers:     # the usual case: everything went through the multi-tensor launches
             self.recorded += 1
@@ -679,6 +701,8 @@ class PSQuantizer(object):
                 continue
             codec, off = self.codecs[i], self.offsets[i]
             grad = param.grad.data
+            if stream is not None and getattr(codec, "own", False):
+                codec.stream = stream      # (until the end of this loop: every other compress of the codec is ONE payload, stream 0)
             if self.dgc_m is not None and isinstance(codec, TopKCodec):
                 self._record_dgc_single(i, grad, wire, user)
             elif self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
@@ -714,7 +738,26 @@ class PSQuantizer(object):
                     param.error[user].data = grad - decoded
             else:
                 codec.encode_into(grad, wire, off, salt, **self._slice(draws, i))
+            if stream is not None and getattr(codec, "own", False):
+                codec.stream = 0
         self.recorded += 1
+
+    def _stream_for(self, slot, world, rank):
+        """Own rotations: the stream of this rank's record into wire slot `slot` -- rank * users per rank + slot, the row the
+        payload has in the gather when every slot is recorded (gq_amd.exchange: rank-major).  It is a function of the slot, so a
+        record graph, keyed by the slot, holds it by value.  Sets the groups' stream_base; None without own rotations."""
+        if self._own_seed is None:
+            return None
+        users = self.capacity
+        if world > 1 and slot > 0 and self._own_users != users:
+            raise RuntimeError("own rotations: the users per rank changed from %r to %d between the records of one aggregate, which "
+                               "renumbers the streams of the payloads already recorded" % (self._own_users, users))
+        self._own_users = users
+        base = rank * users if world > 1 else 0
+        for g in self._groups:
+            if g[2] is not None and g[2].own:
+                g[2].stream_base = base
+        return base + slot
 
     MAX_ADDRESS_GRAPHS = 8      # graphs tied to one set of gradient addresses (the address-free ones are not counted)
 
@@ -756,8 +799,11 @@ class PSQuantizer(object):
             self._ticket_for(dev)      # (allocated and zeroed HERE, eagerly: a first use under stream capture would put it in a graph's pool)
         if getattr(obj, "counter", False) and len(self._groups) * self.RNG_SLOTS <= 256:
             obj.rng_pairs = self._rng_pairs_for(dev, self._groups.index(grp))
-        if getattr(obj, "stepped", False) and dev.type == "cuda":
+        if (getattr(obj, "stepped", False) or obj.own) and dev.type == "cuda":
             obj.rotation = self._rotation_pair(dev)
+        if obj.own:
+            world, rank = _dist_world(self.process_group)
+            obj.stream_base = rank * self.capacity if world > 1 else 0
         return obj
 
     def _ticket_for(self, dev):
@@ -1111,6 +1157,10 @@ class PSQuantizer(object):
                     self._decode_all(buf, False, pend, hold_step=self._rotation_seed is not None)      # (step mode: the real decode is still to come)
                 self.exchange_mode = ex.autotune(
                     step, preflight=lambda mode: ex.start(mode, self.recorded, self.cut, dry_run=True))
+            if self._own_seed is not None and self.recorded != ex.users:
+                # (the gather of fewer rows than slots is rank * recorded + slot, not the row the streams were numbered with)
+                raise RuntimeError("own rotations: %d of %d users per rank were recorded; with several ranks the aggregate needs "
+                                   "every slot recorded, a payload's stream is its row of the full gather" % (self.recorded, ex.users))
             gathered, pending = ex.start(self.exchange_mode, self.recorded, self.cut, cuts=self.cuts)
         else:
             gathered, pending = self._wire[:self.recorded], ()

@@ -35,6 +35,19 @@
  *              does not change by a byte: every payload of one decode-mean must have been compressed at the same (seed, step), and
  *              the decode-mean must run at that (seed, step).  Everything below is the same, word for word, in both forms.
  *
+ * SIGNS, PER STREAM   The *_streams entry points give every payload of one mean a rotation of its own (DRIVE and EDEN are schemes
+ *              for distributed mean estimation with one private rotation per client: the errors of R users then average out even
+ *              when their gradients are equal).  A stream sigma is a non-negative integer.  The sign words of (seed, step, sigma)
+ *              are the STEPPED words of (seed_sigma, step), with
+ *                  seed_0 = seed
+ *                  seed_sigma = fin(seed + sigma * 0xD6E8FEB86659FD93)    for sigma >= 1
+ *              fin: the finaliser above (the two multiplications and the three xor-shifts); all arithmetic on uint64, mod 2^64.
+ *              Stream 0 is therefore exactly the stepped rotation, bit for bit.  `rotation` is the same device { seed, step } pair,
+ *              ONE for the whole parameter list, read and never written.  compress takes its stream by value; payload r of a
+ *              decode-mean is decoded under stream  first_stream + r.  The wire does not change by a byte.  Transforms, code, scale,
+ *              wire section and decoded values below are the same, word for word, under the stream's words; the decode-mean is
+ *              DECODE-MEAN, PER STREAM.
+ *
  * FORWARD TRANSFORM of a block of w (w is g, or under error feedback w = g + ef_scale * err: the product rounded, then the sum,
  *              as in gq_mx.h) -- gq_mxr.h's, word for word:
  *     1. x_j = w_j with its sign bit xor-ed with the element's sign bit.  A bit operation.
@@ -85,6 +98,11 @@
  *                  m_j = (+0 + y_0j + ... + y_{R-1,j}) / (float)R        payloads ascending, a true division
  *              plain (R == 1 only):  m_j = y_0j as it is, no addition and no division.  Then ONE inverse transform, whatever R is;
  *              its first n elements go to out + out offset.  Every payload must have been compressed under the same sign words.
+ *
+ * DECODE-MEAN, PER STREAM   ONE launch over R payloads.  D_r = the inverse transform, under stream first_stream + r, of payload r's
+ *              decoded values y_r: R inverse transforms per block and no addition in the rotated domain.  In the gradient's domain
+ *                  m_j = (+0 + D_0j + ... + D_{R-1,j}) / (float)R        payloads ascending, one f32 addition each, a true division
+ *              plain (R == 1 only):  m_j = D_0j as it is.  The first n elements go to out + out offset.  NON-FINITE is as above.
  */
 #ifndef GQ_DRIVE_H
 #define GQ_DRIVE_H
@@ -144,6 +162,17 @@ int gq_drive_compress_batched_stepped(const gq_drive_batch *b, const uint64_t *r
                                       void *stream);
 int gq_drive_decode_sum_batched_stepped(const gq_drive_batch *b, const uint64_t *rotation, const uint8_t *gathered,
                                         int64_t user_stride_bytes, int R, float *out, int plain, void *stream);
+
+/*
+ * The same two launches under SIGNS, PER STREAM: `rotation` is the device { seed, step } pair (8-byte aligned), b->signs is not read;
+ * `stream` / `first_stream` are passed by value, payload r of the gather decodes under stream first_stream + r (DECODE-MEAN, PER
+ * STREAM).  ONE launch per call, no scratch, no LDS, every launch argument depends on the layout and the wire slot alone.  Refused:
+ * everything the stepped calls refuse, a negative stream or first_stream, and first_stream + R overflowing int32.
+ */
+int gq_drive_compress_batched_streams(const gq_drive_batch *b, const uint64_t *rotation, int32_t stream, uint8_t *wire, float ef_scale, float *out,
+                                      void *stream_handle);
+int gq_drive_decode_sum_batched_streams(const gq_drive_batch *b, const uint64_t *rotation, int32_t first_stream, const uint8_t *gathered,
+                                        int64_t user_stride_bytes, int R, float *out, int plain, void *stream_handle);
 
 #ifdef __cplusplus
 }

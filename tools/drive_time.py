@@ -15,6 +15,8 @@ Rows (one JSON line each):
                   `bar` is 1.05 for each of the three launches and `missed` lists every ratio above it.
 --rotation step: the rot_step rows alone -- the stepped launches against the fixed ones of --parent-lib, then an older libgq_drive.so
 (tools/rot_step_time.py).
+--user-rotation own: the rot_user rows alone -- the *_streams launches (per-user rotations) against the stepped and fixed ones of
+--parent-lib, then an older libgq_drive.so (tools/rot_user_time.py).
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -122,7 +124,14 @@ def main():
     ap.add_argument("--rotation", default=None, choices=["step"],
                     help="the rot_step rows alone (tools/rot_step_time.py): the stepped launches against the fixed ones of --parent-lib, here "
                          "an older libgq_drive.so")
+    ap.add_argument("--user-rotation", default=None, choices=["own"],
+                    help="the rot_user rows alone (tools/rot_user_time.py): the *_streams launches against the stepped and fixed ones of "
+                         "--parent-lib, here ONE older libgq_drive.so")
     a = ap.parse_args()
+    if a.user_rotation == "own":
+        import rot_user_time
+        parent = a.parent_lib[0] if isinstance(a.parent_lib, list) and a.parent_lib else a.parent_lib
+        return rot_user_time.main("drive", a.out, os.path.abspath(parent) if parent else None)
     if a.rotation == "step":
         import rot_step_time
         return rot_step_time.main("drive", a.out, a.parent_lib)

@@ -14,6 +14,8 @@ Rows (one JSON line each):
   resnet50_step   PSQuantizer record + apply over the ResNet-50 parameter list (tests/golden/resnet50_cifar_shapes.json), one
                   user, default launches (graph replay), gradients at fixed addresses: --quantizer eden at b = 2, 3, 4 next to
                   --quantizer drive and --quantizer mx --mx-rotate hadamard (fp4, nearest), alternated, three rounds each.
+--user-rotation own: the rot_user rows alone -- the *_streams launches (per-user rotations) against the stepped and fixed ones of
+--parent-lib, then an older libgq_eden.so (tools/rot_user_time.py).
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -129,7 +131,14 @@ def main():
     ap.add_argument("--rotation", default=None, choices=["step"],
                     help="the rot_step rows alone (tools/rot_step_time.py): the stepped launches against the fixed ones of --parent-lib, here "
                          "ONE older libgq_eden.so")
+    ap.add_argument("--user-rotation", default=None, choices=["own"],
+                    help="the rot_user rows alone (tools/rot_user_time.py): the *_streams launches against the stepped and fixed ones of "
+                         "--parent-lib, here ONE older libgq_eden.so")
     a = ap.parse_args()
+    if a.user_rotation == "own":
+        import rot_user_time
+        parent = a.parent_lib[0] if isinstance(a.parent_lib, list) and a.parent_lib else a.parent_lib
+        return rot_user_time.main("eden", a.out, os.path.abspath(parent) if parent else None)
     if a.rotation == "step":
         import rot_step_time
         if len(a.parent_lib) > 1:
