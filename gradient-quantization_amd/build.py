@@ -27,7 +27,8 @@ LIBS = {
     os.path.join(HERE, "libgq_drive.so"): ["drive.hip"],          # the rotated 1-bit compressor (DRIVE): signs of the rotated block and one f32 scale, on mxr.hip's rotation (csrc/hadamard.hpp)
     os.path.join(HERE, "libgq_eden.so"): ["eden.hip"],            # the rotated 2- / 3- / 4-bit compressor (EDEN): Lloyd-Max codes of the rotated block and one f32 scale, on the same rotation
     os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select
-    os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],     # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
+    os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select, one magnitude per tensor, a 16-bit word per kept element
+    os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],    # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean
     os.path.join(HERE, "libgq_maurey.so"): ["maurey.hip"],        # Maurey sparsification: the sampler's six launches and the decode-mean
     os.path.join(HERE, "libgq_kmeans.so"): ["kmeans.hip"],        # Lloyd k-means for training codebooks (gq_amd.codebook.train_codebook)

@@ -4,8 +4,9 @@
 from gq_amd.compressors import (IdenticalCompressor, QSGDCompressor, NearestNeighborCompressor,  # noqa: F401
                                 ProbabilisticScalarCompressor, ProbabilisticVectorCompressor,
                                 ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor,
-                                MaureySparsification, EdenCompressor, ThresholdSparsificationCompressor)
+                                MaureySparsification, EdenCompressor, ThresholdSparsificationCompressor,
+                                SparseTernaryCompressor)
 
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "EdenCompressor", "ThresholdSparsificationCompressor"]
+           "MaureySparsification", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor"]

@@ -15,7 +15,8 @@ device memory, through gq_amd.native).
     EdenCodec                  EdenCompressor: a 2-, 3- or 4-bit Lloyd-Max code per element of the rotated blocks, then an f32 scale per block
     ThrCodec                   ThresholdSparsificationCompressor: a 16-byte header (kept, found, threshold), then cap ascending uint32 indices and cap f32 values
     BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR /
-    BatchedDrive / BatchedEden / BatchedThr
+    STCCodec                   SparseTernaryCompressor: a 16-byte header (k, the magnitude), a uint32 start per item of 4,096 elements, then k 16-bit words
+    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -30,7 +31,7 @@ import torch
 
 from . import exchange, native
 from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
-                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
+                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
 
@@ -653,6 +654,38 @@ class ThrCodec(_SparseCodec):
         w = wire_user[off:off + 12].cpu().numpy()
         kept, found = (int(x) for x in w[:8].view("<u4"))
         return kept, found, float(w[8:12].view("<f4")[0])
+
+
+def stc_section_bytes(numel, cr):
+    """Bytes of one tensor's section of the sparse ternary wire (include/gq_stc.h): a 16-byte header, a uint32 start per item of 4,096
+    elements, k = numel // cr 16-bit words, zero bytes up to a multiple of 16."""
+    return _stc_bytes(numel, numel // cr)
+
+
+def _stc_bytes(numel, k):
+    return _up(native.STC_HEADER_BYTES + 4 * -(-numel // native.STC_CHUNK) + 2 * k)
+
+
+class STCCodec(_SparseCodec):
+    """SparseTernaryCompressor on the HIP kernels (libgq_stc.so).  Wire per tensor: { k, bits(mu), items, 0 }, the items' starts, then
+    k words  position inside the item | sign << 15  -- stc_section_bytes.  Every call is a one-tensor BatchedSTC; roundtrip /
+    encode_decode_into return the compress launches' own dense decode (copysign(mu, w) on the kept set), not a decode of the wire."""
+
+    def __init__(self, compressor, numel, shape, k=None):
+        """k: another count than numel // cr (the launches take any 0 <= k <= numel)."""
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.k = numel // compressor.cr if k is None else int(k)
+        if not 1 <= numel < 2 ** 31 or not 0 <= self.k <= numel:
+            raise ValueError("STCCodec: k = %d for a tensor of %d elements (1 ... 2^31 - 1)" % (self.k, numel))
+        self.nbytes = _stc_bytes(numel, self.k)
+
+    def _wire_bytes(self):
+        return self.nbytes      # (never empty: the header)
+
+    def header(self, wire_user, off):
+        """(k, mu) of this tensor's section of one user's wire: a read of two words, with a synchronisation."""
+        w = wire_user[off:off + 8].cpu().numpy()
+        return int(w[:4].view("<u4")[0]), float(w[4:8].view("<f4")[0])
 
 
 def sign_section_bytes(numel):
@@ -1741,10 +1774,14 @@ class BatchedTopK(_ItemGroup):
                                       lambda cd: max(1, -(-cd.numel // native.TOPK_CHUNK)), {4: [codecs[i].k for i in idxs]}, self.OUT_PAD)
         self.random = False
         # the select's scratch (include/gq_topk.h): the histograms start zero and every compress leaves them zero
-        self._hist = torch.zeros(nseg * native.TOPK_HIST_BINS, dtype=torch.int32, device=device)
-        self._state = torch.zeros(nseg * 4, dtype=torch.int32, device=device)
-        self._counts = torch.zeros(item * 2, dtype=torch.int32, device=device)
-        self._batch = self.BATCH(self._dev[:self._table_words], self.item_seg, nseg, item, self._hist, self._state, self._counts)
+        scratch = self._scratch(nseg, item, device)
+        self._hist, self._state, self._counts = scratch[:3]
+        self._batch = self.BATCH(self._dev[:self._table_words], self.item_seg, nseg, item, *scratch)
+
+    def _scratch(self, nseg, items, device):
+        """hist, state, counts (and what a subclass's launches take behind them)."""
+        return (torch.zeros(nseg * native.TOPK_HIST_BINS, dtype=torch.int32, device=device),
+                torch.zeros(nseg * 4, dtype=torch.int32, device=device), torch.zeros(items * 2, dtype=torch.int32, device=device))
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
                rng_slot=None, table_current=False, out=None):
@@ -2205,6 +2242,26 @@ class BatchedThr(_ItemGroup):
 ThrCodec.GROUP = BatchedThr
 
 
+class BatchedSTC(BatchedTopK):
+    """All SparseTernaryCompressor tensors in ONE gq_stc_compress_batched sequence (top-k's eight launches: the count launch also sums
+    the kept magnitudes per item, the scan launch folds them into mu, the write launch compacts 16-bit words -- include/gq_stc.h)
+    and ONE gq_stc_decode_sum_batched launch.  Tables, scratch, encode and the graph machinery are BatchedTopK's; `sums` is the one
+    buffer more."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is STCCodec
+
+    BATCH = native.STCBatch
+
+    def _scratch(self, nseg, items, device):
+        self._sums = torch.empty(items, dtype=torch.float64, device=device)
+        return BatchedTopK._scratch(self, nseg, items, device) + (self._sums,)
+
+
+STCCodec.GROUP = BatchedSTC
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -2228,6 +2285,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return EdenCodec(compressor, numel, shape)
     if isinstance(compressor, ThresholdSparsificationCompressor):
         return ThrCodec(compressor, numel, shape)
+    if isinstance(compressor, SparseTernaryCompressor):
+        return STCCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

@@ -850,6 +850,35 @@ class ThresholdSparsificationCompressor(object):
         return signature
 
 
+class SparseTernaryCompressor(object):
+    """Sparse ternary compression (Sattler et al. 2019; no counterpart in the reference's catalogue): top-k's kept set (k = size // cr,
+    the largest |w|, ties to the lowest indices), every kept value replaced by sign(w) * mu, mu the mean |w| of the kept set --
+    include/gq_stc.h defines the sum's order and every rounding.  compress returns the dense decode and decompress is the identity, as
+    for TopKSparsificationCompressor's device path.  HIP kernels only (libgq_stc.so): a float32 tensor on the device."""
+
+    def __init__(self, size, shape, args):
+        cr = getattr(args, "cr", None)
+        if isinstance(cr, bool) or not isinstance(cr, int) or cr < 1:
+            raise ValueError("cr must be a positive integer, got %r" % (cr,))
+        self.size, self.shape, self.cr = size, shape, cr
+        self.k = size // cr
+
+    def compress(self, vec):
+        from .codecs import STCCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("SparseTernaryCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), "
+                            "got %s on %s" % (vec.dtype, vec.device))
+        n = vec.numel()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = STCCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor"]
+           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor"]

@@ -33,7 +33,7 @@ import torch.optim as optim
 
 from .datasets import OnDiskClassification
 from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
-                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
+                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
 quantizer_choices = {          # main.py:20-26
@@ -49,6 +49,7 @@ quantizer_choices = {          # main.py:20-26
     'drive': DriveCompressor,                  # the rotated 1-bit compressor (--drive-scale, --drive-seed): 1.125 bits per element, likewise
     'eden': EdenCompressor,                    # the rotated 2- / 3- / 4-bit compressor (--eden-bits, --eden-scale, --eden-seed): bits + 0.125, likewise
     'threshold': ThresholdSparsificationCompressor,      # what exceeds a fitted or a given threshold (--thr-stages, --thr-value, --thr-cap-percent, --thr-fit-stride, --cr), likewise
+    'stc': SparseTernaryCompressor,            # sparse ternary compression: top-k's kept set (--cr) at one magnitude, a 16-bit word per kept element, likewise
 }
 
 

@@ -1255,6 +1255,53 @@ class ThrBatch(_ItemBatch):
         _check(rc, "gq_thr_compress_batched", THR_LIBRARY)
 
 
+# ---- sparse ternary compression: libgq_stc.so (include/gq_stc.h) -----------------------------------------------------------------
+STC_ABI_VERSION = 1
+STC_EXPORTS = ["gq_stc_abi_version", "gq_stc_last_error", "gq_stc_compress_batched", "gq_stc_decode_sum_batched"]
+STC_CHUNK = 4096            # GQ_STC_CHUNK: elements per item
+STC_HIST_BINS = 2048        # GQ_STC_HIST_BINS: histogram words per tensor
+STC_HEADER_BYTES = 16       # GQ_STC_HEADER_BYTES: k, bits(mu), nitems, 0 in front of a section's starts
+
+STC_LIBRARY = Library("libgq_stc.so", "GQ_STC_LIB_PATH", "gq_stc_", STC_ABI_VERSION, STC_EXPORTS)
+STC_LIB_PATH = STC_LIBRARY.path
+
+
+def stc_lib():
+    return STC_LIBRARY.handle or _load(STC_LIBRARY)
+
+
+class _STCBatchStruct(ctypes.Structure):      # gq_stc_batch (include/gq_stc.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("hist", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_STCBatchStruct) == 80      # (csrc/stc.hip asserts the same of gq_stc_batch)
+
+
+class STCBatch(_ItemBatch):
+    """The launches of libgq_stc.so: gq_stc_compress_batched (top-k's select, the magnitude mu, the 16-bit words, + the dense
+    decoded tensors and the residual) and gq_stc_decode_sum_batched.  hist (int32 [nseg * STC_HIST_BINS], zero), state (int32
+    [nseg * 4]), counts (int32 [nitems * 2]) and sums (float64 [nitems]) are the caller's scratch; the compress leaves hist zero
+    again."""
+
+    LIBRARY, STRUCT = STC_LIBRARY, _STCBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, hist=None, state=None, counts=None, sums=None):
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems,
+                            (("hist", hist, torch.int32), ("state", state, torch.int32), ("counts", counts, torch.int32),
+                             ("sums", sums, torch.float64)))
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
+        launches (seg_table[:, 7] = error buffers; needs out)."""
+        rc = self.L.gq_stc_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
+                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_stc_compress_batched", STC_LIBRARY)
+
+
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
 KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]

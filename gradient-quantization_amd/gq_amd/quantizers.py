@@ -31,7 +31,7 @@ import warnings
 import torch
 
 from . import exchange, native
-from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, ThresholdSparsificationCompressor,
+from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
                           TopKSparsificationCompressor, _next_seed, shared_seeds)
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
@@ -48,7 +48,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
     BatchedDGC, BatchedDrive, BatchedEden, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
-    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec,
+    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -185,6 +185,12 @@ class PSQuantizer(object):
             if odd:
                 raise ValueError("the threshold compressor takes float32 parameters only (its kernels read and write float32 "
                                  "gradients), got %s" % ", ".join(odd))
+        if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
+            # (include/gq_stc.h: float32 tensors only)
+            odd = sorted(set(str(p.dtype) for p in self.parameters if p.dtype != torch.float32))
+            if odd:
+                raise ValueError("the sparse ternary compressor takes float32 parameters only (its kernels read and write float32 "
+                                 "gradients), got %s" % ", ".join(odd))
         factory = codec_factory or quantizer_codec_factory
         self.aggregate_fma = aggregate_fma(args)     # opt-in fused accumulation of the decode-mean (R >= 2 only)
         self.wire_levels = wire_levels_mode(args, _dist_world(process_group)[0])      # "bytes" | "packed6" (6-bit levels where the configuration allows)
@@ -251,7 +257,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -354,6 +360,9 @@ class PSQuantizer(object):
         if isinstance(Compressor, type) and issubclass(Compressor, ThresholdSparsificationCompressor):
             raise ValueError("momentum_correction is not available with the threshold compressor: momentum factor masking is built on "
                              "the top-k wire (--quantizer topk)")
+        if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
+            raise ValueError("momentum_correction is not available with the sparse ternary compressor: momentum factor masking is built "
+                             "on the top-k wire (--quantizer topk)")
         if not (isinstance(Compressor, type) and issubclass(Compressor, TopKSparsificationCompressor)):
             raise ValueError("momentum_correction needs TopKSparsificationCompressor (--quantizer topk), got %s"
                              % getattr(Compressor, "__name__", Compressor))
@@ -1247,6 +1256,9 @@ class RingQuantizer(PSQuantizer):
         if isinstance(Compressor, type) and issubclass(Compressor, ThresholdSparsificationCompressor):
             raise ValueError("the threshold compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
                              "and its wire drops what exceeds the threshold beyond the capacity")
+        if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
+            raise ValueError("the sparse ternary compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
+                             "itself, and its wire carries one magnitude for the whole kept set")
         two_phase = args.two_phase
         args.two_phase = False           # ring_quantizer.py has no second phase and no server residual
         try:
