@@ -28,6 +28,7 @@ LIBS = {
     os.path.join(HERE, "libgq_eden.so"): ["eden.hip"],            # the rotated 2- / 3- / 4-bit compressor (EDEN): Lloyd-Max codes of the rotated block and one f32 scale, on the same rotation
     os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select
     os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select, one magnitude per tensor, a 16-bit word per kept element
+    os.path.join(HERE, "libgq_psgd.so"): ["psgd.hip"],            # low-rank compression (PowerSGD, rank 1 / 2 / 4): project, orthogonalise, back-project, fold, residual; the decode-mean of the factors
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],    # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean
     os.path.join(HERE, "libgq_maurey.so"): ["maurey.hip"],        # Maurey sparsification: the sampler's six launches and the decode-mean

@@ -5,8 +5,9 @@ from gq_amd.compressors import (IdenticalCompressor, QSGDCompressor, NearestNeig
                                 ProbabilisticScalarCompressor, ProbabilisticVectorCompressor,
                                 ResidualCompressor, SignSGDCompressor, TopKSparsificationCompressor,
                                 MaureySparsification, EdenCompressor, ThresholdSparsificationCompressor,
-                                SparseTernaryCompressor)
+                                SparseTernaryCompressor, PowerSGDCompressor)
 
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor"]
+           "MaureySparsification", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor",
+           "PowerSGDCompressor"]

@@ -16,7 +16,8 @@ device memory, through gq_amd.native).
     ThrCodec                   ThresholdSparsificationCompressor: a 16-byte header (kept, found, threshold), then cap ascending uint32 indices and cap f32 values
     BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR /
     STCCodec                   SparseTernaryCompressor: a 16-byte header (k, the magnitude), a uint32 start per item of 4,096 elements, then k 16-bit words
-    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC
+    PowerSGDCodec              PowerSGDCompressor: a 16-byte header (n, m, r), then the factors Ph (n x r) and Q' (m x r) as f32
+    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC / BatchedPowerSGD
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -31,7 +32,7 @@ import torch
 
 from . import exchange, native
 from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
-                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
+                          PowerSGDCompressor, QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
 
@@ -686,6 +687,77 @@ class STCCodec(_SparseCodec):
         """(k, mu) of this tensor's section of one user's wire: a read of two words, with a synchronisation."""
         w = wire_user[off:off + 8].cpu().numpy()
         return int(w[:4].view("<u4")[0]), float(w[4:8].view("<f4")[0])
+
+
+def psgd_section_bytes(n, m, r):
+    """Bytes of one tensor's section of the low-rank wire (include/gq_psgd.h): a 16-byte header, Ph (n x r) and Q' (m x r) as
+    float32, zero bytes up to a multiple of 16."""
+    return _up(native.PSGD_HEADER_BYTES + 4 * r * (n + m))
+
+
+def _uniform_bits(seed, idx):
+    """uniform_bits of csrc/gq_common.hpp over a uint64 array of indices (numpy, on the host)."""
+    import numpy as np
+    u64, m32 = np.uint64, np.uint64(0xFFFFFFFF)
+
+    def mul(a, c):
+        return (a * u64(c)) & m32
+
+    seed = u64(seed & (2 ** 64 - 1))
+    h = ((idx & m32) + mul(seed & m32, 0x9E3779B1)) & m32
+    h = h ^ (h >> u64(16))
+    h = mul(h, 0x7FEB352D)
+    h = h ^ (h >> u64(15))
+    h = mul(h, 0x846CA68B)
+    h = h ^ (h >> u64(16))
+    h = (h + ((seed >> u64(32)) ^ mul(idx >> u64(32), 0x85EBCA77))) & m32
+    h = mul(h, 0xC2B2AE3D)
+    return h ^ (h >> u64(15))
+
+
+def psgd_q0(seed, param_index, user, m, r):
+    """Q0 of include/gq_psgd.h, the warm start before the first record: float32 [m, r] on the host, 2 * uniform01 - 1 of the counter
+    hash under (seed, (parameter index << 12 | user) << 32 | element)."""
+    import numpy as np
+    if not 0 <= user < native.PSGD_MAX_USERS or not 0 <= param_index < 2 ** 20 or m * r >= 2 ** 32:
+        raise ValueError("psgd_q0: user %d (< %d), parameter %d (< 2^20), %d elements (< 2^32)" % (user, native.PSGD_MAX_USERS, param_index, m * r))
+    idx = (np.uint64(((param_index << 12) | user) << 32) | np.arange(m * r, dtype=np.uint64))
+    u = (_uniform_bits(seed, idx) >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return torch.from_numpy((np.float32(2.0) * u - np.float32(1.0)).astype(np.float32).reshape(m, r))
+
+
+class PowerSGDCodec(_SparseCodec):
+    """PowerSGDCompressor on the HIP kernels (libgq_psgd.so).  Wire per tensor: { n, m, r, 0 }, Ph (n x r), Q' (m x r), float32 --
+    psgd_section_bytes.  Every call is a one-tensor BatchedPowerSGD.  A record steps a warm start: the caller's (`q`, `user`; the
+    quantizer keeps one per parameter and user) or, where none is given, one this codec owns (user 0).  roundtrip /
+    encode_decode_into return the compress launches' own dense decode."""
+
+    SERVER_USER = native.PSGD_MAX_USERS - 1      # the key of the two-phase server's warm start
+
+    def __init__(self, compressor, numel, shape, param_index=0):
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.rank, self.seed, self.param_index = compressor.rank, compressor.seed, int(param_index)
+        nm = compressor.matrix(numel, tuple(shape))
+        if nm is None or min(nm) < self.rank or not 1 <= numel < 2 ** 31 or nm[0] * nm[1] != numel:
+            raise ValueError("PowerSGDCodec: a tensor of shape %r is no matrix of at least %d rows and columns" % (tuple(shape), self.rank))
+        self.n, self.m = nm
+        self.nbytes = psgd_section_bytes(self.n, self.m, self.rank)
+        self._q = None
+
+    def warm_start(self, param_index, user, device):
+        """Q0 of (this codec's seed, the parameter, the user) on the device: float32 [m, r]."""
+        return psgd_q0(self.seed, param_index, user, self.m, self.rank).to(device)
+
+    def encode_into(self, grad, wire_user, off, salt, out=None, err=None, ef_scale=None, q=None, user=0):
+        _require_device(grad, "PowerSGDCodec" + (".encode_decode_into" if out is not None else ".encode_into"))
+        flat = grad.contiguous().view(-1)
+        if q is None:
+            if self._q is None or self._q.device != flat.device:
+                self._q = self.warm_start(self.param_index, user, flat.device)
+            q = self._q
+        errs = ([err.view(-1)] if err is not None else None, [q], user)
+        ok = self._batched1(flat.device).encode([flat], self._at(wire_user, off), 0, salt, errs, ef_scale, out=out)
+        assert ok, "PowerSGDCodec: gradient, residual and warm start must be contiguous float32 tensors on the current device"
 
 
 def sign_section_bytes(numel):
@@ -2262,6 +2334,93 @@ class BatchedSTC(BatchedTopK):
 STCCodec.GROUP = BatchedSTC
 
 
+class BatchedPowerSGD(_ItemGroup):
+    """All PowerSGDCompressor tensors of one rank in ONE gq_psgd_compress_batched sequence (project, orthogonalise, back-project,
+    fold, + the residual launch under error feedback or where the dense decode is asked for -- include/gq_psgd.h) and ONE
+    gq_psgd_decode_sum_batched launch.  No draws: every launch replays from a HIP graph.  The group's item table is the TILE
+    table (64 rows x 256 columns: back-project, fold, residual and decode run a workgroup per tile); the project launch has an
+    item table of its own.  The warm starts are the caller's, as BatchedDGC's state is: encode's `errs` is
+    (error buffers or None, [Q per tensor], user) of ONE user, and the launches read a device table of those addresses, built once
+    per set of buffers and never moved (captured graphs hold its address)."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is PowerSGDCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.rank, codec.seed)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        mine = [codecs[i] for i in idxs]
+        self.rank, self.seed = mine[0].rank, mine[0].seed
+        R, P, RB, TC = self.rank, native.PSGD_PIECE, native.PSGD_ROW_BLOCK, native.PSGD_TILE_COLS
+        # 16-byte aligned views in the output buffer: the decode stores float4 there
+        nseg, tiles = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                       lambda cd: -(-cd.n // RB) * -(-cd.m // TC), {4: [cd.n for cd in mine]}, 4)
+        self.random = False
+        lay = torch.zeros((nseg, 4), dtype=torch.int64)
+        aitem_seg, aitem, pw, cp = [], 0, 0, 0
+        for s, cd in enumerate(mine):
+            pieces = 1 if cd.m <= P else -(-cd.m // P)
+            items = -(-cd.n // max(1, P // cd.m)) if cd.m <= P else cd.n * pieces
+            lay[s, 0], lay[s, 1], lay[s, 2], lay[s, 3] = aitem, pw, cp, cd.param_index << 12
+            aitem_seg += [s] * items
+            aitem += items
+            pw += cd.n * pieces * R
+            cp += -(-cd.n // RB) * cd.m * R
+        self._lay = lay.view(-1).to(device)
+        self._aitem_seg = torch.tensor(aitem_seg, dtype=torch.int32, device=device)
+        # scratch (include/gq_psgd.h): written before it is read in every compress
+        self._pwork = torch.empty(pw, dtype=torch.float32, device=device)
+        self._cpart = torch.empty(cp, dtype=torch.float32, device=device)
+        self._flags = torch.empty(nseg * 4, dtype=torch.int32, device=device)
+        self._batch = native.PSGDBatch(self._dev[:self._table_words], self.item_seg, nseg, tiles, rank=R, seed=self.seed, lay=self._lay,
+                                       aitem_seg=self._aitem_seg, naitems=aitem, pwork=self._pwork, cpart=self._cpart, flags=self._flags)
+        self._state_tables = {}
+
+    def _state_table(self, qs, user):
+        """The device table of these warm starts (include/gq_psgd.h: state), or None when they cannot be addressed."""
+        key = (tuple(map(_DATA_PTR, qs)), int(user))
+        tab = self._state_tables.get(key)
+        if tab is None:
+            dev_index = self.device.index if self.device.index is not None else torch._C._cuda_getDevice()
+            if (len(qs) != self.nseg or not 0 <= int(user) < native.PSGD_MAX_USERS or not all(map(_IS_CONTIGUOUS, qs))
+                    or set(map(_DTYPE_OF, qs)) != _F32_ONLY or set(map(_GET_DEVICE, qs)) != {dev_index} or any(p % 4 for p in key[0])
+                    or any(q.numel() != cd.m * self.rank for q, cd in zip(qs, self.codecs))):
+                return None
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("BatchedPowerSGD: a state table is built by an eager record, not under stream capture")
+            host = torch.tensor([[p, int(user)] for p in key[0]], dtype=torch.int64)
+            tab = self._state_tables[key] = (host.view(-1).to(self.device), list(qs))      # (the buffers stay alive with their table)
+        return tab[0]
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None):
+        """errs = (error buffers or None, [Q], user): one record of that user into the wire; out (float32 [out_floats]): also the
+        dense decode.  With error buffers: e <- M + ef_scale * e before the projection and e <- that - decoded after it, in place;
+        the gradients are read only.  graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
+        if errs is None:
+            raise ValueError("BatchedPowerSGD.encode: a record needs its user's warm starts, errs = (error buffers or None, [Q], user)")
+        ebufs, qs, user = errs
+        table = self._state_table(qs, user)
+        if table is None or not self._choose_header(tensors, slot, self.align, ebufs, dense, graph_header, table_current):
+            return False
+        self._batch.set_state(table)
+        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if ebufs is not None else None)
+        return True
+
+    def upload(self, tensors, slot, errs=None, dense=None):
+        """(in front of an address-free graph's replay: its launches read the state table of the buffers it was captured with --
+        the caller keys its graphs by the warm starts' addresses, and a table, once built, stays where it is)"""
+        if errs is None or (tuple(map(_DATA_PTR, errs[1])), int(errs[2])) not in self._state_tables:
+            return False
+        return _ItemGroup.upload(self, tensors, slot, errs[0], dense)
+
+
+PowerSGDCodec.GROUP = BatchedPowerSGD
+
+
 def default_codec_factory(compressor, numel, shape, packed6=False):
     if isinstance(compressor, ProbabilisticVectorCompressor):
         return PVQCodec(compressor, numel, shape, packed6)
@@ -2287,6 +2446,9 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return ThrCodec(compressor, numel, shape)
     if isinstance(compressor, SparseTernaryCompressor):
         return STCCodec(compressor, numel, shape)
+    if isinstance(compressor, PowerSGDCompressor):
+        # (a vector, a matrix thinner than the rank, factors no smaller than the tensor: uncompressed, whatever its size)
+        return PowerSGDCodec(compressor, numel, shape) if compressor.compresses else DenseCodec(compressor, numel, shape)
     return GenericCodec(compressor, numel, shape)
 
 

@@ -879,6 +879,60 @@ class SparseTernaryCompressor(object):
         return signature
 
 
+class PowerSGDCompressor(object):
+    """Low-rank compression (PowerSGD: Vogels, Karimireddy, Jaggi 2019; no counterpart in the reference's catalogue): the tensor as
+    the matrix M of shape[0] rows, one power iteration M Q -> orthogonalise -> M^T Ph from a warm start Q the caller of the kernels
+    owns, rank psgd_rank = 1, 2 or 4 -- include/gq_psgd.h defines every operation's order and rounding.  A tensor that is not a matrix,
+    has a side below the rank, or whose factors would be no smaller than the tensor itself, travels uncompressed (`compresses`).
+    compress returns the dense decode Ph Q'^T and steps this object's own warm start (user 0, parameter 0); decompress is the
+    identity.  HIP kernels only (libgq_psgd.so): a float32 tensor on the device."""
+
+    def __init__(self, size, shape, args):
+        r = getattr(args, "psgd_rank", 2)
+        if isinstance(r, bool) or r not in (1, 2, 4):
+            raise ValueError("psgd_rank must be 1, 2 or 4, got %r" % (r,))
+        seed = getattr(args, "psgd_seed", 0)
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError("psgd_seed must be an integer in [0, 2^64), got %r" % (seed,))
+        self.size, self.shape, self.rank, self.seed = size, tuple(shape), r, seed
+
+    @staticmethod
+    def matrix(size, shape):
+        """(n, m) of the matrix a tensor of this shape is, or None for what is not one."""
+        if len(shape) < 2 or size < 1 or shape[0] < 1:
+            return None
+        return int(shape[0]), int(size) // int(shape[0])
+
+    @property
+    def compresses(self):
+        """Whether a tensor of this size and shape is compressed at all (include/gq_psgd.h; otherwise it travels as it is)."""
+        nm = self.matrix(self.size, self.shape)
+        if nm is None or self.size <= 1000 or self.size >= 2 ** 31 or min(nm) < self.rank:
+            return False
+        return (16 + 4 * self.rank * (nm[0] + nm[1]) + 15) // 16 * 16 < 4 * self.size
+
+    def compress(self, vec):
+        from .codecs import BatchedPowerSGD, PowerSGDCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("PowerSGDCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), "
+                            "got %s on %s" % (vec.dtype, vec.device))
+        if vec.numel() != self.size or not self.compresses:
+            return vec.clone()
+        st = self.__dict__.get("_single")
+        if st is None or st[0].device != vec.device:
+            codec = PowerSGDCodec(self, self.size, self.shape)
+            st = self._single = (BatchedPowerSGD([codec], [0], [0], vec.device, 1, codec.nbytes), codec.warm_start(0, 0, vec.device))
+        grp, q = st
+        views = grp.roundtrip([vec.contiguous().view(-1)], 0, 0, (None, [q], 0))
+        if views is None:
+            raise TypeError("PowerSGDCompressor: the tensor must be 4-byte aligned float32 memory on the current HIP device")
+        return views[0].clone().view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
-           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor"]
+           "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor",
+           "PowerSGDCompressor"]

@@ -33,7 +33,7 @@ import torch.optim as optim
 
 from .datasets import OnDiskClassification
 from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
-                          QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
+                          PowerSGDCompressor, QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
 quantizer_choices = {          # main.py:20-26
@@ -50,6 +50,7 @@ quantizer_choices = {          # main.py:20-26
     'eden': EdenCompressor,                    # the rotated 2- / 3- / 4-bit compressor (--eden-bits, --eden-scale, --eden-seed): bits + 0.125, likewise
     'threshold': ThresholdSparsificationCompressor,      # what exceeds a fitted or a given threshold (--thr-stages, --thr-value, --thr-cap-percent, --thr-fit-stride, --cr), likewise
     'stc': SparseTernaryCompressor,            # sparse ternary compression: top-k's kept set (--cr) at one magnitude, a 16-bit word per kept element, likewise
+    'powersgd': PowerSGDCompressor,            # low-rank compression (--psgd-rank, --psgd-seed): one power iteration per record from a warm start, the two factors on the wire, likewise
 }
 
 
@@ -214,6 +215,11 @@ def build_parser():
                         "not in ring mode")
     p.add_argument('--eden-seed', dest='eden_seed', type=int, default=1,
                    help='--quantizer eden: the seed of the four sign words of its rotation (every rank must use the same)')
+    p.add_argument('--psgd-rank', dest='psgd_rank', type=int, default=2, choices=[1, 2, 4],
+                   help='--quantizer powersgd: the rank of the two factors a matrix-shaped tensor travels as (vectors, and matrices the '
+                        'factors would not shrink, travel uncompressed)')
+    p.add_argument('--psgd-seed', dest='psgd_seed', type=int, default=0,
+                   help="--quantizer powersgd: the seed of the warm starts' first values (per parameter and user, from the counter hash)")
     p.add_argument('--thr-stages', dest='thr_stages', type=int, default=3, choices=list(range(9)),
                    help='--quantizer threshold: passes of the threshold fit (a count-adaptive multi-stage exponential fit of the tail of '
                         '|g|, aiming at numel // cr kept elements); 0: no fit, the fixed threshold --thr-value')

@@ -1302,6 +1302,67 @@ class STCBatch(_ItemBatch):
         _check(rc, "gq_stc_compress_batched", STC_LIBRARY)
 
 
+# ---- low-rank compression (PowerSGD, rank 1 / 2 / 4): libgq_psgd.so (include/gq_psgd.h) ------------------------------------------
+PSGD_ABI_VERSION = 1
+PSGD_EXPORTS = ["gq_psgd_abi_version", "gq_psgd_last_error", "gq_psgd_compress_batched", "gq_psgd_decode_sum_batched"]
+PSGD_PIECE = 4096           # GQ_PSGD_PIECE: columns per piece of a long row
+PSGD_ROW_BLOCK = 64         # GQ_PSGD_ROW_BLOCK: rows per block of the back-projection, and of a tile
+PSGD_TILE_COLS = 256        # GQ_PSGD_TILE_COLS: columns per tile
+PSGD_HEADER_BYTES = 16      # GQ_PSGD_HEADER_BYTES: n, m, r, 0 in front of a section's factors
+PSGD_MAX_USERS = 4096       # GQ_PSGD_MAX_USERS: user < 4096 in the key of Q0; the two-phase server's warm start is user 4095
+
+PSGD_LIBRARY = Library("libgq_psgd.so", "GQ_PSGD_LIB_PATH", "gq_psgd_", PSGD_ABI_VERSION, PSGD_EXPORTS)
+PSGD_LIB_PATH = PSGD_LIBRARY.path
+
+
+def psgd_lib():
+    return PSGD_LIBRARY.handle or _load(PSGD_LIBRARY)
+
+
+class _PSGDBatchStruct(ctypes.Structure):      # gq_psgd_batch (include/gq_psgd.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("lay", ctypes.c_void_p), ("aitem_seg", ctypes.c_void_p),
+                ("naitems", ctypes.c_int64), ("state", ctypes.c_void_p), ("pwork", ctypes.c_void_p), ("cpart", ctypes.c_void_p),
+                ("flags", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("rank", ctypes.c_int32),
+                ("seed", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(_PSGDBatchStruct) == 112      # (csrc/psgd.hip asserts the same of gq_psgd_batch)
+
+
+class PSGDBatch(_ItemBatch):
+    """The launches of libgq_psgd.so: gq_psgd_compress_batched (project, orthogonalise, back-project, fold, + the residual and the
+    dense decode where asked for) over ONE user's state table (set_state) and gq_psgd_decode_sum_batched.  The item table of the
+    base class is the TILE table (the decode's grid); lay, aitem_seg, pwork, cpart and flags are what a compress takes beside it."""
+
+    LIBRARY, STRUCT = PSGD_LIBRARY, _PSGDBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, rank=2, seed=0, lay=None, aitem_seg=None, naitems=0, pwork=None, cpart=None,
+                 flags=None):
+        self.rank, self.seed = int(rank), int(seed)
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems,
+                            (("lay", lay, torch.int64), ("aitem_seg", aitem_seg, torch.int32), ("pwork", pwork, torch.float32),
+                             ("cpart", cpart, torch.float32), ("flags", flags, torch.int32)),
+                            rank=self.rank, seed=self.seed & (2 ** 64 - 1), naitems=int(naitems))
+        self.keep_state = None
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        return type(self)(seg_table, item_seg, nseg, nitems, rank=self.rank, seed=self.seed)
+
+    def set_state(self, state_table):
+        """state_table: int64 [nseg * 2] on the device, one user's { Q, user } per tensor; None: none (a compress refuses)."""
+        self.keep_state = state_table
+        self.s.state = _dev_ptr(state_table, torch.int64, "state").value if state_table is not None else None
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
+        launches (seg_table[:, 7] = error buffers)."""
+        rc = self.L.gq_psgd_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
+                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
+        _check(rc, "gq_psgd_compress_batched", PSGD_LIBRARY)
+
+
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
 KMEANS_EXPORTS = ["gq_kmeans_abi_version", "gq_kmeans_last_error", "gq_kmeans_workspace_bytes", "gq_kmeans_assign", "gq_kmeans_run"]

@@ -31,7 +31,7 @@ import warnings
 import torch
 
 from . import exchange, native
-from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
+from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, PowerSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
                           TopKSparsificationCompressor, _next_seed, shared_seeds)
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
@@ -48,7 +48,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
     BatchedDGC, BatchedDrive, BatchedEden, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
-    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec,
+    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec, BatchedPowerSGD, PowerSGDCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -191,6 +191,15 @@ class PSQuantizer(object):
             if odd:
                 raise ValueError("the sparse ternary compressor takes float32 parameters only (its kernels read and write float32 "
                                  "gradients), got %s" % ", ".join(odd))
+        if isinstance(Compressor, type) and issubclass(Compressor, PowerSGDCompressor):
+            # (include/gq_psgd.h: float32 tensors only; a user is 12 bits of the warm starts' key, the last one the server's)
+            odd = sorted(set(str(p.dtype) for p in self.parameters if p.dtype != torch.float32))
+            if odd:
+                raise ValueError("the low-rank compressor takes float32 parameters only (its kernels read and write float32 "
+                                 "gradients), got %s" % ", ".join(odd))
+            if int(args.num_users) >= PowerSGDCodec.SERVER_USER:
+                raise ValueError("the low-rank compressor keeps a warm start per user for fewer than %d users, got %d"
+                                 % (PowerSGDCodec.SERVER_USER, int(args.num_users)))
         factory = codec_factory or quantizer_codec_factory
         self.aggregate_fma = aggregate_fma(args)     # opt-in fused accumulation of the decode-mean (R >= 2 only)
         self.wire_levels = wire_levels_mode(args, _dist_world(process_group)[0])      # "bytes" | "packed6" (6-bit levels where the configuration allows)
@@ -220,6 +229,16 @@ class PSQuantizer(object):
             if self.dgc_m is not None and isinstance(comp, TopKSparsificationCompressor):
                 param.dgc_u = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
                 param.dgc_v = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
+            if isinstance(self.codecs[-1], PowerSGDCodec):
+                # the warm starts (include/gq_psgd.h: Q, m x r), per parameter and user like param.dgc_u: param.psgd_q[user], and
+                # the server's for the two-phase re-compress of the mean, like param.server_error.  They start at Q0 of (seed,
+                # parameter index, user) and every record steps its user's; warm_starts() / set_warm_starts() for a resume.
+                codec, i = self.codecs[-1], len(self.codecs) - 1
+                codec.param_index = i
+                param.psgd_q = [codec.warm_start(i, u, param.device) for u in range(args.num_users)]
+                if self.two_phase:
+                    param.psgd_server_q = codec.warm_start(i, codec.SERVER_USER, param.device)
+        self._psgd = any(isinstance(c, PowerSGDCodec) for c in self.codecs)
         # wire layout of one user: 16-byte aligned sections for the compressed tensors first, then ONE
         # packed region with the raw f32 of all identity-compressed (<= 1000 element) tensors
         self.offsets = [0] * self.num_layers
@@ -257,7 +276,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC, BatchedPowerSGD):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -363,6 +382,9 @@ class PSQuantizer(object):
         if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
             raise ValueError("momentum_correction is not available with the sparse ternary compressor: momentum factor masking is built "
                              "on the top-k wire (--quantizer topk)")
+        if isinstance(Compressor, type) and issubclass(Compressor, PowerSGDCompressor):
+            raise ValueError("momentum_correction is not available with the low-rank compressor: momentum factor masking is built "
+                             "on the top-k wire (--quantizer topk)")
         if not (isinstance(Compressor, type) and issubclass(Compressor, TopKSparsificationCompressor)):
             raise ValueError("momentum_correction needs TopKSparsificationCompressor (--quantizer topk), got %s"
                              % getattr(Compressor, "__name__", Compressor))
@@ -378,7 +400,49 @@ class PSQuantizer(object):
         if self.dgc_m is not None:
             ps = [self.parameters[i] for i in idxs]
             return ([p.dgc_u[user] for p in ps], [p.dgc_v[user] for p in ps])
-        return [self.parameters[i].error[user] for i in idxs] if self.error_feedback else None
+        errs = [self.parameters[i].error[user] for i in idxs] if self.error_feedback else None
+        if self._psgd and isinstance(self.codecs[idxs[0]], PowerSGDCodec):      # (BatchedPowerSGD.encode: the user's warm starts ride along)
+            return (errs, [self.parameters[i].psgd_q[user] for i in idxs], user)
+        return errs
+
+    def _record_psgd_single(self, i, grad, wire, user, scale):
+        """The per-tensor route of a low-rank record: the same launches over a one-tensor group on the user's warm start, error
+        feedback inside them (the launches read a contiguous float32 copy of a gradient they cannot address)."""
+        param, codec = self.parameters[i], self.codecs[i]
+        flat = grad.detach().to(torch.float32).contiguous().view(-1)
+        if flat.data_ptr() % 4:
+            flat = flat.clone()
+        err = None
+        if self.error_feedback:
+            err = param.error[user]
+            if not (err.is_contiguous() and err.dtype == torch.float32 and err.device == flat.device):
+                err = param.error[user] = err.to(device=flat.device, dtype=torch.float32).contiguous()
+        codec.encode_into(flat, wire, self.offsets[i], 0, err=err, ef_scale=scale if err is not None else None, q=param.psgd_q[user], user=user)
+
+    def warm_starts(self):
+        """The low-rank compressor's warm starts for a checkpoint: {parameter index: {"users": [Q of user 0, 1, ...], "server": Q of
+        the two-phase server or None}}, copies on the host ({} with another compressor).  A read of device memory: it synchronises."""
+        out = {}
+        for i, p in enumerate(self.parameters):
+            if hasattr(p, "psgd_q"):
+                srv = getattr(p, "psgd_server_q", None)
+                out[i] = {"users": [q.detach().cpu().clone() for q in p.psgd_q], "server": srv.detach().cpu().clone() if srv is not None else None}
+        return out
+
+    def set_warm_starts(self, state):
+        """Restore what warm_starts() returned (a resume).  The values are copied INTO the quantizer's buffers, whose addresses the
+        launches' tables and the captured graphs hold; ValueError for a state of another model or configuration."""
+        mine = {i for i, p in enumerate(self.parameters) if hasattr(p, "psgd_q")}
+        if set(state) != mine:
+            raise ValueError("set_warm_starts: the state names the parameters %r, this quantizer's low-rank tensors are %r" % (sorted(state), sorted(mine)))
+        for i in sorted(mine):
+            p, ent = self.parameters[i], state[i]
+            srv = getattr(p, "psgd_server_q", None)
+            pairs = list(zip(p.psgd_q, ent["users"])) + ([(srv, ent["server"])] if srv is not None else [])
+            if len(ent["users"]) != len(p.psgd_q) or any(s is None or tuple(s.shape) != tuple(q.shape) or s.dtype != torch.float32 for q, s in pairs):
+                raise ValueError("set_warm_starts: parameter %d: %d users of float32 %r expected%s" % (i, len(p.psgd_q), tuple(p.psgd_q[0].shape), ", and the server's" if srv is not None else ""))
+            for q, s in pairs:
+                q.copy_(s)
 
     def _record_dgc_single(self, i, grad, wire, user):
         """The per-tensor route of a record with momentum correction: the same three launches over a one-tensor group, for a
@@ -659,6 +723,10 @@ class PSQuantizer(object):
                 state = tuple(t.data_ptr() for p in self.parameters if hasattr(p, "dgc_u") for t in (p.dgc_u[user], p.dgc_v[user]))
                 graph_key += (state,)
                 generic_key += (state,)
+            if self._psgd:      # likewise the warm starts' addresses, in the low-rank launches' state table
+                state = tuple(p.psgd_q[user].data_ptr() for p in self.parameters if hasattr(p, "psgd_q"))
+                graph_key += (state,)
+                generic_key += (state,)
             if not self._all_f32:      # (every gradient contiguous and of its parameter's dtype: what the groups' uploads were checked with)
                 plain_f32 = all(map(_IS_CONTIGUOUS, all_grads)) and list(map(_DTYPE_OF, all_grads)) == self._dtypes
             else:
@@ -714,6 +782,8 @@ class PSQuantizer(object):
                 codec.stream = stream      # (until the end of this loop: every other compress of the codec is ONE payload, stream 0)
             if self.dgc_m is not None and isinstance(codec, TopKCodec):
                 self._record_dgc_single(i, grad, wire, user)
+            elif isinstance(codec, PowerSGDCodec):
+                self._record_psgd_single(i, grad, wire, user, scale)
             elif self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
                 # a bfloat16 gradient: the sum and the residual in the compress launch itself, which keeps them unrounded (a torch
                 # add_ would narrow grad + scale*error before the residual is taken)
@@ -1068,6 +1138,8 @@ class PSQuantizer(object):
                 # ps_quantizer.py:52-61, replicated on every rank (salt 0, the ranks' shared seed stream); with error
                 # feedback g += server_error and server_error = g - decoded happen inside the launches
                 serr = [self.parameters[i].server_error for i in idxs] if self.error_feedback else None
+                if cls is BatchedPowerSGD:      # (the server's warm starts ride along: ONE payload, a state of its own)
+                    serr = (serr, [self.parameters[i].psgd_server_q for i in idxs], PowerSGDCodec.SERVER_USER)
                 hdr = phase2_headers[gi] if phase2_headers is not None else None      # (capture: the device copy of THIS launch's table)
                 with shared_seeds(self._second_phase_seed):
                     dec = obj.roundtrip(list(gs), self.capacity, 0, serr, 1.0, draws=draws2, rng_slot=self.TWO_PHASE_RNG_SLOT,
@@ -1133,7 +1205,16 @@ class PSQuantizer(object):
                 param, codec, g = self.parameters[i], self.codecs[i], done[i]
                 kw = self._slice(draws2, i)
                 with shared_seeds(self._second_phase_seed):
-                    if self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
+                    if isinstance(codec, PowerSGDCodec):
+                        # (the server's warm start; sum and residual inside the launches)
+                        g = g.contiguous()
+                        out = torch.empty(codec.numel, dtype=torch.float32, device=g.device)
+                        tmp = torch.empty(codec._wire_bytes(), dtype=torch.uint8, device=g.device)
+                        ef = self.error_feedback
+                        codec.encode_into(g, tmp, 0, 0, out=out, err=param.server_error if ef else None, ef_scale=1.0 if ef else None,
+                                          q=param.psgd_server_q, user=codec.SERVER_USER)
+                        g = out.view(codec.shape)
+                    elif self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
                         # (a bfloat16 mean: sum and residual inside the launch, unrounded -- see record())
                         g = g.contiguous()
                         out = torch.empty(codec.numel, dtype=codec.dtype, device=g.device)
@@ -1259,6 +1340,9 @@ class RingQuantizer(PSQuantizer):
         if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
             raise ValueError("the sparse ternary compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
                              "itself, and its wire carries one magnitude for the whole kept set")
+        if isinstance(Compressor, type) and issubclass(Compressor, PowerSGDCompressor):
+            raise ValueError("the low-rank compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
+                             "itself, and its warm start belongs to one user's gradients, not to the running sum of the users before it")
         two_phase = args.two_phase
         args.two_phase = False           # ring_quantizer.py has no second phase and no server residual
         try:
