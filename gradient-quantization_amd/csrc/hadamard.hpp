@@ -1,4 +1,4 @@
-// The 256-point randomized Hadamard rotation libgq_mxr.so (mxr.hip) and libgq_drive.so (drive.hip) share, in registers
+// The 256-point randomized Hadamard rotation libgq_mxr.so (mxr.hip), libgq_drive.so (drive.hip) and libgq_eden.so (eden.hip) share, in registers
 // (include/gq_mxr.h: the transform, to the bit).  Internal linkage: each library compiles its own copy.
 // A lane owns eight consecutive elements, so 32 lanes own a rotation block of 256: the Walsh-Hadamard transform is three
 // butterfly stages inside the lane (strides 1, 2, 4) and five across lanes (strides 8 ... 128 = lane xor 1, 2, 4, 8, 16), which
@@ -125,7 +125,7 @@ __device__ __forceinline__ void stages_and_scale(float (&x)[HAD_PER_LANE]) {
 
 __device__ __forceinline__ float flip(float v, uint32_t sbyte, int k) { return __uint_as_float(__float_as_uint(v) ^ (((sbyte >> k) & 1u) << 31)); }
 
-// The rotation by H * diag(signs) / 16 over blocks of 256, as the policy csrc/mx_kernels.hpp asks for (drive.hip calls forward
+// The rotation by H * diag(signs) / 16 over blocks of 256, as the policy csrc/mx_kernels.hpp asks for (csrc/rotq_kernels.hpp calls forward
 // and inverse with rot = true: its blocks are zero-padded, every one is rotated); it carries the lane's sign byte.
 struct Hadamard {
     using Args = Signs;
@@ -134,7 +134,7 @@ struct Hadamard {
     uint32_t sbyte;
     __device__ __forceinline__ explicit Hadamard(const Signs &s) : sbyte(sign_byte(s)) {}
     __device__ __forceinline__ explicit Hadamard(const SignByte &b) : sbyte(b.v) {}
-    __device__ __forceinline__ explicit Hadamard(const Stepped &r) : Hadamard(stepped_sign_byte(r.pair)) {}      // (drive.hip / eden.hip)
+    __device__ __forceinline__ explicit Hadamard(const Stepped &r) : Hadamard(stepped_sign_byte(r.pair)) {}      // (csrc/rotq_kernels.hpp)
     __device__ __forceinline__ explicit Hadamard(const Streamed &r) : Hadamard(stream_sign_byte(r.pair[0], r.pair[1], r.sigma)) {}
     // w -> x' (rot; otherwise x' = w)
     __device__ __forceinline__ const HadLane &forward(const HadLane &w, HadLane &x, bool rot) const {

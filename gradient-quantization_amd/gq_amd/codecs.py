@@ -908,13 +908,18 @@ class DriveCodec(_SparseCodec):
     rotation = None      # the { seed, step } pair (device int64 [1, 2]) of a stepped or `own` codec inside a quantizer
     stream = 0           # own: the stream of the next compress
 
+    _SCALES = native.DRIVE_SCALES      # the compressor's `scale` -> the descriptor's scale_mode
+
     def __init__(self, compressor, numel, shape):
         self.c, self.numel, self.shape = compressor, numel, shape
         if numel < 1:
-            raise ValueError("DriveCodec: a tensor of %d elements" % numel)
-        self.scale_mode = native.DRIVE_SCALES[compressor.scale]
+            raise ValueError("%s: a tensor of %d elements" % (type(self).__name__, numel))
+        self.scale_mode = self._SCALES[compressor.scale]
         self._rotation_of(compressor)
-        self.nbytes = drive_section_bytes(numel)
+        self.nbytes = self._section_bytes()
+
+    def _section_bytes(self):
+        return drive_section_bytes(self.numel)
 
     def _rotation_of(self, compressor):
         self.signs = tuple(int(w) for w in compressor.signs)
@@ -955,14 +960,14 @@ class EdenCodec(DriveCodec):
     block -- eden_section_bytes, bits + 0.125 bits per element.  Otherwise DriveCodec: the decode ends with an inverse rotation, no
     draws, every call is a one-tensor BatchedEden."""
 
+    _SCALES = native.EDEN_SCALES
+
     def __init__(self, compressor, numel, shape):
-        self.c, self.numel, self.shape = compressor, numel, shape
-        if numel < 1:
-            raise ValueError("EdenCodec: a tensor of %d elements" % numel)
         self.bits = int(compressor.bits)
-        self.scale_mode = native.EDEN_SCALES[compressor.scale]
-        self._rotation_of(compressor)
-        self.nbytes = eden_section_bytes(numel, self.bits)
+        DriveCodec.__init__(self, compressor, numel, shape)
+
+    def _section_bytes(self):
+        return eden_section_bytes(self.numel, self.bits)
 
 
 _DATA_PTR = torch.Tensor.data_ptr

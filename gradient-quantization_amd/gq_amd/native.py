@@ -1110,7 +1110,7 @@ def _stream_arg(stream):
 
 
 def _rotated_compress(batch, name, wire, out, ef_scale, rotation, stream=None):
-    """DriveBatch.compress / EdenBatch.compress: the entry point `name`, with a rotation pair `name`_stepped, with a pair and a
+    """_RotatedBatch.compress (DriveBatch, EdenBatch): the entry point `name`, with a rotation pair `name`_stepped, with a pair and a
     stream `name`_streams."""
     args = (_dev_ptr(wire, torch.uint8, "wire"), ctypes.c_float(_NAN if ef_scale is None else ef_scale),
             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
@@ -1131,7 +1131,31 @@ class _DriveBatchStruct(ctypes.Structure):    # gq_drive_batch (include/gq_drive
                 ("ndense", ctypes.c_int32), ("scale_mode", ctypes.c_int32), ("signs", ctypes.c_uint64 * 4)]
 
 
-class DriveBatch(_ItemBatch):
+class _RotatedBatch(_ItemBatch):
+    """What DriveBatch and EdenBatch share: the four sign words last in the descriptor, a decode-only part() under the same
+    fields, and compress on <COMPRESS>, <COMPRESS>_stepped or <COMPRESS>_streams.  A subclass states LIBRARY, STRUCT, COMPRESS and,
+    in the order of its constructor's arguments, the descriptor's FIELDS in front of the sign words."""
+
+    COMPRESS, FIELDS = None, ()
+
+    def _bind(self, seg_table, item_seg, nseg, nitems, signs, **fields):
+        signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
+        assert len(signs) == 4
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, signs=(ctypes.c_uint64 * 4)(*signs),
+                            **{k: int(v) for k, v in fields.items()})
+        self.signs = signs
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        # (positional: FIELDS is the order of the subclass's constructor arguments between nitems and signs)
+        return type(self)(seg_table, item_seg, nseg, nitems, *([getattr(self.s, f) for f in self.FIELDS] + [self.signs]))
+
+    def compress(self, wire, out=None, ef_scale=None, rotation=None, stream=None):
+        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
+        (seg_table[:, 7] = error buffers); rotation, stream: see DriveBatch."""
+        _rotated_compress(self, self.COMPRESS, wire, out, ef_scale, rotation, stream)
+
+
+class DriveBatch(_RotatedBatch):
     """The two launches of libgq_drive.so: gq_drive_compress_batched (sign bits of the rotated blocks and one f32 scale per block, +
     the dense decode and the residual) and gq_drive_decode_sum_batched (the mean in the rotated domain, one inverse rotation).
     No scratch and no draws.  scale_mode: DRIVE_UNBIASED or DRIVE_MSE; signs: the four 64-bit sign words (gq_mxr.h's).
@@ -1140,21 +1164,10 @@ class DriveBatch(_ItemBatch):
     first_stream= beside the pair (SIGNS, PER STREAM): the *_streams entry points -- compress under that stream's words, payload r
     of the decode-mean through its own inverse rotation under stream first_stream + r, the mean in the gradient's domain."""
 
-    LIBRARY, STRUCT = DRIVE_LIBRARY, _DriveBatchStruct
+    LIBRARY, STRUCT, COMPRESS, FIELDS = DRIVE_LIBRARY, _DriveBatchStruct, "gq_drive_compress_batched", ("scale_mode",)
 
     def __init__(self, seg_table, item_seg, nseg, nitems, scale_mode=DRIVE_UNBIASED, signs=(0, 0, 0, 0)):
-        signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
-        assert len(signs) == 4
-        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, scale_mode=int(scale_mode), signs=(ctypes.c_uint64 * 4)(*signs))
-        self.signs = signs
-
-    def part(self, seg_table, item_seg, nseg, nitems):
-        return type(self)(seg_table, item_seg, nseg, nitems, self.s.scale_mode, self.signs)
-
-    def compress(self, wire, out=None, ef_scale=None, rotation=None, stream=None):
-        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers); rotation, stream: see the class."""
-        _rotated_compress(self, "gq_drive_compress_batched", wire, out, ef_scale, rotation, stream)
+        self._bind(seg_table, item_seg, nseg, nitems, signs, scale_mode=scale_mode)
 
 
 # ---- the rotated 2- / 3- / 4-bit compressor (EDEN): libgq_eden.so (include/gq_eden.h) ----------------------------------------------
@@ -1182,29 +1195,17 @@ class _EdenBatchStruct(ctypes.Structure):     # gq_eden_batch (include/gq_eden.h
                 ("signs", ctypes.c_uint64 * 4)]
 
 
-class EdenBatch(_ItemBatch):
+class EdenBatch(_RotatedBatch):
     """The two launches of libgq_eden.so: gq_eden_compress_batched (b-bit Lloyd-Max codes of the rotated blocks and one f32 scale per
     block, + the dense decode and the residual) and gq_eden_decode_sum_batched (the mean in the rotated domain, one inverse
     rotation).  No scratch and no draws.  bits: 2, 3 or 4; scale_mode: EDEN_UNBIASED or EDEN_MSE; signs: the four 64-bit sign
     words (gq_mxr.h's).  rotation= (and stream= / first_stream=) on compress / decode: DriveBatch's, on gq_eden_*_stepped
     (gq_eden_*_streams)."""
 
-    LIBRARY, STRUCT = EDEN_LIBRARY, _EdenBatchStruct
+    LIBRARY, STRUCT, COMPRESS, FIELDS = EDEN_LIBRARY, _EdenBatchStruct, "gq_eden_compress_batched", ("bits", "scale_mode")
 
     def __init__(self, seg_table, item_seg, nseg, nitems, bits=4, scale_mode=EDEN_UNBIASED, signs=(0, 0, 0, 0)):
-        signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
-        assert len(signs) == 4
-        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, scale_mode=int(scale_mode), bits=int(bits),
-                            signs=(ctypes.c_uint64 * 4)(*signs))
-        self.signs = signs
-
-    def part(self, seg_table, item_seg, nseg, nitems):
-        return type(self)(seg_table, item_seg, nseg, nitems, self.s.bits, self.s.scale_mode, self.signs)
-
-    def compress(self, wire, out=None, ef_scale=None, rotation=None, stream=None):
-        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers); rotation, stream: see DriveBatch."""
-        _rotated_compress(self, "gq_eden_compress_batched", wire, out, ef_scale, rotation, stream)
+        self._bind(seg_table, item_seg, nseg, nitems, signs, bits=bits, scale_mode=scale_mode)
 
 
 # ---- threshold sparsification with a fitted threshold: libgq_thr.so (include/gq_thr.h) -----------------------------------------

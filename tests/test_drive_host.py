@@ -147,6 +147,11 @@ def test_drive_library_is_built_and_exports_its_abi():
     for f in ("mxr.hip", "drive.hip"):
         text = open(os.path.join(csrc, f)).read()
         assert '#include "hadamard.hpp"' in text and "ds_swizzle" not in text.split("#include", 1)[1]
+    # drive.hip and eden.hip share their kernels and their host path through one header, which has no exchange of its own
+    assert "ds_swizzle" not in open(os.path.join(csrc, "rotq_kernels.hpp")).read()
+    for f in ("drive.hip", "eden.hip"):
+        text = open(os.path.join(csrc, f)).read()
+        assert '#include "rotq_kernels.hpp"' in text and "__global__" not in text
     assert "__builtin_amdgcn_ds_swizzle" in open(os.path.join(csrc, "hadamard.hpp")).read()
 
 

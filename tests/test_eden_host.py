@@ -164,7 +164,8 @@ def test_eden_library_is_built_and_exports_its_abi():
     assert names == [f[0] for f in native._DriveBatchStruct._fields_][:-1] + ["bits", "reserved", "signs"]
     # the rotation is one header, included and not copied; the file starts from the small libraries' prelude
     text = open(os.path.join(ROOT, "gradient-quantization_amd", "csrc", "eden.hip")).read()
-    assert '#include "hadamard.hpp"' in text and '#include "gq_lib_prelude.hpp"' in text
+    assert '#include "hadamard.hpp"' in text and '#include "gq_lib_prelude.hpp"' in text and '#include "rotq_kernels.hpp"' in text
+    assert "__global__" not in text
     body = text.split("#include", 1)[1]
     assert "ds_swizzle" not in body and "update_dpp" not in body and "__shared__" not in body and "__syncthreads" not in body
 

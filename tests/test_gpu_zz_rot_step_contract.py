@@ -31,7 +31,8 @@ GARBAGE = (0xDEADBEEFDEADBEEF, 0x0123456789ABCDEF, M64, 0)
 SIZES = [1, 255, 256, 257, 4095, 4096, 4097, 8193]
 DENSE = [300]
 PAIRS = [(1, 0), (1, 1), (1, 2), (0, 5), (M64, 3), (1, 2 ** 62), (1, M64)]
-KINDS = [("drive", "unbiased"), ("drive", "mse"), ("eden2", "unbiased"), ("eden3", "unbiased"), ("eden4", "unbiased")]
+KINDS = [("drive", "unbiased"), ("drive", "mse"), ("eden2", "unbiased"), ("eden2", "mse"), ("eden3", "unbiased"), ("eden3", "mse"),
+         ("eden4", "unbiased"), ("eden4", "mse")]
 IDS = ["%s-%s" % k for k in KINDS]
 
 

@@ -134,6 +134,8 @@ def main():
     ap.add_argument("--user-rotation", default=None, choices=["own"],
                     help="the rot_user rows alone (tools/rot_user_time.py): the *_streams launches against the stepped and fixed ones of "
                          "--parent-lib, here ONE older libgq_eden.so")
+    ap.add_argument("--scale", default=None, choices=["mse"], help="with --rotation step: the compress launch under the mse scale")
+    ap.add_argument("--ef", action="store_true", help="with --rotation step: the compress launch with error feedback")
     a = ap.parse_args()
     if a.user_rotation == "own":
         import rot_user_time
@@ -143,7 +145,7 @@ def main():
         import rot_step_time
         if len(a.parent_lib) > 1:
             ap.error("--rotation step takes one --parent-lib, an older libgq_eden.so")
-        return rot_step_time.main("eden", a.out, os.path.abspath(a.parent_lib[0]) if a.parent_lib else None)
+        return rot_step_time.main("eden", a.out, os.path.abspath(a.parent_lib[0]) if a.parent_lib else None, a.scale, a.ef)
     parent = {"mxr": None, "drive": None}
     for p in a.parent_lib:
         kind = [k for k in parent if k in os.path.basename(p)]

@@ -1,14 +1,19 @@
-"""The compiled code of libgq_mx.so's and libgq_mxr.so's kernels, this tree against another checkout (the parent commit), kernel
-by kernel.
+"""The compiled code of a family of libraries' kernels, this tree against another checkout (the parent commit), kernel by kernel.
 
-    python tools/mx_isa_compare.py --parent DIR [--out profiles/mx_refactor_isa.txt]
+    python tools/mx_isa_compare.py --parent DIR [--family mx] [--family rotq] [--out profiles/<family>_refactor_isa.txt]
 
-DIR is a checkout of the commit to compare with (`git worktree add DIR HEAD~1`, or `git archive` unpacked).  Both trees' csrc/mx.hip
-and csrc/mxr.hip are compiled with build.py's flags + --save-temps into scratch directories (no GPU needed); the 2 x 56 kernels are
-matched by library, kind (compress / decode), format, draw mode, error feedback and tensor type, read off the template arguments
-in their mangled names.  Per kernel: the instruction count (the .s text of the function, labels, directives and comments
-dropped), the registers and the scratch / LDS bytes of the kernel's metadata, both sides, and whether the instruction text is the
-same once the labels are renumbered.  Whole texts and numbers are compared; no instruction is looked for.
+DIR is a checkout of the commit to compare with (`git worktree add DIR HEAD~1`, or `git archive` unpacked).  A family (FAMILIES
+below) is a list of csrc files, the number of kernels each holds and a key function:
+    mx    mx.hip and mxr.hip, 2 x 56 kernels (csrc/mx_kernels.hpp), matched by library, kind (compress / decode), format, draw
+          mode, error feedback and tensor type;
+    rotq  drive.hip and eden.hip, 15 + 45 kernels (csrc/rotq_kernels.hpp), matched by library, kind (compress / decode /
+          decode-streams), bits, scale mode, error feedback and rotation kind (Signs / Stepped / Streamed).
+Both trees' files are compiled with build.py's flags + --save-temps into scratch directories (no GPU needed); a kernel's key is
+read off the template arguments in its mangled name, whatever the function itself is called.  Per kernel: the instruction count
+(the .s text of the function, labels, directives and comments dropped), the registers and the scratch / LDS bytes of the kernel's
+metadata, both sides, and whether the instruction text is the same once the labels are renumbered.  Whole texts and numbers are
+compared; no instruction is looked for.  With one --family and no --out the result goes to profiles/<family>_refactor_isa.txt;
+several families (a change to a header both share) go into the first one's file.
 Exit status 1 if a kernel has scratch or LDS, or if its VGPR count falls into a lower waves-per-SIMD class than the other tree's.
 """
 import argparse
@@ -21,10 +26,10 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "gradient-quantization_amd"
-FILES = ("mx.hip", "mxr.hip")
 FMT = {0: "fp4", 1: "fp8", 0x23: "fp6_e2m3", 0x32: "fp6_e3m2"}
 MODE = {0: "off", 1: "given", 2: "device"}
 TT = {0: "f32", 1: "bf16"}
+SCALE = {0: "unbiased", 1: "mse"}
 META = (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
 
@@ -40,10 +45,16 @@ def build_asm(root, name):
     return open(os.path.join(d, [f for f in os.listdir(d) if f.endswith("gfx950.s")][0])).read()
 
 
-def key_of(symbol):
-    """(kind, format, mode, ef, tensor type) from the integer template arguments of a kernel's mangled name."""
+def template_args(symbol):
+    """The template-argument part of a kernel's mangled name ('' if it is no template) and the integers among the arguments."""
+    part = symbol[:symbol.index("EEv")] + "E" if "EEv" in symbol else ""
+    return part, [int(v) for v in re.findall(r"L[ib](\d+)E", part)]
+
+
+def mx_key(symbol):
+    """(kind, format, mode, ef, tensor type) of a kernel of mx.hip / mxr.hip."""
     kind = "compress" if "compress_kernel" in symbol else "decode"
-    args = [int(v) for v in re.findall(r"L[ib](\d+)E", symbol[:symbol.index("EEv")] + "E")]
+    args = template_args(symbol)[1]
     if kind == "compress":
         fmt, mode, ef, tt = args
         return kind, FMT[fmt], MODE[mode], "ef" if ef else "-", TT[tt]
@@ -51,7 +62,26 @@ def key_of(symbol):
     return kind, FMT[fmt], "-", "-", TT[tt]
 
 
-def kernels(txt):
+def rotq_key(symbol):
+    """(kind, bits, scale mode, ef, rotation kind) of a kernel of drive.hip / eden.hip: the integers are [bits,] scale, ef of a
+    compress and [bits] of a decode -- one bit where no width is an argument -- and the rotation is the last argument's type."""
+    kind = "compress" if "compress_kernel" in symbol else "decode-streams" if "decode_streams_kernel" in symbol else "decode"
+    part, args = template_args(symbol)
+    rot = re.findall(r"\d(Signs|Stepped|Streamed)E", part)
+    if kind == "compress":
+        scale, ef = args[-2:]
+        return kind, "b%d" % (args[0] if len(args) == 3 else 1), SCALE[scale], "ef" if ef else "-", rot[0]
+    return kind, "b%d" % (args[0] if args else 1), "-", "-", rot[0] if kind == "decode" else "-"
+
+
+# family -> ((csrc file, kernels in it), ...), the key function, the key's column names
+FAMILIES = {
+    "mx": ((("mx.hip", 56), ("mxr.hip", 56)), mx_key, "kind format mode ef type", "%-8s %-8s %-6s %-2s %-4s"),
+    "rotq": ((("drive.hip", 15), ("eden.hip", 45)), rotq_key, "kind bits scale ef rotation", "%-14s %-2s %-8s %-2s %-8s"),
+}
+
+
+def kernels(txt, key_of):
     """key -> (instruction lines with the labels renumbered, the kernel's metadata numbers)."""
     out = {}
     for m in re.finditer(r"^(_Z\w+_kernel\w+):", txt, re.M):
@@ -71,6 +101,7 @@ def kernels(txt):
         entry = txt[start:end if end > 0 else len(txt)]
         meta = {f: int(re.search(r"^\s+%s:\s+(\d+)" % re.escape(f), entry, re.M).group(1)) for f in META}
         meta["instructions"] = sum(1 for ln in text if not ln.endswith(":"))
+        assert key_of(sym) not in out, "two kernels with the key %s" % (key_of(sym),)
         out[key_of(sym)] = (text, meta)
     return out
 
@@ -83,32 +114,38 @@ def waves_per_simd(vgprs):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", required=True, help="a checkout of the commit to compare with")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mx_refactor_isa.txt"))
+    ap.add_argument("--family", action="append", choices=sorted(FAMILIES), help="default: mx")
+    ap.add_argument("--out", help="default: profiles/<the first family>_refactor_isa.txt")
     a = ap.parse_args()
-    rows, bad, differ = [], [], 0
-    for name in FILES:
-        old, new = kernels(build_asm(os.path.abspath(a.parent), name)), kernels(build_asm(ROOT, name))
-        assert sorted(old) == sorted(new) and len(new) == 56, "%s: %d kernels against %d" % (name, len(old), len(new))
-        for key in sorted(new):
-            (t0, m0), (t1, m1) = old[key], new[key]
-            same = t0 == t1
-            differ += not same
-            rows.append("%-4s %-8s %-8s %-6s %-2s %-4s  %5d %5d  %3d %3d  %3d %3d  %d %d  %d %d  %s"
-                        % ((name[:-4],) + key + (m0["instructions"], m1["instructions"], m0[".vgpr_count"], m1[".vgpr_count"],
-                                                 m0[".sgpr_count"], m1[".sgpr_count"], m0[".private_segment_fixed_size"],
-                                                 m1[".private_segment_fixed_size"], m0[".group_segment_fixed_size"],
-                                                 m1[".group_segment_fixed_size"], "identical" if same else "DIFFERS")))
-            if m1[".private_segment_fixed_size"] or m1[".group_segment_fixed_size"]:
-                bad.append("%s %s: scratch or LDS" % (name, key))
-            if waves_per_simd(m1[".vgpr_count"]) < waves_per_simd(m0[".vgpr_count"]):
-                bad.append("%s %s: %d VGPRs against %d: fewer waves per SIMD" % (name, key, m1[".vgpr_count"], m0[".vgpr_count"]))
-    head = ["# tools/mx_isa_compare.py: the kernels of mx.hip and mxr.hip, the parent commit against this tree (gfx950, build.py's flags).",
-            "# columns: library kind format mode ef type | instructions parent new | VGPRs parent new | SGPRs parent new |",
-            "#          scratch bytes parent new | LDS bytes parent new | instruction text with labels renumbered",
-            "# %d kernels, %d with other instruction text than the parent's" % (len(rows), differ)]
-    with open(a.out, "w") as f:
-        f.write("\n".join(head + rows) + "\n")
-    print("\n".join(head[3:] + bad))
+    families = a.family or ["mx"]
+    out = a.out or os.path.join(ROOT, "profiles", families[0] + "_refactor_isa.txt")
+    text, bad, total, differ = [], [], 0, 0
+    for fam in families:
+        files, key_of, columns, fmt = FAMILIES[fam]
+        text += ["# tools/mx_isa_compare.py: the kernels of %s, the parent commit against this tree (gfx950, build.py's flags)."
+                 % " and ".join(name for name, _ in files),
+                 "# columns: library %s | instructions parent new | VGPRs parent new | SGPRs parent new |" % columns,
+                 "#          scratch bytes parent new | LDS bytes parent new | instruction text with labels renumbered"]
+        for name, count in files:
+            old, new = kernels(build_asm(os.path.abspath(a.parent), name), key_of), kernels(build_asm(ROOT, name), key_of)
+            assert sorted(old) == sorted(new) and len(new) == count, "%s: %d kernels against %d, %d expected" % (name, len(old), len(new), count)
+            for key in sorted(new):
+                (t0, m0), (t1, m1) = old[key], new[key]
+                same = t0 == t1
+                total, differ = total + 1, differ + (not same)
+                text.append(("%-5s " + fmt + "  %5d %5d  %3d %3d  %3d %3d  %d %d  %d %d  %s")
+                            % ((name[:-4],) + key + (m0["instructions"], m1["instructions"], m0[".vgpr_count"], m1[".vgpr_count"],
+                                                     m0[".sgpr_count"], m1[".sgpr_count"], m0[".private_segment_fixed_size"],
+                                                     m1[".private_segment_fixed_size"], m0[".group_segment_fixed_size"],
+                                                     m1[".group_segment_fixed_size"], "identical" if same else "DIFFERS")))
+                if m1[".private_segment_fixed_size"] or m1[".group_segment_fixed_size"]:
+                    bad.append("%s %s: scratch or LDS" % (name, key))
+                if waves_per_simd(m1[".vgpr_count"]) < waves_per_simd(m0[".vgpr_count"]):
+                    bad.append("%s %s: %d VGPRs against %d: fewer waves per SIMD" % (name, key, m1[".vgpr_count"], m0[".vgpr_count"]))
+    tail = "# %d kernels, %d with other instruction text than the parent's" % (total, differ)
+    with open(out, "w") as f:
+        f.write("\n".join(text + [tail]) + "\n")
+    print("\n".join([tail] + bad))
     return 1 if bad else 0
 
 

@@ -11,6 +11,9 @@ Rows (case rot_step, one JSON line each; the file's other rows stay):
   resnet50_step   PSQuantizer record + apply over the ResNet-50 parameter list, one user, graph replay, gradients at fixed addresses:
                   rotation 'step' next to 'fixed', alternated, three rounds; the entry-point calls of one EAGER step of either
                   (launches_per_eager_step: the list has identity tensors, so gq_mean_rows carries the step move and the two agree).
+--scale mse / --ef (with --rotation step): the compress launch alone under EDEN's mse scale and / or with error feedback in the
+launch (ef_scale 0, so the tensor stays as it is from launch to launch) -- the instantiations the rows above do not reach; case
+rot_step_<scale>[_ef], single_25m rows only.
 Times: tools/mx_time.py's method."""
 import ctypes
 import json
@@ -56,12 +59,15 @@ class parent_library(object):
         self.batch_cls.LIBRARY = self.saved
 
 
-def single_rows(kind, dev, parent_lib, n=25_000_000):
+def single_rows(kind, dev, parent_lib, n=25_000_000, scale=None, ef=False, case="rot_step"):
     torch.manual_seed(1)
     t = torch.randn(n, device=dev)
     pair = torch.tensor([[1, 3]], dtype=torch.int64).to(dev)
+    enc = {"errs": [torch.zeros(n, device=dev)], "ef_scale": 0.0} if ef else {}
     rows = []
     for name, (comp_cls, codec_cls, group_cls, batch_cls, kw) in variants(kind).items():
+        if scale and kind == "eden":
+            kw = dict(kw, eden_scale=scale)
         cd = codec_cls(comp_cls(n, (n,), _args(**kw)), n, (n,))
         groups = {}
 
@@ -69,7 +75,7 @@ def single_rows(kind, dev, parent_lib, n=25_000_000):
             g = group_cls([cd], [0], [0], dev, 1, cd.nbytes)
             g.rotation = rotation
             wire = torch.zeros((8, cd.nbytes), dtype=torch.uint8, device=dev)
-            assert g.encode([t], wire[0], 0, 0)
+            assert g.encode([t], wire[0], 0, 0, **enc)
             for r in range(1, 8):
                 wire[r].copy_(wire[0])
             groups[tag] = (g, wire)
@@ -84,16 +90,16 @@ def single_rows(kind, dev, parent_lib, n=25_000_000):
         for rnd in range(3):
             for tag, (g, w) in groups.items():
                 kwd = {"rotation": g.rotation} if g.rotation is not None else {}
-                times.setdefault(tag + "_compress", []).append(graphed(lambda: g.encode([t], w[0], 0, 0)))
-                for R in (1, 8):
+                times.setdefault(tag + "_compress", []).append(graphed(lambda: g.encode([t], w[0], 0, 0, **enc)))
+                for R in (1, 8) if case == "rot_step" else ():      # (the decode-mean has neither a scale mode nor error feedback)
                     times.setdefault("%s_decode_mean_R%d" % (tag, R), []).append(graphed(lambda: g._batch.decode(w[:R], R, out, **kwd)))
-        row = {"case": "rot_step", "row": "single_25m", "path": name, "elements": n, "bar": BAR, "parent_lib": bool(parent_lib)}
+        row = {"case": case, "row": "single_25m", "path": name, "elements": n, "bar": BAR, "parent_lib": bool(parent_lib)}
         for key, ts in times.items():
             row[key + "_us_rounds"] = [round(x, 2) for x in ts]
             row[key + "_us"] = round(min(ts), 2)
         yard = "parent_fixed" if parent_lib else "fixed"
         row["missed"] = []
-        for launch in ("compress", "decode_mean_R1", "decode_mean_R8"):
+        for launch in ("compress", "decode_mean_R1", "decode_mean_R8") if case == "rot_step" else ("compress",):
             field = "step_%s_over_%s" % (launch, yard)
             row[field] = round(row["step_%s_us" % launch] / row["%s_%s_us" % (yard, launch)], 3)
             if row[field] > BAR:
@@ -150,6 +156,9 @@ def resnet50_rows(kind, dev):
     return [row]
 
 
-def main(kind, out, parent_lib):
+def main(kind, out, parent_lib, scale=None, ef=False):
     dev = torch.device("cuda:0")
+    if scale or ef:
+        case = "rot_step" + ("_" + scale if scale else "") + ("_ef" if ef else "")
+        return write_rows(out, single_rows(kind, dev, parent_lib, scale=scale, ef=ef, case=case), replace_case=case)
     write_rows(out, single_rows(kind, dev, parent_lib) + resnet50_rows(kind, dev), replace_case="rot_step")
