@@ -19,15 +19,15 @@ SOURCES = ["gq_common.hip", "gq_api.hip", "hsq_encode.hip", "hsq_encode_pf.hip",
 # entry points stay as they are; each is one file that starts from csrc/gq_lib_prelude.hpp.
 LIBS = {
     LIB: SOURCES,
-    os.path.join(HERE, "libgq_topk.so"): ["topk.hip"],            # top-k sparsification
+    os.path.join(HERE, "libgq_topk.so"): ["topk.hip"],            # top-k sparsification; with thr.hip, stc.hip and maurey.hip over csrc/sparse_kernels.hpp (the key, the radix select, the compaction, the sparse decode-mean: each library compiles its own copy)
     os.path.join(HERE, "libgq_dgc.so"): ["dgc.hip"],              # momentum correction and masking around the top-k select
     os.path.join(HERE, "libgq_sign.so"): ["sign.hip"],            # signSGD on a 2-bit wire
     os.path.join(HERE, "libgq_mx.so"): ["mx.hip"],                # block-scaled small floats (MXFP4 / MXFP6 / MXFP8): one compress launch, one decode-mean launch
     os.path.join(HERE, "libgq_mxr.so"): ["mxr.hip"],              # the same behind a randomized 256-point Hadamard rotation: both instantiate the kernels and the host path of csrc/mx_kernels.hpp (formats and element types: csrc/mx_common.hpp)
     os.path.join(HERE, "libgq_drive.so"): ["drive.hip"],          # the rotated 1-bit compressor (DRIVE): signs of the rotated block and one f32 scale, on mxr.hip's rotation (csrc/hadamard.hpp)
     os.path.join(HERE, "libgq_eden.so"): ["eden.hip"],            # the rotated 2- / 3- / 4-bit compressor (EDEN): Lloyd-Max codes of the rotated block and one f32 scale, on the same rotation
-    os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select
-    os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select, one magnitude per tensor, a 16-bit word per kept element
+    os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select (top-k's compaction and decode-mean: csrc/sparse_kernels.hpp)
+    os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select (the same kernels: csrc/sparse_kernels.hpp), one magnitude per tensor, a 16-bit word per kept element
     os.path.join(HERE, "libgq_psgd.so"): ["psgd.hip"],            # low-rank compression (PowerSGD, rank 1 / 2 / 4): project, orthogonalise, back-project, fold, residual; the decode-mean of the factors
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],    # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean

@@ -23,13 +23,20 @@
 #include "gq_common.hpp"
 #include "gq_lib_prelude.hpp"
 #include "gq_maurey.h"
+#include "sparse_kernels.hpp"
 
 #define GQM_API extern "C" __attribute__((visibility("default")))
 
 namespace gqm {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
+using gql::copy_dense;
+using gql::err_buf;
+using gql::fail;
+using gqsp::block_exclusive_scan;
+using gqsp::load_w;
+using gqsp::THREADS;
+using gqsp::WAVES;
+
 constexpr int CHUNK = GQ_MAUREY_CHUNK;
 constexpr int PER_THREAD = CHUNK / THREADS;           // 16 consecutive elements
 constexpr int HEADER = GQ_MAUREY_HEADER_BYTES;
@@ -37,23 +44,8 @@ constexpr int PADDED = CHUNK + CHUNK / PER_THREAD;    // an LDS array of one wor
 static_assert(PER_THREAD == 16 && THREADS == 256, "the order of additions (gq_maurey.h) is 16 x 16 x 16");
 static_assert(sizeof(gq_maurey_batch) == 96, "gq_maurey_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
-using gql::copy_dense;
-using gql::err_buf;
-using gql::fail;
-
 // element e of an item in an LDS array: a thread's 16 words are contiguous, the pad spreads the threads over the banks
 __device__ __forceinline__ int phys(int e) { return e + (e >> 4); }
-
-// the value the compress works on: v, or v + ef_scale * err (as load_w of topk.hip; -ffp-contract=off keeps the two roundings)
-template <bool EF>
-__device__ __forceinline__ float load_w(const float *__restrict__ v, const float *__restrict__ err, int64_t i, float ef_scale) {
-    float w = v[i];
-    if (EF && err) {
-        const float p = ef_scale * err[i];
-        w = w + p;
-    }
-    return w;
-}
 
 // this thread's 16 elements of the item that starts at `base` (elements past `end` read as +0)
 template <bool EF>
@@ -128,28 +120,6 @@ __device__ __forceinline__ double draw_t(float u, double T) {
 
 __device__ __forceinline__ float draw_u(int random_mode, const float *__restrict__ r, uint64_t seed, int64_t d) {
     return random_mode == GQ_RANDOM_GIVEN ? r[d] : gq::uniform01(seed, (uint64_t)d);
-}
-
-// exclusive prefix sum over the workgroup in thread order (as in topk.hip); lds: WAVES words, free on entry
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t *lds, uint32_t *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < WAVES; ++j) {
-        const uint32_t t = lds[j];
-        if (j < w) before += t;
-        tot += t;
-    }
-    *total = tot;
-    return before + incl - x;
 }
 
 template <bool EF>

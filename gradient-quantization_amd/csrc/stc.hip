@@ -1,8 +1,7 @@
 // Sparse ternary compression on a 16-bit wire, multi-tensor (segment table) form -- libgq_stc.so (include/gq_stc.h).
 //
-// The kept set is top-k's (csrc/topk.hip: the radix select on the 31-bit key, three hist / pick pairs, then count, scan, write;
-// libgq_topk.so's kernels are held to their instruction text, so the select is repeated here, not lifted out of that file).
-// What is new sits in the last three launches:
+// The kept set is top-k's (csrc/topk.hip is the map: the radix select on the 31-bit key, three hist / pick pairs -- the kernels of
+// csrc/sparse_kernels.hpp, which both libraries instantiate -- then count, scan, write).  What is new sits in the last three launches:
 //   count    also the item's float64 sum s[t] of the |w| with key > T: slot j = 256 s + thread of the item is step s of that
 //            thread, so the header's halvings 2048 ... 256 add a thread's own sixteen values, 128 and 64 cross the waves through
 //            LDS and 32 ... 1 are lane shifts of wave 0 -- a fixed tree, no atomics.
@@ -18,66 +17,30 @@
 
 #include "gq_lib_prelude.hpp"
 #include "gq_stc.h"
+#include "sparse_kernels.hpp"
 
 #define GQS_API extern "C" __attribute__((visibility("default")))
 
 namespace gqs {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
-constexpr int CHUNK = GQ_STC_CHUNK;
-constexpr int PER_THREAD = CHUNK / THREADS;
-constexpr int BINS = GQ_STC_HIST_BINS;
-constexpr uint32_t NO_KEY = 0x80000000u;      // above every key: the threshold of a tensor with k == 0 (nothing kept)
-static_assert(CHUNK == 4096 && THREADS == 256, "the sum tree of include/gq_stc.h is written out for 16 steps of 256 threads");
-static_assert(sizeof(gq_stc_batch) == 80, "gq_stc_batch: the layout the ctypes binding declares (gq_amd/native.py)");
-
 using gql::copy_dense;
 using gql::err_buf;
 using gql::fail;
+using gqsp::block_exclusive_scan;
+using gqsp::kept_before;
+using gqsp::key_of;
+using gqsp::load_w;
+using gqsp::NO_KEY;
+using gqsp::THREADS;
+using gqsp::WAVES;
 
-// pass p of the select: the key bits [shift, shift + nb)
-__host__ __device__ constexpr int pass_shift(int p) { return p == 0 ? 20 : (p == 1 ? 9 : 0); }
-__host__ __device__ constexpr int pass_bits(int p) { return p == 2 ? 9 : 11; }
-
-__device__ __forceinline__ uint32_t key_of(float w) {
-    const uint32_t a = __float_as_uint(w) & 0x7fffffffu;
-    return a > 0x7f800000u ? 0x7fffffffu : a;
-}
-
-// the value the compress works on: v, or v + ef_scale * err (-ffp-contract=off keeps the two roundings)
-template <bool EF>
-__device__ __forceinline__ float load_w(const float *__restrict__ v, const float *__restrict__ err, int64_t i, float ef_scale) {
-    float w = v[i];
-    if (EF && err) {
-        const float p = ef_scale * err[i];
-        w = w + p;
-    }
-    return w;
-}
-
-// exclusive prefix sum over the workgroup in thread order; *total = the workgroup's sum.  lds: WAVES words, free on entry
-// (the caller separates two uses of the same words by a barrier).
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t *lds, uint32_t *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < WAVES; ++j) {
-        const uint32_t t = lds[j];
-        if (j < w) before += t;
-        tot += t;
-    }
-    *total = tot;
-    return before + incl - x;
-}
+struct Sizes {      // what the select's kernels (csrc/sparse_kernels.hpp) are instantiated over
+    static constexpr int CHUNK = GQ_STC_CHUNK, BINS = GQ_STC_HIST_BINS;
+};
+constexpr int CHUNK = Sizes::CHUNK;
+constexpr int PER_THREAD = CHUNK / THREADS;
+static_assert(CHUNK == 4096 && THREADS == 256, "the sum tree of include/gq_stc.h is written out for 16 steps of 256 threads");
+static_assert(sizeof(gq_stc_batch) == 80, "gq_stc_batch: the layout the ctypes binding declares (gq_amd/native.py)");
 
 // halve(x, 256) of include/gq_stc.h over the threads' values: x[t] + x[t + h] for h = 128, 64 (LDS), 32 ... 1 (lane shifts).
 // The result is thread 0's.  lds: THREADS doubles, free on entry.
@@ -92,88 +55,6 @@ __device__ __forceinline__ double block_halve(double x, double *lds) {
         for (int d = 32; d >= 1; d >>= 1) r = r + __shfl_down(r, d, 64);
     }
     return r;
-}
-
-template <bool EF>
-__global__ __launch_bounds__(THREADS) void stc_hist_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
-                                                           const int32_t *__restrict__ state, uint32_t *__restrict__ hist, int pass,
-                                                           float ef_scale) {
-    __shared__ uint32_t h[BINS];
-    const int64_t item = blockIdx.x;
-    const int seg = item_seg[item];
-    const int64_t *rec = seg_table + 8 * (int64_t)seg;
-    const int64_t n = rec[1], k = rec[4];
-    if (k == 0) return;
-    const int shift = pass_shift(pass), nb = pass_bits(pass), hi = shift + nb;
-    const uint32_t nbins = 1u << nb;
-    const uint32_t prefix = pass == 0 ? 0u : (uint32_t)state[4 * seg];
-    for (uint32_t b = threadIdx.x; b < nbins; b += THREADS) h[b] = 0u;
-    __syncthreads();
-    const float *v = reinterpret_cast<const float *>(rec[0]);
-    const float *err = EF ? reinterpret_cast<const float *>(rec[7]) : nullptr;
-    const int64_t base = (item - rec[2]) * CHUNK;
-    const int64_t end = base + CHUNK < n ? base + CHUNK : n;
-    for (int64_t i = base + threadIdx.x; i < end; i += THREADS) {
-        const uint32_t key = key_of(load_w<EF>(v, err, i, ef_scale));
-        if (pass == 0 || (key >> hi) == (prefix >> hi)) atomicAdd(&h[(key >> shift) & (nbins - 1u)], 1u);
-    }
-    __syncthreads();
-    uint32_t *g = hist + (int64_t)seg * BINS;
-    for (uint32_t b = threadIdx.x; b < nbins; b += THREADS) {
-        const uint32_t c = h[b];
-        if (c) atomicAdd(&g[b], c);
-    }
-}
-
-// one workgroup per tensor: state[0] = prefix (after pass 2: the threshold key T), state[1] = the rank, among the keys that
-// share the prefix, of the k-th largest one (after pass 2: how many keys == T are kept)
-__global__ __launch_bounds__(THREADS) void stc_pick_kernel(const int64_t *__restrict__ seg_table, int32_t *__restrict__ state,
-                                                           uint32_t *__restrict__ hist, int pass) {
-    __shared__ uint32_t lds[WAVES];
-    const int seg = blockIdx.x;
-    const int64_t k = seg_table[8 * (int64_t)seg + 4];
-    int32_t *st = state + 4 * seg;
-    if (k == 0) {
-        if (pass == 2 && threadIdx.x == 0) {
-            st[0] = (int32_t)NO_KEY;
-            st[1] = 0;
-        }
-        return;
-    }
-    const int shift = pass_shift(pass), nb = pass_bits(pass);
-    const uint32_t nbins = 1u << nb;
-    const int per = (int)(nbins / THREADS);       // 8 or 2 bins per thread, thread 0 the highest ones
-    const uint32_t kr = pass == 0 ? (uint32_t)k : (uint32_t)st[1];
-    const uint32_t prefix = pass == 0 ? 0u : (uint32_t)st[0];
-    uint32_t *g = hist + (int64_t)seg * BINS;
-    const uint32_t top = nbins - (uint32_t)per * threadIdx.x;
-    uint32_t c[8];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        c[j] = 0;
-        if (j < per) {
-            c[j] = g[top - 1 - j];
-            g[top - 1 - j] = 0u;      // the only reader of this bin: the histogram is clean for the next pass / step
-            sum += c[j];
-        }
-    }
-    uint32_t total;
-    const uint32_t before = block_exclusive_scan(sum, lds, &total);   // (the barrier inside orders the reads of st above)
-    if (before < kr && kr <= before + sum) {
-        uint32_t cum = before;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j < per) {
-                if (kr <= cum + c[j]) {
-                    st[0] = (int32_t)(prefix | ((top - 1 - (uint32_t)j) << shift));
-                    st[1] = (int32_t)(kr - cum);
-                    break;
-                }
-                cum += c[j];
-            }
-        }
-    }
 }
 
 // per item: #(key > T), #(key == T) and s[t], the float64 sum of the |w| with key > T in the header's order
@@ -230,31 +111,13 @@ __global__ __launch_bounds__(THREADS) void stc_count_kernel(const int64_t *__res
 // and mu into state[2]
 __global__ __launch_bounds__(THREADS) void stc_scan_kernel(const int64_t *__restrict__ seg_table, int32_t *__restrict__ state,
                                                            int32_t *__restrict__ counts, double *sums) {
-    __shared__ uint32_t lds[2][WAVES];
     __shared__ double tree[THREADS];
     const int seg = blockIdx.x;
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
     const int64_t n = rec[1], first = rec[2], k = rec[4];
     const int64_t nit = (n + CHUNK - 1) / CHUNK;
-    uint32_t cg = 0, ce = 0;
-    for (int64_t b0 = 0; b0 < nit; b0 += THREADS) {
-        const int64_t it = b0 + threadIdx.x;
-        uint32_t g = 0, e = 0;
-        if (it < nit) {
-            g = (uint32_t)counts[2 * (first + it)];
-            e = (uint32_t)counts[2 * (first + it) + 1];
-        }
-        uint32_t tg, te;
-        const uint32_t bg = block_exclusive_scan(g, lds[0], &tg);
-        const uint32_t be = block_exclusive_scan(e, lds[1], &te);
-        if (it < nit) {
-            counts[2 * (first + it)] = (int32_t)(cg + bg);
-            counts[2 * (first + it) + 1] = (int32_t)(ce + be);
-        }
-        cg += tg;
-        ce += te;
-        __syncthreads();      // (the next round rewrites lds)
-    }
+    uint32_t total[2];
+    gqsp::scan_item_counts<2, 0>(counts, first, nit, total);
     // halve(s, P): slot j and slot j + h belong to one thread while h >= 256; a slot past the tensor's items is +0.0, and
     // x + +0.0 is x for every x a sum of magnitudes can be
     double *s = sums + first;
@@ -280,7 +143,6 @@ __global__ __launch_bounds__(THREADS) void stc_write_kernel(const int64_t *__res
                                                             uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
                                                             const int64_t *__restrict__ dense_table, int ndense) {
     copy_dense<THREADS>(dense_table, ndense, wire);
-    __shared__ uint32_t lds[2][2][WAVES];      // [step parity][> T, == T][wave]
     __shared__ uint16_t words[CHUNK];          // the item's words at their rank inside the item
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
@@ -290,7 +152,7 @@ __global__ __launch_bounds__(THREADS) void stc_write_kernel(const int64_t *__res
     const uint32_t T = (uint32_t)state[4 * seg], need = (uint32_t)state[4 * seg + 1];
     const uint32_t mu = (uint32_t)state[4 * seg + 2] & 0x7fffffffu;
     uint32_t gt_before = (uint32_t)counts[2 * item], eq_before = (uint32_t)counts[2 * item + 1];
-    const uint32_t start = gt_before + (eq_before < need ? eq_before : need);
+    const uint32_t start = kept_before(gt_before, eq_before, need);
     float *v = reinterpret_cast<float *>(rec[0]);
     float *err = EF ? reinterpret_cast<float *>(rec[7]) : nullptr;
     uint32_t *head = reinterpret_cast<uint32_t *>(wire + rec[3]);
@@ -298,8 +160,6 @@ __global__ __launch_bounds__(THREADS) void stc_write_kernel(const int64_t *__res
     float *o = out ? out + rec[5] : nullptr;
     const int64_t base = t * CHUNK;
     const int64_t end = base + CHUNK < n ? base + CHUNK : n;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     if (threadIdx.x == 0) head[4 + t] = start;
     if (t == 0) {
         if (threadIdx.x == 0) {
@@ -323,45 +183,20 @@ __global__ __launch_bounds__(THREADS) void stc_write_kernel(const int64_t *__res
         }
         const bool is_gt = valid && key > T;
         const bool is_eq = valid && key == T;
-        const uint64_t mg = __ballot(is_gt), me = __ballot(is_eq);
-        if (lane == 0) {
-            lds[s & 1][0][wv] = (uint32_t)__popcll(mg);
-            lds[s & 1][1][wv] = (uint32_t)__popcll(me);
-        }
-        __syncthreads();      // (parity: a wave still reading step s's words is not overwritten before step s + 2)
-        uint32_t pg = 0, pe = 0, tg = 0, te = 0;
-#pragma unroll
-        for (int j = 0; j < WAVES; ++j) {
-            const uint32_t a = lds[s & 1][0][j], b = lds[s & 1][1][j];
-            if (j < wv) {
-                pg += a;
-                pe += b;
-            }
-            tg += a;
-            te += b;
-        }
-        const uint32_t gb = gt_before + pg + (uint32_t)__popcll(mg & below);
-        const uint32_t eb = eq_before + pe + (uint32_t)__popcll(me & below);
-        const bool kept = is_gt || (is_eq && eb < need);
+        const gqsp::Rank r = gqsp::rank_step<true>(s, is_gt, is_eq, gt_before, eq_before);
+        const bool kept = r.kept(is_gt, is_eq, need);
         const uint32_t sign = __float_as_uint(w) & 0x80000000u;
         if (kept) {
-            const uint32_t local = gb + (eb < need ? eb : need) - start;
+            const uint32_t local = r.pos(need) - start;
             if (local < (uint32_t)CHUNK) words[local] = (uint16_t)((uint32_t)(s * THREADS + threadIdx.x) | (sign >> 16));
         }
-        if (valid) {
-            const float dec = __uint_as_float(kept ? (mu | sign) : 0u);
-            if (o) o[i] = dec;
-            if (EF && err) {
-                v[i] = w;
-                err[i] = w - dec;
-            }
-        }
-        gt_before += tg;
-        eq_before += te;
+        if (valid) gqsp::store_decoded<EF>(v, err, o, i, w, __uint_as_float(kept ? (mu | sign) : 0u));
+        gt_before += r.tg;
+        eq_before += r.te;
     }
     __syncthreads();
     // the run [lo, hi) of the tensor's words, two words a store where both are the item's
-    const uint32_t stop = gt_before + (eq_before < need ? eq_before : need);
+    const uint32_t stop = kept_before(gt_before, eq_before, need);
     const uint32_t lo = start < (uint64_t)k ? start : (uint32_t)k, hi = stop < (uint64_t)k ? stop : (uint32_t)k;
     for (uint32_t d = (lo >> 1) + threadIdx.x; d < (hi + 1) >> 1; d += THREADS) {
         const uint32_t g0 = 2 * d, g1 = g0 + 1;
@@ -391,8 +226,7 @@ __global__ __launch_bounds__(THREADS) void stc_decode_kernel(const int64_t *__re
     const int64_t base = t * CHUNK;
     const int64_t end = base + CHUNK < n ? base + CHUNK : n;
     const uint32_t len = (uint32_t)(end - base);
-    for (int j = threadIdx.x; j < CHUNK; j += THREADS) acc[j] = 0.0f;
-    __syncthreads();
+    gqsp::decode_clear<CHUNK>(acc);
     const bool direct = plain && R == 1;
     for (int r = 0; r < R; ++r) {
         const uint8_t *p = gathered + (int64_t)r * stride + off;
@@ -409,15 +243,12 @@ __global__ __launch_bounds__(THREADS) void stc_decode_kernel(const int64_t *__re
         }
         __syncthreads();      // payloads in order: r + 1 adds to what r left
     }
-    const float fR = (float)R;
-    for (uint32_t j = threadIdx.x; j < len; j += THREADS) o[base + j] = direct ? acc[j] : acc[j] / fR;
+    gqsp::decode_store_mean(acc, o, base, len, R, direct);
 }
 
 static int check_batch(const gq_stc_batch *b, const char *what, bool compress) {
-    if (!b || b->struct_bytes != sizeof(gq_stc_batch)) return fail(GQ_ERR_INVALID_ARG, "%s: descriptor missing or of another size", what);
-    if (b->nseg < 1 || b->nitems < 1 || b->nitems > 0x7fffffff || b->ndense < 0)
-        return fail(GQ_ERR_INVALID_ARG, "%s: bad sizes (nseg %d, nitems %lld, ndense %d)", what, b->nseg, (long long)b->nitems, b->ndense);
-    if (!b->seg_table || !b->item_seg) return fail(GQ_ERR_INVALID_ARG, "%s: null table", what);
+    const int rc = gqsp::check_batch_common(b, what);
+    if (rc != GQ_OK) return rc;
     if (compress && (!b->hist || !b->state || !b->counts || !b->sums || (b->ndense > 0 && !b->dense_table)))
         return fail(GQ_ERR_INVALID_ARG, "%s: null scratch buffer", what);
     return GQ_OK;
@@ -434,10 +265,10 @@ static int stc_compress(const gq_stc_batch *b, uint8_t *wire, float ef_scale, fl
     using namespace gqs;
     const dim3 items((unsigned)b->nitems), segs((unsigned)b->nseg), block(THREADS);
     for (int p = 0; p < 3; ++p) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(stc_hist_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->state, b->hist, p,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(gqsp::hist_kernel<Sizes, EF>), items, block, 0, st, b->seg_table, b->item_seg, b->state, b->hist, p,
                            ef_scale);
         GQL_CHECK_LAUNCH("gq_stc_compress_batched (hist)");
-        hipLaunchKernelGGL(stc_pick_kernel, segs, block, 0, st, b->seg_table, b->state, b->hist, p);
+        hipLaunchKernelGGL(gqsp::pick_kernel<Sizes>, segs, block, 0, st, b->seg_table, b->state, b->hist, p);
         GQL_CHECK_LAUNCH("gq_stc_compress_batched (pick)");
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(stc_count_kernel<EF>), items, block, 0, st, b->seg_table, b->item_seg, b->state, b->counts, b->sums,
@@ -465,13 +296,9 @@ GQS_API int gq_stc_compress_batched(const gq_stc_batch *b, uint8_t *wire, float 
 
 GQS_API int gq_stc_decode_sum_batched(const gq_stc_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out,
                                       int plain, void *stream) {
-    const int rc = gqs::check_batch(b, "gq_stc_decode_sum_batched", false);
+    int rc = gqs::check_batch(b, "gq_stc_decode_sum_batched", false);
+    if (rc == GQ_OK) rc = gqsp::check_decode("gq_stc_decode_sum_batched", gathered, out, user_stride_bytes, R);
     if (rc != GQ_OK) return rc;
-    if (!gathered || !out) return gqs::fail(GQ_ERR_INVALID_ARG, "gq_stc_decode_sum_batched: null pointer");
-    if (R < 1 || (R > 1 && (user_stride_bytes < 0 || (user_stride_bytes & 3) != 0)))
-        return gqs::fail(GQ_ERR_INVALID_ARG, "gq_stc_decode_sum_batched: R = %d, user stride %lld", R, (long long)user_stride_bytes);
-    if ((reinterpret_cast<uintptr_t>(gathered) & 3) != 0)
-        return gqs::fail(GQ_ERR_INVALID_ARG, "gq_stc_decode_sum_batched: the gathered wire must be 4-byte aligned");
     hipLaunchKernelGGL(gqs::stc_decode_kernel, dim3((unsigned)b->nitems), dim3(gqs::THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                        b->seg_table, b->item_seg, gathered, user_stride_bytes, R, out, plain ? 1 : 0);
     GQL_CHECK_LAUNCH("gq_stc_decode_sum_batched");

@@ -5,24 +5,32 @@
 //                                     finite elements above eta_{s-1} (the contract's balanced tree: two levels inside a float4,
 //                                     six across the wave, two across the waves, two across the four quarters of the item); the
 //                                     pick launch (one workgroup per tensor) sums the items in the contract's tree and moves eta.
-//   count / scan / write              top-k's compaction without the tie bookkeeping (csrc/topk.hip): per-item counts of key > eta,
-//                                     their exclusive scan in index order, then every kept pair at its position -- ascending
-//                                     indices, the same bytes whatever order the workgroups run in -- plus the header, the pad
-//                                     slots, the dense decoded tensor and the residual.
-//   decode                            top-k's chunked binary-search decode-mean behind a header read and a clamp.
+//   count / scan / write              top-k's compaction without the tie bookkeeping (csrc/sparse_kernels.hpp): per-item counts of
+//                                     key > eta, their exclusive scan in index order, then every kept pair at its position --
+//                                     ascending indices, the same bytes whatever order the workgroups run in -- plus the header,
+//                                     the pad slots, the dense decoded tensor and the residual.
+//   decode                            top-k's chunked binary-search decode-mean (the same header's) behind a header read and a clamp.
 // No float or double atomics; every launch's arguments depend on the layout (and the caller's eta) alone.
 #include <math.h>
 #include <string.h>
 
 #include "gq_lib_prelude.hpp"
 #include "gq_thr.h"
+#include "sparse_kernels.hpp"
 
 #define GQH_API extern "C" __attribute__((visibility("default")))
 
 namespace gqh {
 
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
+using gql::copy_dense;
+using gql::err_buf;
+using gql::fail;
+using gqsp::block_exclusive_scan;
+using gqsp::key_of;
+using gqsp::load_w;
+using gqsp::THREADS;
+using gqsp::WAVES;
+
 constexpr int CHUNK = GQ_THR_CHUNK;
 constexpr int PER_THREAD = CHUNK / THREADS;
 constexpr int HDR = GQ_THR_HEADER_BYTES;
@@ -31,47 +39,6 @@ constexpr uint32_t MAX_ETA = 0x7f7fffffu;     // bits(FLT_MAX)
 constexpr int RUN_LEVELS = 12;                // a thread of the pick launch sums a run of up to 2^11 fit items (n < 2^31: 2^19 items)
 static_assert(CHUNK == 4 * 4 * THREADS, "the reduce launch's tree: four float4 per thread");
 static_assert(sizeof(gq_thr_batch) == 88, "gq_thr_batch: the layout the ctypes binding declares (gq_amd/native.py)");
-
-using gql::copy_dense;
-using gql::err_buf;
-using gql::fail;
-
-// (csrc/topk.hip's key, load and scan, copied: that file is another library's source)
-__device__ __forceinline__ uint32_t key_of(float w) {
-    const uint32_t a = __float_as_uint(w) & 0x7fffffffu;
-    return a > INF_KEY ? 0x7fffffffu : a;
-}
-
-template <bool EF>
-__device__ __forceinline__ float load_w(const float *__restrict__ v, const float *__restrict__ err, int64_t i, float ef_scale) {
-    float w = v[i];
-    if (EF && err) {
-        const float p = ef_scale * err[i];
-        w = w + p;
-    }
-    return w;
-}
-
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t x, uint32_t *lds, uint32_t *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t incl = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (int j = 0; j < WAVES; ++j) {
-        const uint32_t t = lds[j];
-        if (j < w) before += t;
-        tot += t;
-    }
-    *total = tot;
-    return before + incl - x;
-}
 
 __device__ __forceinline__ int64_t cap_of(const int64_t *rec) { return rec[6] & 0xffffffffll; }
 __device__ __forceinline__ int64_t stride_of(const int64_t *rec) {
@@ -286,24 +253,13 @@ __global__ __launch_bounds__(THREADS) void thr_count_kernel(const int64_t *__res
 // one workgroup per tensor: the items' counts -> their exclusive prefix sums (in place), in index order; state[1] = found
 __global__ __launch_bounds__(THREADS) void thr_scan_kernel(const int64_t *__restrict__ seg_table, int32_t *__restrict__ counts,
                                                            int32_t *__restrict__ state, int fixed, uint32_t fixed_eta) {
-    __shared__ uint32_t lds[WAVES];
     const int64_t *rec = seg_table + 8 * (int64_t)blockIdx.x;
     const int64_t n = rec[1], first = rec[2];
-    const int64_t nit = (n + CHUNK - 1) / CHUNK;
-    uint32_t cg = 0;
-    for (int64_t b0 = 0; b0 < nit; b0 += THREADS) {
-        const int64_t it = b0 + threadIdx.x;
-        uint32_t g = 0;
-        if (it < nit) g = (uint32_t)counts[2 * (first + it) + 1];
-        uint32_t tg;
-        const uint32_t bg = block_exclusive_scan(g, lds, &tg);
-        if (it < nit) counts[2 * (first + it) + 1] = (int32_t)(cg + bg);
-        cg += tg;
-        __syncthreads();      // (the next round rewrites lds)
-    }
+    uint32_t found[1];
+    gqsp::scan_item_counts<1, 1>(counts, first, (n + CHUNK - 1) / CHUNK, found);
     if (threadIdx.x == 0) {
         if (fixed) state[4 * blockIdx.x] = (int32_t)fixed_eta;
-        state[4 * blockIdx.x + 1] = (int32_t)cg;
+        state[4 * blockIdx.x + 1] = (int32_t)found[0];
     }
 }
 
@@ -313,7 +269,6 @@ __global__ __launch_bounds__(THREADS) void thr_write_kernel(const int64_t *__res
                                                             uint8_t *__restrict__ wire, float *__restrict__ out, float ef_scale,
                                                             const int64_t *__restrict__ dense_table, int ndense) {
     copy_dense<THREADS>(dense_table, ndense, wire);
-    __shared__ uint32_t lds[2][WAVES];      // [step parity][wave]
     const int64_t item = blockIdx.x;
     const int seg = item_seg[item];
     const int64_t *rec = seg_table + 8 * (int64_t)seg;
@@ -339,8 +294,6 @@ __global__ __launch_bounds__(THREADS) void thr_write_kernel(const int64_t *__res
     }
     const int64_t base = li * CHUNK;
     const int64_t end = base + CHUNK < n ? base + CHUNK : n;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
 #pragma unroll 1
     for (int s = 0; s < PER_THREAD; ++s) {
         const int64_t i = base + (int64_t)s * THREADS + threadIdx.x;
@@ -352,42 +305,15 @@ __global__ __launch_bounds__(THREADS) void thr_write_kernel(const int64_t *__res
             key = key_of(w);
         }
         const bool is_gt = valid && key > T;
-        const uint64_t mg = __ballot(is_gt);
-        if (lane == 0) lds[s & 1][wv] = (uint32_t)__popcll(mg);
-        __syncthreads();      // (parity: a wave still reading step s's words is not overwritten before step s + 2)
-        uint32_t pg = 0, tg = 0;
-#pragma unroll
-        for (int j = 0; j < WAVES; ++j) {
-            const uint32_t a = lds[s & 1][j];
-            if (j < wv) pg += a;
-            tg += a;
-        }
-        const uint32_t pos = gt_before + pg + (uint32_t)__popcll(mg & below);
-        const bool kept = is_gt && pos < (uint64_t)cap;
+        const gqsp::Rank r = gqsp::rank_step<false>(s, is_gt, false, gt_before, 0u);
+        const bool kept = is_gt && r.gb < (uint64_t)cap;
         if (kept) {
-            idx[pos] = (uint32_t)i;
-            val[pos] = w;
+            idx[r.gb] = (uint32_t)i;
+            val[r.gb] = w;
         }
-        if (valid) {
-            const float dec = w * (kept ? 1.0f : 0.0f);
-            if (o) o[i] = dec;
-            if (EF && err) {
-                v[i] = w;
-                err[i] = w - dec;
-            }
-        }
-        gt_before += tg;
+        if (valid) gqsp::store_decoded<EF>(v, err, o, i, w, w * (kept ? 1.0f : 0.0f));
+        gt_before += r.tg;
     }
-}
-
-__device__ __forceinline__ int64_t lower_bound_u32(const uint32_t *__restrict__ a, int64_t n, int64_t x) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)a[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(THREADS) void thr_decode_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
@@ -402,31 +328,21 @@ __global__ __launch_bounds__(THREADS) void thr_decode_kernel(const int64_t *__re
     const int64_t base = (item - rec[2]) * CHUNK;
     const int64_t end = base + CHUNK < n ? base + CHUNK : n;
     const uint32_t len = (uint32_t)(end - base);
-    for (int t = threadIdx.x; t < CHUNK; t += THREADS) acc[t] = 0.0f;
-    __syncthreads();
+    gqsp::decode_clear<CHUNK>(acc);
     const bool direct = plain && R == 1;
     for (int r = 0; r < R; ++r) {
         const uint8_t *p = gathered + (int64_t)r * stride + off;
         const uint32_t kept = *reinterpret_cast<const uint32_t *>(p);
         const int64_t kk = kept < (uint64_t)cap ? (int64_t)kept : cap;
-        const uint32_t *idx = reinterpret_cast<const uint32_t *>(p + HDR);
-        const float *val = reinterpret_cast<const float *>(p + HDR + 4 * cap);
-        const int64_t lo = lower_bound_u32(idx, kk, base), hi = lower_bound_u32(idx, kk, end);
-        for (int64_t j = lo + threadIdx.x; j < hi; j += THREADS) {
-            const uint32_t u = idx[j] - (uint32_t)base;
-            if (u < len) acc[u] = direct ? val[j] : acc[u] + val[j];
-        }
-        __syncthreads();      // payloads in order: r + 1 adds to what r left
+        gqsp::decode_add_pairs(acc, reinterpret_cast<const uint32_t *>(p + HDR), reinterpret_cast<const float *>(p + HDR + 4 * cap), kk, base, end,
+                               len, direct);
     }
-    const float fR = (float)R;
-    for (uint32_t t = threadIdx.x; t < len; t += THREADS) o[base + t] = direct ? acc[t] : acc[t] / fR;
+    gqsp::decode_store_mean(acc, o, base, len, R, direct);
 }
 
 static int check_batch(const gq_thr_batch *b, const char *what, bool compress) {
-    if (!b || b->struct_bytes != sizeof(gq_thr_batch)) return fail(GQ_ERR_INVALID_ARG, "%s: descriptor missing or of another size", what);
-    if (b->nseg < 1 || b->nitems < 1 || b->nitems > 0x7fffffff || b->ndense < 0)
-        return fail(GQ_ERR_INVALID_ARG, "%s: bad sizes (nseg %d, nitems %lld, ndense %d)", what, b->nseg, (long long)b->nitems, b->ndense);
-    if (!b->seg_table || !b->item_seg) return fail(GQ_ERR_INVALID_ARG, "%s: null table", what);
+    const int rc = gqsp::check_batch_common(b, what);
+    if (rc != GQ_OK) return rc;
     if (b->min_k < 1 || b->min_cap < 1 || b->min_stride < 1)
         return fail(GQ_ERR_INVALID_ARG, "%s: k = %d, cap = %d, fit stride = %d (each must be at least 1)", what, b->min_k, b->min_cap,
                     b->min_stride);
@@ -486,11 +402,9 @@ GQH_API int gq_thr_compress_batched(const gq_thr_batch *b, uint8_t *wire, float 
 
 GQH_API int gq_thr_decode_sum_batched(const gq_thr_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out,
                                       int plain, void *stream) {
-    const int rc = gqh::check_batch(b, "gq_thr_decode_sum_batched", false);
+    int rc = gqh::check_batch(b, "gq_thr_decode_sum_batched", false);
+    if (rc == GQ_OK) rc = gqsp::check_payloads("gq_thr_decode_sum_batched", gathered, out, user_stride_bytes, R);
     if (rc != GQ_OK) return rc;
-    if (!gathered || !out) return gqh::fail(GQ_ERR_INVALID_ARG, "gq_thr_decode_sum_batched: null pointer");
-    if (R < 1 || (R > 1 && (user_stride_bytes < 0 || (user_stride_bytes & 3) != 0)))
-        return gqh::fail(GQ_ERR_INVALID_ARG, "gq_thr_decode_sum_batched: R = %d, user stride %lld", R, (long long)user_stride_bytes);
     if (plain && R != 1) return gqh::fail(GQ_ERR_INVALID_ARG, "gq_thr_decode_sum_batched: plain takes one payload, got R = %d", R);
     if ((reinterpret_cast<uintptr_t>(gathered) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 3) != 0)
         return gqh::fail(GQ_ERR_INVALID_ARG, "gq_thr_decode_sum_batched: the gathered wire and `out` must be 4-byte aligned");

@@ -258,3 +258,10 @@ def test_error_table_of_the_readme():
         kept_abs = np.abs(w[d_stc != 0]).astype(np.float64).sum()
         assert abs(np.abs(d_stc).astype(np.float64).sum() - kept_abs) <= kept_abs * 2.0 ** -23
         assert "| %s | %.4f | %.4f |" % (name, e_stc, e_topk) in readme
+
+
+def test_the_select_and_the_shared_code_are_the_sparse_header_s():
+    import re
+    from test_topk_host import shared_header_checks
+    text = shared_header_checks("stc.hip")
+    assert not re.search(r"(hist|pick)_kernel\(const", text) and "gqsp::hist_kernel<Sizes, EF>" in text and "gqsp::pick_kernel<Sizes>" in text

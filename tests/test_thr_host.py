@@ -96,3 +96,9 @@ def test_struct_and_exports_against_the_header_and_the_library():
     assert int(re.search(r"#define GQ_THR_ABI_VERSION (\d+)", h).group(1)) == native.THR_ABI_VERSION
     L = native.thr_lib()
     assert L.gq_thr_abi_version() == native.THR_ABI_VERSION and all(hasattr(L, n) for n in native.THR_EXPORTS)
+
+
+def test_the_shared_code_is_the_sparse_header_s():
+    from test_topk_host import shared_header_checks
+    text = shared_header_checks("thr.hip")
+    assert "thr_reduce_kernel" in text and "thr_pick_kernel" in text      # the fit is its own

@@ -194,7 +194,7 @@ def test_error_feedback_against_torch_cpu_ops(name):
 
 # ---- preconditions of tests/test_gpu_topk_contract.py --------------------------------------------------------------------------
 def test_passes_as_the_kernel_file_states_them():
-    src = open(os.path.join(os.path.dirname(HERE), "gradient-quantization_amd", "csrc", "topk.hip")).read()
+    src = open(os.path.join(os.path.dirname(HERE), "gradient-quantization_amd", "csrc", "sparse_kernels.hpp")).read()
     assert "return p == 0 ? 20 : (p == 1 ? 9 : 0);" in src and "return p == 2 ? 9 : 11;" in src
     assert "constexpr int THREADS = 256;" in src and "#define GQ_TOPK_CHUNK 4096" in open(
         os.path.join(os.path.dirname(HERE), "include", "gq_topk.h")).read()

@@ -102,6 +102,36 @@ def test_topk_library_is_built_and_exports_its_abi():
     assert ctypes.sizeof(native._TopKBatchStruct) == 72      # (topk.hip static_asserts the same size)
 
 
+SHARED = ("key_of", "load_w", "block_exclusive_scan", "lower_bound_u32", "pass_shift", "pass_bits", "decode_add_pairs")
+
+
+def shared_header_checks(name):
+    """csrc/<name> takes what the sparse family shares from csrc/sparse_kernels.hpp and defines none of it itself."""
+    import re
+    csrc = os.path.join(os.path.dirname(HERE), "gradient-quantization_amd", "csrc")
+    text = open(os.path.join(csrc, name)).read()
+    assert '#include "sparse_kernels.hpp"' in text
+    for fn in SHARED:
+        assert not re.search(r"\b%s\([^;{]*\)\s*\{" % fn, text), "%s defines %s" % (name, fn)
+    return text
+
+
+def test_the_sparse_family_shares_one_header():
+    import re
+    csrc = os.path.join(os.path.dirname(HERE), "gradient-quantization_amd", "csrc")
+    header = open(os.path.join(csrc, "sparse_kernels.hpp")).read()
+    for fn in SHARED:      # each defined once, in the header; no other file under csrc/ defines it
+        assert len(re.findall(r"\b%s\([^;{]*\)\s*\{" % fn, header)) == 1, fn
+    assert len(re.findall(r"__global__[^;{]*\b(?:hist|pick)_kernel\(", header)) == 2
+    shared_header_checks("maurey.hip")
+    assert not re.search(r"(hist|pick)_kernel\(const", shared_header_checks("topk.hip"))      # the select's kernels: the header's
+    for name in sorted(os.listdir(csrc)):
+        if name != "sparse_kernels.hpp":
+            text = open(os.path.join(csrc, name)).read()
+            for fn in ("key_of", "block_exclusive_scan", "lower_bound_u32", "pass_shift", "pass_bits", "decode_add_pairs"):
+                assert not re.search(r"\b%s\([^;{]*\)\s*\{" % fn, text), "%s defines %s" % (name, fn)
+
+
 def test_topk_calls_fail_loudly_without_a_gpu_tensor():
     from gq_amd import native
     from gq_amd.codecs import TopKCodec

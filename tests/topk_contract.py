@@ -7,7 +7,7 @@ independent witnesses and asserts what every input claims about itself, tests/te
     section  = k x uint32 index, ascending, then k x f32 value (bit copies)
     dense    = w * (kept ? 1 : 0)
 
-The select reads the key in three passes (csrc/topk.hip: pass_shift / pass_bits): bits [20, 31), [9, 20) and [0, 9); a pick
+The select reads the key in three passes (csrc/sparse_kernels.hpp: pass_shift / pass_bits): bits [20, 31), [9, 20) and [0, 9); a pick
 launch of 256 threads walks a pass's histogram from the top, thread t owning the bins nbins - 1 - per * t downwards (per = 8, 8, 2)."""
 import numpy as np
 

@@ -1,20 +1,23 @@
 """The compiled code of a family of libraries' kernels, this tree against another checkout (the parent commit), kernel by kernel.
 
-    python tools/mx_isa_compare.py --parent DIR [--family mx] [--family rotq] [--out profiles/<family>_refactor_isa.txt]
+    python tools/mx_isa_compare.py --parent DIR [--family mx] [--family rotq] [--family sparse] [--out profiles/<family>_refactor_isa.txt]
 
 DIR is a checkout of the commit to compare with (`git worktree add DIR HEAD~1`, or `git archive` unpacked).  A family (FAMILIES
 below) is a list of csrc files, the number of kernels each holds and a key function:
     mx    mx.hip and mxr.hip, 2 x 56 kernels (csrc/mx_kernels.hpp), matched by library, kind (compress / decode), format, draw
           mode, error feedback and tensor type;
     rotq  drive.hip and eden.hip, 15 + 45 kernels (csrc/rotq_kernels.hpp), matched by library, kind (compress / decode /
-          decode-streams), bits, scale mode, error feedback and rotation kind (Signs / Stepped / Streamed).
+          decode-streams), bits, scale mode, error feedback and rotation kind (Signs / Stepped / Streamed);
+    sparse topk.hip, stc.hip, thr.hip and maurey.hip, 4 x 9 kernels (csrc/sparse_kernels.hpp), matched by library, the launch's
+          stage (the word in front of `_kernel`) and error feedback.
 Both trees' files are compiled with build.py's flags + --save-temps into scratch directories (no GPU needed); a kernel's key is
 read off the template arguments in its mangled name, whatever the function itself is called.  Per kernel: the instruction count
 (the .s text of the function, labels, directives and comments dropped), the registers and the scratch / LDS bytes of the kernel's
 metadata, both sides, and whether the instruction text is the same once the labels are renumbered.  Whole texts and numbers are
 compared; no instruction is looked for.  With one --family and no --out the result goes to profiles/<family>_refactor_isa.txt;
 several families (a change to a header both share) go into the first one's file.
-Exit status 1 if a kernel has scratch or LDS, or if its VGPR count falls into a lower waves-per-SIMD class than the other tree's.
+Exit status 1 if a kernel has scratch or LDS (mx, rotq: kernels that stay in registers) or other scratch or LDS bytes than the other
+tree's (sparse: kernels that use LDS by design), or if its VGPR count falls into a lower waves-per-SIMD class than the other tree's.
 """
 import argparse
 import importlib.util
@@ -74,10 +77,20 @@ def rotq_key(symbol):
     return kind, "b%d" % (args[0] if args else 1), "-", "-", rot[0] if kind == "decode" else "-"
 
 
-# family -> ((csrc file, kernels in it), ...), the key function, the key's column names
+def sparse_key(symbol):
+    """(stage, ef) of a kernel of topk.hip / stc.hip / thr.hip / maurey.hip: the stage is the word in front of `_kernel`, whatever
+    library or header the function is named after; ef is the bool among the template arguments ('-' where there is none)."""
+    stage = re.search(r"(hist|pick|count|scan|write|decode|reduce|sum|offsets|place|item)_kernel", symbol).group(1)
+    ef = re.findall(r"Lb(\d)E", template_args(symbol)[0])
+    return stage, ("ef" if int(ef[-1]) else "noef") if ef else "-"
+
+
+# family -> ((csrc file, kernels in it), ...), the key function, the key's column names and format, whether its kernels stay in
+# registers (any scratch or LDS is an error) or use LDS by design (other bytes than the parent's are)
 FAMILIES = {
-    "mx": ((("mx.hip", 56), ("mxr.hip", 56)), mx_key, "kind format mode ef type", "%-8s %-8s %-6s %-2s %-4s"),
-    "rotq": ((("drive.hip", 15), ("eden.hip", 45)), rotq_key, "kind bits scale ef rotation", "%-14s %-2s %-8s %-2s %-8s"),
+    "mx": ((("mx.hip", 56), ("mxr.hip", 56)), mx_key, "kind format mode ef type", "%-8s %-8s %-6s %-2s %-4s", True),
+    "rotq": ((("drive.hip", 15), ("eden.hip", 45)), rotq_key, "kind bits scale ef rotation", "%-14s %-2s %-8s %-2s %-8s", True),
+    "sparse": ((("topk.hip", 9), ("stc.hip", 9), ("thr.hip", 9), ("maurey.hip", 9)), sparse_key, "stage ef", "%-7s %-4s", False),
 }
 
 
@@ -121,9 +134,9 @@ def main():
     out = a.out or os.path.join(ROOT, "profiles", families[0] + "_refactor_isa.txt")
     text, bad, total, differ = [], [], 0, 0
     for fam in families:
-        files, key_of, columns, fmt = FAMILIES[fam]
+        files, key_of, columns, fmt, in_registers = FAMILIES[fam]
         text += ["# tools/mx_isa_compare.py: the kernels of %s, the parent commit against this tree (gfx950, build.py's flags)."
-                 % " and ".join(name for name, _ in files),
+                 % (", ".join(name for name, _ in files[:-1]) + " and " + files[-1][0]),
                  "# columns: library %s | instructions parent new | VGPRs parent new | SGPRs parent new |" % columns,
                  "#          scratch bytes parent new | LDS bytes parent new | instruction text with labels renumbered"]
         for name, count in files:
@@ -133,13 +146,16 @@ def main():
                 (t0, m0), (t1, m1) = old[key], new[key]
                 same = t0 == t1
                 total, differ = total + 1, differ + (not same)
-                text.append(("%-5s " + fmt + "  %5d %5d  %3d %3d  %3d %3d  %d %d  %d %d  %s")
+                text.append(("%%-%ds " % max(5, max(len(n) - 4 for n, _ in files)) + fmt + "  %5d %5d  %3d %3d  %3d %3d  %d %d  %d %d  %s")
                             % ((name[:-4],) + key + (m0["instructions"], m1["instructions"], m0[".vgpr_count"], m1[".vgpr_count"],
                                                      m0[".sgpr_count"], m1[".sgpr_count"], m0[".private_segment_fixed_size"],
                                                      m1[".private_segment_fixed_size"], m0[".group_segment_fixed_size"],
                                                      m1[".group_segment_fixed_size"], "identical" if same else "DIFFERS")))
-                if m1[".private_segment_fixed_size"] or m1[".group_segment_fixed_size"]:
+                if in_registers and (m1[".private_segment_fixed_size"] or m1[".group_segment_fixed_size"]):
                     bad.append("%s %s: scratch or LDS" % (name, key))
+                for what, field in (("scratch", ".private_segment_fixed_size"), ("LDS", ".group_segment_fixed_size")):
+                    if not in_registers and m1[field] != m0[field]:
+                        bad.append("%s %s: %d bytes of %s against %d" % (name, key, m1[field], what, m0[field]))
                 if waves_per_simd(m1[".vgpr_count"]) < waves_per_simd(m0[".vgpr_count"]):
                     bad.append("%s %s: %d VGPRs against %d: fewer waves per SIMD" % (name, key, m1[".vgpr_count"], m0[".vgpr_count"]))
     tail = "# %d kernels, %d with other instruction text than the parent's" % (total, differ)

@@ -31,7 +31,9 @@ import contextlib
 import ctypes
 import json
 import os
+import shutil
 import sys
+import tempfile
 from argparse import Namespace
 
 import torch
@@ -142,6 +144,30 @@ def other_library(path, batch_cls, name, prefix, exports):
         yield
     finally:
         batch_cls.LIBRARY = saved
+
+
+def second_load(path):
+    """A copy of the library at `path` under another directory: loading it gives the process a second code object of the same
+    instruction text -- the A/A yardstick of a refactor's timing (the loader hands out ONE handle per file, however often asked)."""
+    return shutil.copy(path, os.path.join(tempfile.mkdtemp(prefix="gq_second_load_"), os.path.basename(path)))
+
+
+def refactor_ratios(row, new, parent, kinds=("compress", "decode_mean_R1", "decode_mean_R8")):
+    """This build's launches (`new`) over the parent's (`parent`) next to the parent's second load over its first (A/A), graphed
+    times of `row`.  The bar of a case: its largest A/A ratio + 0.01 (the half-width of stc_time.py's BAND)."""
+    out = {"new_over_parent": {}, "aa": {}}
+    for kind in kinds:
+        base = row["%s_%s_us" % (parent, kind)]
+        out["new_over_parent"][kind] = round(row["%s_%s_us" % (new, kind)] / base, 3)
+        out["aa"][kind] = round(row["%s_again_%s_us" % (parent, kind)] / base, 3)
+    return out
+
+
+def refactor_verdict(row, ratios):
+    """ratios: library -> refactor_ratios(...).  One bar for the case; `missed`: the launches above it."""
+    bar = round(max(r for lib in ratios.values() for r in lib["aa"].values()) + 0.01, 3)
+    row["refactor"] = dict(ratios, bar=bar, missed=["%s_%s" % (lib, kind) for lib, rr in ratios.items()
+                                                     for kind, r in rr["new_over_parent"].items() if r > bar])
 
 
 def exports_bf16(path, prefix):

@@ -2,6 +2,7 @@
 commit's libgq_topk.so) loaded into the same process:
 
     python tools/stc_time.py --parent-lib libgq_topk.so [--out FILE]      (default: profiles/stc_time.jsonl)
+    python tools/stc_time.py --parent-lib libgq_topk.so --parent-own-lib libgq_stc.so --launches-only --out FILE
 
 Rows (one JSON line each), cr = 256, N(0, 1) gradients:
   single_25m, resnet50_list
@@ -16,6 +17,10 @@ Rows (one JSON line each), cr = 256, N(0, 1) gradients:
   resnet50_step   PSQuantizer record + apply over the whole ResNet-50 parameter list, one user, default launches (graph replay),
                   gradients at fixed addresses: --quantizer stc and stc --ef next to --quantizer topk and topk --ef (the in-tree
                   library), alternated, three rounds each.
+--parent-own-lib: an older libgq_stc.so as well (a refactor of both libraries against its parent commit).  The two launch rows then
+also time parent_stc, and a second load of either parent file (parent_topk_again, parent_stc_again: the A/A ratios), and carry
+`refactor`: stc over parent_stc and topk over parent_topk per launch, the A/A ratios, the case's bar (its largest A/A ratio + 0.01)
+and what missed it.  --launches-only leaves the resnet50_step rows out.
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -29,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gradient-quantization_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from mx_time import _args, graphed, other_library, timed, write_rows  # noqa: E402
+from mx_time import _args, graphed, other_library, refactor_ratios, refactor_verdict, second_load, timed, write_rows  # noqa: E402
 from gq_amd import native  # noqa: E402
 from gq_amd.codecs import BatchedSTC, BatchedTopK, STCCodec, TopKCodec, _up  # noqa: E402
 from gq_amd.compressors import SparseTernaryCompressor, TopKSparsificationCompressor  # noqa: E402
@@ -49,20 +54,26 @@ def _group(cls, codecs, dev):
     return cls(codecs, offs, list(range(len(codecs))), dev, 1, ub), ub
 
 
-def launches_row(name, sizes, dev, parent_topk):
+def launches_row(name, sizes, dev, parent_topk, parent_stc=None):
     torch.manual_seed(1)
     ts = [torch.randn(n, device=dev) for n in sizes]
     elems = sum(sizes)
     tk = lambda: [TopKCodec(TopKSparsificationCompressor(n, (n,), _args(cr=CR)), n, (n,)) for n in sizes]
+    stc = lambda: [STCCodec(SparseTernaryCompressor(n, (n,), _args(cr=CR)), n, (n,)) for n in sizes]
     groups, wires = {}, {}
     yard = "parent_topk" if parent_topk else "topk"
-    if parent_topk:
-        with other_library(parent_topk, native.TopKBatch, "libgq_topk.so", "gq_topk_", native.TOPK_EXPORTS):
-            groups[yard], ub = _group(BatchedTopK, tk(), dev)
-        wires[yard] = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
+    olds = [(yard, parent_topk, BatchedTopK, tk)] if parent_topk else []
+    if parent_stc:
+        olds += [("parent_topk_again", second_load(parent_topk), BatchedTopK, tk), ("parent_stc", parent_stc, BatchedSTC, stc),
+                 ("parent_stc_again", second_load(parent_stc), BatchedSTC, stc)]
+    for gname, path, cls, codecs in olds:
+        with (other_library(path, native.TopKBatch, "libgq_topk.so", "gq_topk_", native.TOPK_EXPORTS) if cls is BatchedTopK
+              else other_library(path, native.STCBatch, "libgq_stc.so", "gq_stc_", native.STC_EXPORTS)):
+            groups[gname], ub = _group(cls, codecs(), dev)
+        wires[gname] = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
     groups["topk"], ub = _group(BatchedTopK, tk(), dev)
     wires["topk"] = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
-    groups["stc"], ub = _group(BatchedSTC, [STCCodec(SparseTernaryCompressor(n, (n,), _args(cr=CR)), n, (n,)) for n in sizes], dev)
+    groups["stc"], ub = _group(BatchedSTC, stc(), dev)
     wires["stc"] = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
     for gname, g in groups.items():
         assert g.encode(ts, wires[gname][0], 0, 0)
@@ -88,7 +99,7 @@ def launches_row(name, sizes, dev, parent_topk):
         row[key + "_us_rounds"] = [round(x, 2) for x in tt]
         row[key + "_us"] = round(min(tt), 2)
     missed = []
-    for path in [p for p in groups if p != yard]:
+    for path in ("topk", "stc") if parent_topk else ("stc",):
         for kind in KINDS:
             for eager in ("", "_eager"):
                 field = "%s_%s%s_over_%s" % (path, kind, eager, yard)
@@ -99,6 +110,8 @@ def launches_row(name, sizes, dev, parent_topk):
     for path in groups:
         row[path + "_compress_gradient_reads_equiv"] = round(row[path + "_compress_us"] * 1e-6 * 6.3e12 / (elems * 4), 2)
     row["missed"] = missed
+    if parent_stc:
+        refactor_verdict(row, {"topk": refactor_ratios(row, "topk", "parent_topk"), "stc": refactor_ratios(row, "stc", "parent_stc")})
     return row
 
 
@@ -133,14 +146,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stc_time.jsonl"))
     ap.add_argument("--parent-lib", default=None, help="an older libgq_topk.so: its launches are the yardstick; without it the in-tree one")
+    ap.add_argument("--parent-own-lib", default=None, help="an older libgq_stc.so (needs --parent-lib): the rows' `refactor` field")
+    ap.add_argument("--launches-only", action="store_true", help="the two launch rows, no resnet50_step rows")
     a = ap.parse_args()
+    if a.parent_own_lib and not a.parent_lib:
+        ap.error("--parent-own-lib needs --parent-lib")
     dev = torch.device("cuda:0")
     with open(os.path.join(ROOT, "tests", "golden", "resnet50_cifar_shapes.json")) as f:
         shapes = json.load(f)["parameter_shapes"]
     r50 = [n for n in (int(torch.Size(s).numel()) for s in shapes) if n > 1000]
     parent = os.path.abspath(a.parent_lib) if a.parent_lib else None
-    write_rows(a.out, [launches_row("single_25m", [25_000_000], dev, parent), launches_row("resnet50_list", r50, dev, parent)]
-               + resnet50_rows(dev, shapes))
+    own = os.path.abspath(a.parent_own_lib) if a.parent_own_lib else None
+    write_rows(a.out, [launches_row("single_25m", [25_000_000], dev, parent, own), launches_row("resnet50_list", r50, dev, parent, own)]
+               + ([] if a.launches_only else resnet50_rows(dev, shapes)))
 
 
 if __name__ == "__main__":

@@ -2,6 +2,7 @@
 commit's libgq_topk.so) loaded into the same process:
 
     python tools/thr_time.py --parent-lib libgq_topk.so [--out FILE]      (default: profiles/thr_time.jsonl)
+    python tools/thr_time.py --parent-lib libgq_topk.so --parent-own-lib libgq_thr.so --launches-only --out FILE
 
 Rows (one JSON line each), cr = 256, N(0, 1) gradients:
   single_25m, resnet50_list
@@ -19,6 +20,10 @@ Rows (one JSON line each), cr = 256, N(0, 1) gradients:
   resnet50_step   PSQuantizer record + apply over the whole ResNet-50 parameter list, one user, default launches (graph replay),
                   gradients at fixed addresses: --quantizer threshold (three stages; --thr-fit-stride 8; a fixed threshold; --ef)
                   next to --quantizer topk and topk --ef (the in-tree library), alternated, three rounds each.
+--parent-own-lib: an older libgq_thr.so as well (a refactor of the library against its parent commit).  The two launch rows then also
+time parent_thr (three stages at fit stride 1, and the decode-means on thr's payloads) and a second load of the same file
+(parent_thr_again: the A/A ratios), and carry `refactor`: thr over parent_thr per launch, the A/A ratios, the case's bar (its
+largest A/A ratio + 0.01) and what missed it.  --launches-only leaves the resnet50_step rows out.
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -34,7 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gradient-quantization_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from mx_time import _args, graphed, other_library, timed, write_rows  # noqa: E402
+from mx_time import _args, graphed, other_library, refactor_ratios, refactor_verdict, second_load, timed, write_rows  # noqa: E402
 from gq_amd import native  # noqa: E402
 from gq_amd.codecs import BatchedThr, BatchedTopK, ThrCodec, TopKCodec, _up  # noqa: E402
 from gq_amd.compressors import ThresholdSparsificationCompressor, TopKSparsificationCompressor  # noqa: E402
@@ -70,7 +75,7 @@ def _thr_wire_of(topk_wire, topk_codecs, topk_offs, thr_codecs, thr_offs, ub):
     return torch.from_numpy(dst)
 
 
-def launches_row(name, sizes, dev, parent_topk):
+def launches_row(name, sizes, dev, parent_topk, parent_thr=None):
     torch.manual_seed(1)
     ts = [torch.randn(n, device=dev) for n in sizes]
     elems = sum(sizes)
@@ -86,6 +91,12 @@ def launches_row(name, sizes, dev, parent_topk):
         thr_codecs[mode] = [ThrCodec(ThresholdSparsificationCompressor(n, (n,), _args(cr=CR, **kw)), n, (n,)) for n in sizes]
         groups[mode], thr_offs, ub = _group(BatchedThr, thr_codecs[mode], dev)
         wires[mode] = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
+    olds = [("parent_thr", parent_thr), ("parent_thr_again", second_load(parent_thr))] if parent_thr else []
+    for gname, path in olds:
+        with other_library(path, native.ThrBatch, "libgq_thr.so", "gq_thr_", native.THR_EXPORTS):
+            codecs = [ThrCodec(ThresholdSparsificationCompressor(n, (n,), _args(cr=CR, **MODES["thr_s3_m1"])), n, (n,)) for n in sizes]
+            groups[gname], _, ub = _group(BatchedThr, codecs, dev)
+        wires[gname] = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
     for gname, g in groups.items():
         assert g.encode(ts, wires[gname][0], 0, 0)
     torch.cuda.synchronize()
@@ -117,7 +128,7 @@ def launches_row(name, sizes, dev, parent_topk):
             times.setdefault(gname + "_compress_eager", []).append(timed(lambda: g.encode(ts, w[0], 0, 0)))
             times.setdefault(gname + "_compress", []).append(graphed(lambda: g.encode(ts, w[0], 0, 0)))
         for R in (1, 8):
-            for gname, g, w in ((yard, g_tk, wires[yard]), ("thr", g_thr, dec)):
+            for gname, g, w in [(yard, g_tk, wires[yard]), ("thr", g_thr, dec)] + [(gname, groups[gname], dec) for gname, _ in olds]:
                 times.setdefault("%s_decode_mean_R%d_eager" % (gname, R), []).append(timed(lambda: g._batch.decode(w[:R], R, out)))
                 times.setdefault("%s_decode_mean_R%d" % (gname, R), []).append(graphed(lambda: g._batch.decode(w[:R], R, out)))
     for key, tt in times.items():
@@ -134,6 +145,9 @@ def launches_row(name, sizes, dev, parent_topk):
     for path in list(MODES) + [yard]:
         row[path + "_compress_gradient_reads_equiv"] = round(row[path + "_compress_us"] * 1e-6 * 6.3e12 / (elems * 4), 2)
     row["missed"] = missed
+    if parent_thr:
+        row["thr_compress_us"] = row["thr_s3_m1_compress_us"]      # (the new side of the refactor's compress: the parent's mode)
+        refactor_verdict(row, {"thr": refactor_ratios(row, "thr", "parent_thr")})
     return row
 
 
@@ -171,14 +185,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "thr_time.jsonl"))
     ap.add_argument("--parent-lib", default=None, help="an older libgq_topk.so: its launches are the yardstick; without it the in-tree one")
+    ap.add_argument("--parent-own-lib", default=None, help="an older libgq_thr.so (needs --parent-lib): the rows' `refactor` field")
+    ap.add_argument("--launches-only", action="store_true", help="the two launch rows, no resnet50_step rows")
     a = ap.parse_args()
+    if a.parent_own_lib and not a.parent_lib:
+        ap.error("--parent-own-lib needs --parent-lib")
     dev = torch.device("cuda:0")
     with open(os.path.join(ROOT, "tests", "golden", "resnet50_cifar_shapes.json")) as f:
         shapes = json.load(f)["parameter_shapes"]
     r50 = [n for n in (int(torch.Size(s).numel()) for s in shapes) if n > 1000]
     parent = os.path.abspath(a.parent_lib) if a.parent_lib else None
-    write_rows(a.out, [launches_row("single_25m", [25_000_000], dev, parent), launches_row("resnet50_list", r50, dev, parent)]
-               + resnet50_rows(dev, shapes))
+    own = os.path.abspath(a.parent_own_lib) if a.parent_own_lib else None
+    write_rows(a.out, [launches_row("single_25m", [25_000_000], dev, parent, own), launches_row("resnet50_list", r50, dev, parent, own)]
+               + ([] if a.launches_only else resnet50_rows(dev, shapes)))
 
 
 if __name__ == "__main__":
