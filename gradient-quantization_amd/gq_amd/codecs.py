@@ -556,8 +556,25 @@ class _SparseCodec(object):
     dtype = torch.float32      # of the gradients, and of what roundtrip / decode_mean return (MXCodec: float32 or bfloat16)
 
     def _wire_bytes(self):
-        """Bytes of a wire of this tensor alone (a launch is handed a valid address also when the section is empty)."""
+        """Bytes of a wire of this tensor alone.  A launch is handed a valid address also when the section is empty, which only
+        TopKCodec's can be (k = 0); every other section is at least 16 bytes at one element, so this is nbytes."""
         return max(16, self.nbytes)
+
+    def _draws(self, r, dev):
+        """The draws of a call as the group takes them: `r`, or for gq_rng "reference" torch.rand(draw_count()) (the codec on its
+        own: the quantizers draw once per record and hand out slices); None where there are none."""
+        if r is None and self.uses_reference_draws():
+            r = torch.rand(self.draw_count()).to(dev)
+        return (r, {0: 0}) if r is not None else None
+
+    @staticmethod
+    def _errs_of(grad, err, who):
+        """A call's residual as the group's `errs`.  Error feedback updates the gradient in place: it must be contiguous itself."""
+        if err is None:
+            return None
+        if not grad.is_contiguous():
+            raise ValueError("%s: error feedback updates the gradient in place and needs a contiguous one" % who)
+        return [err.view(-1)]
 
     def _batched1(self, dev):
         if self._single is None or self._single.device != dev:
@@ -647,9 +664,6 @@ class ThrCodec(_SparseCodec):
         self.stages, self.eta = compressor.stages, compressor.eta
         self.nbytes = thr_section_bytes(numel, compressor.cr, compressor.percent)
 
-    def _wire_bytes(self):
-        return self.nbytes      # (never empty: the header)
-
     def header(self, wire_user, off):
         """(kept, found, eta) of this tensor's section of one user's wire: a read of three words, with a synchronisation."""
         w = wire_user[off:off + 12].cpu().numpy()
@@ -679,9 +693,6 @@ class STCCodec(_SparseCodec):
         if not 1 <= numel < 2 ** 31 or not 0 <= self.k <= numel:
             raise ValueError("STCCodec: k = %d for a tensor of %d elements (1 ... 2^31 - 1)" % (self.k, numel))
         self.nbytes = _stc_bytes(numel, self.k)
-
-    def _wire_bytes(self):
-        return self.nbytes      # (never empty: the header)
 
     def header(self, wire_user, off):
         """(k, mu) of this tensor's section of one user's wire: a read of two words, with a synchronisation."""
@@ -801,14 +812,6 @@ class MaureyCodec(_SparseCodec):
     def draw_count(self):
         return self.k
 
-    def _wire_bytes(self):
-        return self.nbytes      # (never empty: the header)
-
-    def _draws(self, r, dev):
-        if r is None and self.uses_reference_draws():
-            r = torch.rand(self.k).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
-        return (r, {0: 0}) if r is not None else None
-
     def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None):
         _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out)
 
@@ -852,14 +855,6 @@ class MXCodec(_SparseCodec):
     def draw_count(self):
         return self.numel
 
-    def _wire_bytes(self):
-        return self.nbytes      # (never empty: numel >= 1)
-
-    def _draws(self, r, dev):
-        if r is None and self.uses_reference_draws():
-            r = torch.rand(self.numel).to(dev)      # (the codec on its own: the quantizers draw once per record and hand out slices)
-        return (r, {0: 0}) if r is not None else None
-
     def set_dtype(self, dtype):
         """(the quantizers: a codec factory is not told the parameter's dtype)"""
         if dtype not in native.MX_DTYPES:
@@ -869,10 +864,9 @@ class MXCodec(_SparseCodec):
     def encode_into(self, grad, wire_user, off, salt, r=None, seed=None, out=None, err=None, ef_scale=None):
         """err, ef_scale: error feedback in the same launch -- grad <- w = grad + ef_scale * err (narrowed where grad is bfloat16),
         err <- w - decoded from the unrounded w.  err: float32, contiguous, of grad's size; grad must then be contiguous itself."""
-        if err is not None and not grad.is_contiguous():
-            raise ValueError("MXCodec: error feedback updates the gradient in place and needs a contiguous one")
-        _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out,
-                                 errs=[err.view(-1)] if err is not None else None, ef_scale=ef_scale)
+        errs = self._errs_of(grad, err, "MXCodec")      # (in front of the draws: a refused call takes none from the generator)
+        _SparseCodec.encode_into(self, grad, wire_user, off, salt, draws=self._draws(r, grad.device), seed=seed, out=out, errs=errs,
+                                 ef_scale=ef_scale)
 
 
 class MXRCodec(MXCodec):
@@ -933,16 +927,10 @@ class DriveCodec(_SparseCodec):
         grp.stream_base = self.stream     # (a one-tensor group records into slot 0)
         return grp
 
-    def _wire_bytes(self):
-        return self.nbytes      # (never empty: numel >= 1)
-
     def encode_into(self, grad, wire_user, off, salt, out=None, err=None, ef_scale=None):
         """err, ef_scale: error feedback in the same launch -- grad <- w = grad + ef_scale * err, err <- w - decoded.  err: float32,
         contiguous, of grad's size; grad must then be contiguous itself."""
-        if err is not None and not grad.is_contiguous():
-            raise ValueError("DriveCodec: error feedback updates the gradient in place and needs a contiguous one")
-        _SparseCodec.encode_into(self, grad, wire_user, off, salt, out=out, errs=[err.view(-1)] if err is not None else None,
-                                 ef_scale=ef_scale)
+        _SparseCodec.encode_into(self, grad, wire_user, off, salt, out=out, errs=self._errs_of(grad, err, "DriveCodec"), ef_scale=ef_scale)
 
 
 def eden_section_bytes(numel, bits):
@@ -1227,11 +1215,9 @@ class _BatchedBase(object):
         out, views = self._out_buffer(gathered.device, advance=part is None or part[2])
         batch = self._batch if part is None else self._range(part[0], part[1])
         if batch is not None:
-            kw = {"tail": tail} if tail is not None else {}      # (BatchedHSQ only: see takes_tail)
-            if self.rotation is not None:
-                kw["rotation"] = self.rotation                   # (BatchedDrive / BatchedEden in step mode)
-            if self.own:
-                kw["rotation"], kw["first_stream"] = self._pair(), 0      # (payload r of the gather under stream r)
+            kw = self._rotation_kw()
+            if tail is not None:
+                kw["tail"] = tail      # (BatchedHSQ only: see takes_tail)
             if getattr(self, "fma", False) and R >= 2 and not plain:
                 batch.decode(gathered, R, out, fma=True, **kw)      # (BatchedHSQ only: the quantizer sets `fma` on its HSQ groups)
             else:
@@ -1241,6 +1227,13 @@ class _BatchedBase(object):
     takes_tail = False      # the group's decode-mean launch can take the aggregate's small per-step work along (native.StepTail)
     rotation = None         # BatchedDrive / BatchedEden in step mode: the quantizer's { seed, step } pair, read by every launch
     own = False             # BatchedDrive / BatchedEden under user_rotation = 'own': the *_streams launches (they read the pair too)
+
+    def _rotation_kw(self):
+        """The decode launch's keywords for `rotation` and `own` (two attribute reads for every other group): the pair of step
+        mode, or under 'own' the pair and first stream 0 -- payload r of the gather under stream r."""
+        if self.own:
+            return {"rotation": self._pair(), "first_stream": 0}
+        return {"rotation": self.rotation} if self.rotation is not None else {}
 
     def upload_layout(self):
         """Device header with the layout columns only (no tensor pointers): enough for decode_mean,
@@ -1759,13 +1752,35 @@ class BatchedQSGD(_BatchedBase):
         return True
 
 
+def _item_draws(random, given, seed, counter_seed, salt):
+    """(mode, seed, r) of an item group's compress: none where the rounding is to nearest; the given uniforms (laid out as the group
+    reads them); the caller's seed; the group's { seed, step } pair (its address); a fresh seed per call."""
+    if not random:
+        return native.RANDOM_OFF, 0, None
+    if given is not None:
+        return native.RANDOM_GIVEN, 0, given
+    if seed is not None:
+        return native.RANDOM_DEVICE, int(seed), None
+    if counter_seed is not None:
+        return native.RANDOM_DEVICE_COUNTER, counter_seed, None
+    return native.RANDOM_DEVICE, _next_seed() ^ salt, None
+
+
 class _ItemGroup(_BatchedBase):
-    """What BatchedTopK, BatchedSign, BatchedMaurey and BatchedMX share: a segment table over an item table (native._ItemBatch), a compress
-    that also writes the dense decoded tensors where a caller asks for them -- which is what roundtrip returns -- and a
-    decode-mean without a step tail."""
+    """What the item-table groups share: a segment table over an item table (native._ItemBatch), a decode-mean without a step tail
+    and ONE encode, whose compress also writes the dense decoded tensors where a caller asks for them -- which is what roundtrip
+    returns.  What a group may state about its encode: what it refuses (WIRE_ALIGN, reference_draws: _refuses), EF_DENSE,
+    _compress_args and, where its launches read one user's state (BatchedDGC, BatchedPowerSGD), _user_state over the state-table cache."""
 
     takes_tail = False
     align = 4
+    WIRE_ALIGN = 1          # the wire's address is a multiple of so many bytes, or encode refuses
+    # Error feedback takes its residual from the dense decode, so a record with it needs `out` (the group's own buffer where nobody asked):
+    #   True  -- the sparsifiers (top-k, STC, threshold, Maurey): the residual launch subtracts the decoded tensors it finds there;
+    #   False -- sign, MX / MXR, DRIVE / EDEN, PowerSGD: the launch that rounds an element (a tile) has its decoded value at hand.
+    EF_DENSE = False
+    random = counter = reference_draws = False      # the draws (BatchedMaurey, BatchedMX): see _drawn
+    _state_tables = None    # {key: (device table, the buffers it names)} of a group whose launches read one user's state
 
     def _item_setup(self, codecs, offsets, idxs, device, slots, user_bytes, dense, items_of, columns, out_pad):
         """The group's tables and header.  items_of(codec): the items of a tensor; columns: {column of the segment table: its
@@ -1803,16 +1818,88 @@ class _ItemGroup(_BatchedBase):
             self._ef_out = torch.empty(self.out_floats, dtype=torch.float32, device=device)
         return self._ef_out
 
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
+               rng_slot=None, table_current=False, out=None, seed=None):
+        """One user's record: `tensors` compressed into the wire; out (the group's dtype [out_floats]): also their dense decode.  With
+        `errs` (float32): error feedback in the same launches (t += ef_scale*err in front, err = t - decoded behind, both in place);
+        a group with state gives `errs` its own meaning (_user_state).  draws (given uniforms, see _given_draws): required for gq_rng
+        "reference", taken in any stochastic mode when handed in; seed: the device generator's seed for this call.  False --
+        nothing launched -- where the group refuses or a tensor cannot be addressed.  graph_header, table_current: see
+        _choose_header; dense, rng_slot: see BatchedHSQ.encode."""
+        if self._refuses(wire_user, draws):
+            return False
+        ebufs, table, ef_on = self._user_state(errs)
+        if table is False or not self._choose_header(tensors, slot, self.align, ebufs, dense, graph_header, table_current):
+            return False
+        if table is not None:
+            self._batch.set_state(table)
+        ef = ef_scale if ef_on else None
+        if ef is not None and out is None and self.EF_DENSE:
+            out = self._ef_buffer(wire_user.device)
+        launches, args = self._compress_args(out, ef, table, slot, salt, rng_slot, draws, seed)
+        self._launch(graph_header, defer_reset, launches, wire_user, *args)
+        return True
+
+    def _refuses(self, wire_user, draws):
+        """What an encode refuses in front of the header: reference draws that are not there for every tensor, a misaligned wire."""
+        return (self.reference_draws and not self._has_draws(draws)) or wire_user.data_ptr() % self.WIRE_ALIGN != 0
+
+    def _user_state(self, errs):
+        """errs -> (the error buffers for the header, the user's state table -- None: the group has none, False: refuse --, whether
+        this is a record with error feedback)."""
+        return errs, None, errs is not None
+
+    def _compress_args(self, out, ef, table, slot, salt, rng_slot, draws, seed):
+        """-> (the launches, their arguments behind `wire`)."""
+        return self._batch.compress, (out, ef)
+
+    def _has_draws(self, draws):
+        return self.random and draws is not None and all(i in draws[1] for i in self.idxs)
+
+    def _drawn(self, slot, salt, rng_slot, draws, seed):
+        """(mode, seed, r) of this call (_item_draws): the given draws in the group's layout, `seed`, the { seed, step } pair of the
+        slot (rng_slot: the reserved pair by name) where the quantizer gave the group pairs (`counter`), a fresh seed."""
+        counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
+        return _item_draws(self.random, self._given_draws(draws) if self._has_draws(draws) else None, seed,
+                           counter_seed if self.counter else None, salt)
+
+    # ---- one user's state behind the launches: a device table per set of state buffers, built once, never freed or moved (captured
+    # graphs hold its address), which keeps its buffers alive.  The group states _state_key(errs) -> (key, the header's error
+    # buffers), _state_valid(errs, key) and _state_rows(errs, key) -> (host table, the buffers it names).
+    def _state_table(self, errs):
+        """The device table of the state in `errs`, or False when its buffers cannot be addressed."""
+        key = self._state_key(errs)[0]
+        ent = self._state_tables.get(key)
+        if ent is None:
+            if not self._state_valid(errs, key):
+                return False
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("%s: a state table is built by an eager record, not under stream capture" % type(self).__name__)
+            host, buffers = self._state_rows(errs, key)
+            ent = self._state_tables[key] = (host.view(-1).to(self.device), buffers)
+        return ent[0]
+
+    def _addressable(self, ts, numels):
+        """Every tensor of one kind of state: one per tensor of the group, contiguous float32 of that size on the group's device."""
+        dev_index = self.device.index if self.device.index is not None else torch._C._cuda_getDevice()
+        return (len(ts) == self.nseg and all(map(_IS_CONTIGUOUS, ts)) and set(map(_DTYPE_OF, ts)) == _F32_ONLY
+                and set(map(_GET_DEVICE, ts)) == {dev_index} and all(t.numel() == n for t, n in zip(ts, numels)))
+
+    def upload(self, tensors, slot, errs=None, dense=None):
+        """(a group with state, in front of an address-free graph's replay: the graph's launches read the state table of the buffers
+        it was captured with -- the caller keys its graphs by those buffers' addresses, and a table, once built, stays where it is.
+        A table that was never built: False)"""
+        if self._state_tables is not None:
+            key, errs = self._state_key(errs)
+            if key is not None and key not in self._state_tables:
+                return False
+        return _BatchedBase.upload(self, tensors, slot, errs, dense)
+
     def decode_into(self, gathered, R, out, plain=False):
         """The decode-mean launch into a caller's buffer (_SparseCodec: a one-tensor group, its section at offset 0 of the rows)."""
         if not self.ready:
             self.upload_layout()
-        if self.own:
-            self._batch.decode(gathered, R, out, plain=plain, rotation=self._pair(), first_stream=0)
-        elif self.rotation is not None:
-            self._batch.decode(gathered, R, out, plain=plain, rotation=self.rotation)
-        else:
-            self._batch.decode(gathered, R, out, plain=plain)
+        self._batch.decode(gathered, R, out, plain=plain, **self._rotation_kw())
 
     def roundtrip(self, tensors, slot, salt, errs=None, ef_scale=None, draws=None, rng_slot=None, graph_header=None, defer_reset=None):
         """decompress(compress(t)) for every tensor of the group: the compress launches' own dense decode (the reference's signed
@@ -1844,6 +1931,7 @@ class BatchedTopK(_ItemGroup):
 
     OUT_PAD = 1                 # a tensor's views in the output buffer are packed back to back
     BATCH = native.TopKBatch
+    EF_DENSE = True
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         # an item is a chunk of elements
@@ -1859,20 +1947,6 @@ class BatchedTopK(_ItemGroup):
         """hist, state, counts (and what a subclass's launches take behind them)."""
         return (torch.zeros(nseg * native.TOPK_HIST_BINS, dtype=torch.int32, device=device),
                 torch.zeros(nseg * 4, dtype=torch.int32, device=device), torch.zeros(items * 2, dtype=torch.int32, device=device))
-
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None):
-        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
-        feedback in the same launches (t += ef_scale*err before the select, err = t - decoded after it, both in place).
-        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
-        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
-            return False
-        ef = ef_scale if errs is not None else None
-        if ef is not None and out is None:
-            out = self._ef_buffer(wire_user.device)
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef)
-        return True
-
 
 TopKCodec.GROUP = BatchedTopK
 
@@ -1896,47 +1970,28 @@ class BatchedDGC(BatchedTopK):
         self._scratch = torch.empty(max(4, self.out_floats), dtype=torch.float32, device=device)
         self._state_tables = {}
 
-    def _state_table(self, us, vs):
-        """The device table of these state buffers (include/gq_dgc.h: state_table), or None when they cannot be addressed."""
-        key = (tuple(map(_DATA_PTR, us)), tuple(map(_DATA_PTR, vs)))
-        tab = self._state_tables.get(key)
-        if tab is None:
-            dev_index = self.device.index if self.device.index is not None else torch._C._cuda_getDevice()
-            for ts in (us, vs):
-                if (len(ts) != self.nseg or not all(map(_IS_CONTIGUOUS, ts)) or set(map(_DTYPE_OF, ts)) != _F32_ONLY
-                        or set(map(_GET_DEVICE, ts)) != {dev_index} or any(t.numel() != cd.numel for t, cd in zip(ts, self.codecs))):
-                    return None
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("BatchedDGC: a state table is built by an eager record, not under stream capture")
-            host = self._layout.clone()
-            base = self._scratch.data_ptr()
-            for s in range(self.nseg):
-                host[s, 0], host[s, 6], host[s, 7] = base + 4 * self.out_off[s], key[0][s], key[1][s]
-            tab = self._state_tables[key] = (host.view(-1).to(self.device), list(us), list(vs))      # (the buffers stay alive with their table)
-        return tab[0]
+    def _state_key(self, errs):
+        return (None, None) if errs is None else ((tuple(map(_DATA_PTR, errs[0])), tuple(map(_DATA_PTR, errs[1]))), None)
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None):
-        """errs = ([u], [v]) of one user, ef_scale = m: one record with momentum correction into that user's wire.  errs None:
-        BatchedTopK.encode (plain top-k).  graph_header, table_current, dense: see BatchedTopK.encode."""
-        if errs is None:
-            return BatchedTopK.encode(self, tensors, wire_user, slot, salt, None, None, draws, graph_header, dense, defer_reset, rng_slot,
-                                      table_current, out)
-        table = self._state_table(*errs)
-        if table is None or not self._choose_header(tensors, slot, self.align, None, dense, graph_header, table_current):
-            return False
-        self._batch.set_state(table)
-        if out is None:
-            out = self._ef_buffer(wire_user.device)
-        self._launch(graph_header, defer_reset, self._batch.record, wire_user, out, float(ef_scale))
-        return True
+    def _state_valid(self, errs, key):
+        numels = [cd.numel for cd in self.codecs]
+        return self._addressable(errs[0], numels) and self._addressable(errs[1], numels)
 
-    def upload(self, tensors, slot, errs=None, dense=None):
-        """(in front of an address-free graph's replay: the graph's launches read the state table of the buffers it was captured
-        with -- the caller keys its graphs by the state buffers' addresses, and a table, once built, stays where it is)"""
-        if errs is not None and (tuple(map(_DATA_PTR, errs[0])), tuple(map(_DATA_PTR, errs[1]))) not in self._state_tables:
-            return False
-        return BatchedTopK.upload(self, tensors, slot, None, dense)
+    def _state_rows(self, errs, key):
+        """include/gq_dgc.h, state_table: the layout with the scratch for the gradients, u and v."""
+        host = self._layout.clone()
+        base = self._scratch.data_ptr()
+        for s in range(self.nseg):
+            host[s, 0], host[s, 6], host[s, 7] = base + 4 * self.out_off[s], key[0][s], key[1][s]
+        return host, (list(errs[0]), list(errs[1]))
+
+    def _user_state(self, errs):
+        """errs = ([u], [v]) of one user, ef_scale = m: one record with momentum correction (the header carries no error buffers: the
+        select's are the table's).  errs None: plain top-k, no error feedback."""
+        return (None, None, False) if errs is None else (None, self._state_table(errs), True)
+
+    def _compress_args(self, out, ef, table, *how):
+        return (self._batch.compress, (out, ef)) if table is None else (self._batch.record, (out, float(ef)))
 
 
 class BatchedSign(_ItemGroup):
@@ -1961,17 +2016,6 @@ class BatchedSign(_ItemGroup):
         self.random = False
         self._batch = native.SignBatch(self._dev[:self._table_words], self.item_seg, nseg, item)
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None):
-        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense sign.  With `errs`: error feedback
-        in the same launch (t += ef_scale*err before the sign, err = t - sign(t) after it, both in place).
-        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
-        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
-            return False
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None)
-        return True
-
-
 SignCodec.GROUP = BatchedSign
 
 
@@ -1991,6 +2035,8 @@ class BatchedMaurey(_ItemGroup):
     @staticmethod
     def group_key(codec):
         return (codec._rng,)
+
+    EF_DENSE = True
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         ks = [codecs[i].k for i in idxs]
@@ -2028,32 +2074,8 @@ class BatchedMaurey(_ItemGroup):
         torch.index_select(r_all, 0, self._r_gather[0], out=self._r_gather[1])
         return self._r_gather[1]
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None, seed=None):
-        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
-        feedback in the same launches (t += ef_scale*err before the sums, err = t - decoded in the last launch, both in place).
-        draws (given uniforms, see _given_draws): required for gq_rng "reference", taken in any mode when handed in.
-        seed: the device generator's seed for this call.  graph_header, table_current: see _choose_header; dense, rng_slot: see
-        BatchedHSQ.encode."""
-        given = draws is not None and all(i in draws[1] for i in self.idxs)
-        if self.reference_draws and not given:
-            return False
-        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
-            return False
-        ef = ef_scale if errs is not None else None
-        if ef is not None and out is None:
-            out = self._ef_buffer(wire_user.device)
-        counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
-        if given:
-            mode, sd, r = native.RANDOM_GIVEN, 0, self._given_draws(draws)
-        elif seed is not None:
-            mode, sd, r = native.RANDOM_DEVICE, int(seed), None
-        elif self.counter and counter_seed is not None:
-            mode, sd, r = native.RANDOM_DEVICE_COUNTER, counter_seed, None
-        else:
-            mode, sd, r = native.RANDOM_DEVICE, _next_seed() ^ salt, None
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, mode, sd, r, out, ef)
-        return True
+    def _compress_args(self, out, ef, table, *how):
+        return self._batch.compress, self._drawn(*how) + (out, ef)
 
 
 MaureyCodec.GROUP = BatchedMaurey
@@ -2069,6 +2091,7 @@ class BatchedMX(_ItemGroup):
     per tensor, in parameter order) as given draws; "keyed" / a group without pairs: a fresh seed per call."""
 
     align = 4       # the class's default; every instance sets its own from its codecs' dtype (_set_dtype: 2 for bfloat16)
+    WIRE_ALIGN = 16
 
     @staticmethod
     def eligible(codec):
@@ -2123,34 +2146,7 @@ class BatchedMX(_ItemGroup):
             self._r[fd:fd + cd.numel].copy_(r_all[offsets[i]:offsets[i] + cd.numel])
         return self._r
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None, seed=None):
-        """Compress `tensors` into one user's wire; out (the group's dtype [out_floats]): also their dense decode.  With `errs`
-        (float32): error feedback in the same launch (t += ef_scale*err before the rounding, err = t - decoded after it, both in
-        place; a bfloat16 t is stored narrowed, err comes from the unrounded sum).
-        draws (given uniforms, see _given_draws): required for gq_rng "reference", taken in any stochastic mode when handed in.
-        seed: the device generator's seed for this call.  graph_header, table_current: see _choose_header; dense, rng_slot: see
-        BatchedHSQ.encode."""
-        given = self.random and draws is not None and all(i in draws[1] for i in self.idxs)
-        if self.reference_draws and not given:
-            return False
-        if wire_user.data_ptr() % 16:
-            return False
-        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
-            return False
-        counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
-        if not self.random:
-            mode, sd, r = native.RANDOM_OFF, 0, None
-        elif given:
-            mode, sd, r = native.RANDOM_GIVEN, 0, self._given_draws(draws)
-        elif seed is not None:
-            mode, sd, r = native.RANDOM_DEVICE, int(seed), None
-        elif self.counter and counter_seed is not None:
-            mode, sd, r = native.RANDOM_DEVICE_COUNTER, counter_seed, None
-        else:
-            mode, sd, r = native.RANDOM_DEVICE, _next_seed() ^ salt, None
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, mode, sd, r, out, ef_scale if errs is not None else None)
-        return True
+    _compress_args = BatchedMaurey._compress_args
 
 
 MXCodec.GROUP = BatchedMX
@@ -2194,6 +2190,7 @@ class BatchedDrive(_ItemGroup):
     the quantizer's pair in either rotation mode (under 'fixed' nothing ever steps it); a group on its own makes one at step 0."""
 
     stream_base = 0
+    WIRE_ALIGN = 16
 
     @staticmethod
     def eligible(codec):
@@ -2228,22 +2225,10 @@ class BatchedDrive(_ItemGroup):
     def _make_batch(self, nseg, item):
         return native.DriveBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.scale_mode, self.signs)
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None):
-        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error feedback
-        in the same launch (t += ef_scale*err before the rotation, err = t - decoded after it, both in place).
-        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
-        if wire_user.data_ptr() % 16:
-            return False
-        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
-            return False
-        if self.own:
-            stream = 0 if rng_slot is not None else self.stream_base + slot      # (rng_slot: the two-phase re-compress, ONE payload)
-            self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None, self._pair(),
-                         stream)
-        else:
-            self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if errs is not None else None, self.rotation)
-        return True
+    def _compress_args(self, out, ef, table, slot, salt, rng_slot, *draws):
+        if self.own:      # (rng_slot: the two-phase re-compress, ONE payload)
+            return self._batch.compress, (out, ef, self._pair(), 0 if rng_slot is not None else self.stream_base + slot)
+        return self._batch.compress, (out, ef, self.rotation)
 
 
 DriveCodec.GROUP = BatchedDrive
@@ -2283,6 +2268,8 @@ class BatchedThr(_ItemGroup):
     def group_key(codec):
         return (codec.stages, codec.eta)
 
+    EF_DENSE = True
+
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         mine = [codecs[i] for i in idxs]
         nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
@@ -2298,18 +2285,8 @@ class BatchedThr(_ItemGroup):
         self._batch = native.ThrBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self._sums, self._state, self._counts,
                                       self.stages, min(cd.k for cd in mine), min(cd.cap for cd in mine), min(cd.stride for cd in mine))
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None):
-        """Compress `tensors` into one user's wire; out (float32 [out_floats]): also their dense decode.  With `errs`: error
-        feedback in the same launches (t += ef_scale*err before the fit, err = t - decoded in the write launch, both in place).
-        graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
-        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
-            return False
-        ef = ef_scale if errs is not None else None
-        if ef is not None and out is None:
-            out = self._ef_buffer(wire_user.device)
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef, self.eta)
-        return True
+    def _compress_args(self, out, ef, table, *how):
+        return self._batch.compress, (out, ef, self.eta)
 
     def kept_counts(self, wire_user):
         """[(kept, found, eta), ...] of the group's tensors, read from the headers of one user's wire."""
@@ -2384,43 +2361,24 @@ class BatchedPowerSGD(_ItemGroup):
                                        aitem_seg=self._aitem_seg, naitems=aitem, pwork=self._pwork, cpart=self._cpart, flags=self._flags)
         self._state_tables = {}
 
-    def _state_table(self, qs, user):
-        """The device table of these warm starts (include/gq_psgd.h: state), or None when they cannot be addressed."""
-        key = (tuple(map(_DATA_PTR, qs)), int(user))
-        tab = self._state_tables.get(key)
-        if tab is None:
-            dev_index = self.device.index if self.device.index is not None else torch._C._cuda_getDevice()
-            if (len(qs) != self.nseg or not 0 <= int(user) < native.PSGD_MAX_USERS or not all(map(_IS_CONTIGUOUS, qs))
-                    or set(map(_DTYPE_OF, qs)) != _F32_ONLY or set(map(_GET_DEVICE, qs)) != {dev_index} or any(p % 4 for p in key[0])
-                    or any(q.numel() != cd.m * self.rank for q, cd in zip(qs, self.codecs))):
-                return None
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("BatchedPowerSGD: a state table is built by an eager record, not under stream capture")
-            host = torch.tensor([[p, int(user)] for p in key[0]], dtype=torch.int64)
-            tab = self._state_tables[key] = (host.view(-1).to(self.device), list(qs))      # (the buffers stay alive with their table)
-        return tab[0]
+    def _state_key(self, errs):
+        # (no warm starts: a key no table has)
+        return ((), None) if errs is None else ((tuple(map(_DATA_PTR, errs[1])), int(errs[2])), errs[0])
 
-    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, draws=None, graph_header=None, dense=None, defer_reset=None,
-               rng_slot=None, table_current=False, out=None):
-        """errs = (error buffers or None, [Q], user): one record of that user into the wire; out (float32 [out_floats]): also the
-        dense decode.  With error buffers: e <- M + ef_scale * e before the projection and e <- that - decoded after it, in place;
-        the gradients are read only.  graph_header, table_current: see _choose_header; dense: see BatchedHSQ.encode."""
+    def _state_valid(self, errs, key):
+        return (0 <= key[1] < native.PSGD_MAX_USERS and not any(p % 4 for p in key[0])
+                and self._addressable(errs[1], [cd.m * self.rank for cd in self.codecs]))
+
+    def _state_rows(self, errs, key):
+        """include/gq_psgd.h, state: { Q, user } per tensor."""
+        return torch.tensor([[p, key[1]] for p in key[0]], dtype=torch.int64), list(errs[1])
+
+    def _user_state(self, errs):
+        """errs = (error buffers or None, [Q], user): one record of that user.  With error buffers: e <- M + ef_scale * e before the
+        projection and e <- that - decoded after it, in place; the gradients are read only."""
         if errs is None:
             raise ValueError("BatchedPowerSGD.encode: a record needs its user's warm starts, errs = (error buffers or None, [Q], user)")
-        ebufs, qs, user = errs
-        table = self._state_table(qs, user)
-        if table is None or not self._choose_header(tensors, slot, self.align, ebufs, dense, graph_header, table_current):
-            return False
-        self._batch.set_state(table)
-        self._launch(graph_header, defer_reset, self._batch.compress, wire_user, out, ef_scale if ebufs is not None else None)
-        return True
-
-    def upload(self, tensors, slot, errs=None, dense=None):
-        """(in front of an address-free graph's replay: its launches read the state table of the buffers it was captured with --
-        the caller keys its graphs by the warm starts' addresses, and a table, once built, stays where it is)"""
-        if errs is None or (tuple(map(_DATA_PTR, errs[1])), int(errs[2])) not in self._state_tables:
-            return False
-        return _ItemGroup.upload(self, tensors, slot, errs[0], dense)
+        return errs[0], self._state_table(errs), errs[0] is not None
 
 
 PowerSGDCodec.GROUP = BatchedPowerSGD

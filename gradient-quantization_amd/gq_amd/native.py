@@ -20,32 +20,35 @@ class GQNativeError(RuntimeError):
 class Library(object):
     """One native library as this binding expects it: its file (`env` names the variable that overrides the path), the prefix
     of its <prefix>abi_version / <prefix>last_error, the ABI number the binding is written for, every entry point its header
-    declares and the result types that are not int.  `handle` caches the loaded library (_load)."""
+    declares and the result types that are not int.  `handle` caches the loaded library (load)."""
 
     def __init__(self, name, env, prefix, abi, exports, restypes=()):
         self.name, self.prefix, self.abi, self.exports, self.restypes = name, prefix, abi, exports, tuple(restypes)
         self.path = os.environ.get(env) or os.path.join(_PKG_DIR, name)
         self.handle = None
 
+    def load(self):
+        """The library; fails loudly if it was not built (python gradient-quantization_amd/build.py) or is stale."""
+        if self.handle is None:
+            if not os.path.exists(self.path):
+                raise GQNativeError("%s not found at %s -- build it with `python gradient-quantization_amd/build.py` "
+                                    "(there is no CPU fallback)" % (self.name, self.path))
+            L = ctypes.CDLL(self.path)
+            abi_version = getattr(L, self.prefix + "abi_version")
+            abi_version.restype = ctypes.c_int
+            getattr(L, self.prefix + "last_error").restype = ctypes.c_char_p
+            for name, restype in self.restypes:
+                getattr(L, name).restype = restype
+            for name in self.exports:
+                getattr(L, name)  # AttributeError if the library is stale
+            if abi_version() != self.abi:
+                raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it" % (self.path, abi_version(), self.abi))
+            self.handle = L
+        return self.handle
+
 
 def _load(d):
-    """The library of description `d`; fails loudly if it was not built (python gradient-quantization_amd/build.py) or is stale."""
-    if d.handle is None:
-        if not os.path.exists(d.path):
-            raise GQNativeError("%s not found at %s -- build it with `python gradient-quantization_amd/build.py` "
-                                "(there is no CPU fallback)" % (d.name, d.path))
-        L = ctypes.CDLL(d.path)
-        abi_version = getattr(L, d.prefix + "abi_version")
-        abi_version.restype = ctypes.c_int
-        getattr(L, d.prefix + "last_error").restype = ctypes.c_char_p
-        for name, restype in d.restypes:
-            getattr(L, name).restype = restype
-        for name in d.exports:
-            getattr(L, name)  # AttributeError if the library is stale
-        if abi_version() != d.abi:
-            raise GQNativeError("%s has ABI version %d, this binding is written for %d: rebuild it" % (d.path, abi_version(), d.abi))
-        d.handle = L
-    return d.handle
+    return d.load()
 
 
 GQ_MAX_PARTIALS = 1024
@@ -71,12 +74,7 @@ ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_HIP = -1, -2, -3      # GQ_ERR_* of includ
 
 HSQ_LIBRARY = Library("libgq_hsq.so", "GQ_LIB_PATH", "gq_", ABI_VERSION, EXPORTS,
                       [("gq_hsq_workspace_bytes", ctypes.c_size_t), ("gq_launch_plan_destroy", None)])
-LIB_PATH = HSQ_LIBRARY.path
-
-
-def lib():
-    """Load libgq_hsq.so; fail loudly if it was not built (python gradient-quantization_amd/build.py)."""
-    return HSQ_LIBRARY.handle or _load(HSQ_LIBRARY)
+LIB_PATH, lib = HSQ_LIBRARY.path, HSQ_LIBRARY.load
 
 
 CALLS = [0]      # entry-point calls that went through _check (each is one launch, or two for the wide QSGD compress): bench.py's `launches`
@@ -86,7 +84,7 @@ def _check(rc, what, owner=HSQ_LIBRARY):
     """owner: the library the entry point belongs to (the failure's text is in its own *_last_error)."""
     CALLS[0] += 1
     if rc != 0:
-        raise GQNativeError("%s failed (%d): %s" % (what, rc, getattr(_load(owner), owner.prefix + "last_error")().decode()))
+        raise GQNativeError("%s failed (%d): %s" % (what, rc, getattr(owner.load(), owner.prefix + "last_error")().decode()))
 
 
 def _dev_ptr(t, dtype=None, name="tensor"):
@@ -609,18 +607,42 @@ def qsgd_decode_sum(norm, signs, levels, d, n_bit, out, R=1):
     _check(rc, "gq_qsgd_decode_sum")
 
 
-# ---- the item-table libraries: one descriptor base for top-k, sign, Maurey and MX -----------------------------------------------
+# ---- the item-table libraries: one descriptor base, one compress and one decode for all eleven ---------------------------------
+def _rotation_ptr(rotation):
+    """The { seed, step } pair of a stepped launch: a device int64 [1, 2] tensor (include/gq_drive.h: SIGNS, STEPPED)."""
+    if not (isinstance(rotation, torch.Tensor) and rotation.dtype == torch.int64 and tuple(rotation.shape) == (1, 2)):
+        raise TypeError("rotation must be a device int64 [1, 2] tensor, the { seed, step } pair")
+    return _dev_ptr(rotation, torch.int64, "rotation")
+
+
+def _stream_arg(stream):
+    """The stream of a *_streams launch (include/gq_drive.h: SIGNS, PER STREAM): an int that fits int32, passed by value.  A
+    negative one goes through: the library refuses it."""
+    if isinstance(stream, bool) or not isinstance(stream, int):
+        raise TypeError("stream must be an int, got %r" % (stream,))
+    if not -2 ** 31 <= stream < 2 ** 31:
+        raise ValueError("stream %d does not fit int32" % stream)
+    return ctypes.c_int32(stream)
+
+
+def _draw_args(random_mode, r, seed):
+    """What stands between `wire` and `ef_scale` in a compress that draws (gq_maurey.h, gq_mx.h): the mode, the given draws, the seed."""
+    return (ctypes.c_int(random_mode), _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
+            ctypes.c_uint64(seed & (2 ** 64 - 1)))
+
+
 class _ItemBatch(_Tables):
     """A descriptor over a segment table and an item table (item_seg names the tensor of every item) -- gq_topk_batch,
-    gq_sign_batch, gq_maurey_batch -- and its <prefix>decode_sum_batched launch.  A subclass names its library (LIBRARY) and
-    its ctypes struct (STRUCT), hands its scratch buffers to this constructor and has a compress of its own."""
+    gq_sign_batch, gq_maurey_batch ... -- and its two launches, <prefix>compress_batched and <prefix>decode_sum_batched.  A subclass
+    names its library (LIBRARY) and its ctypes struct (STRUCT) and hands its scratch buffers to this constructor; where its
+    compress takes more than (wire, ef_scale, out), its own `compress` hands _compress the arguments that stand between."""
 
     LIBRARY = STRUCT = None
     dtype, _suffix = torch.float32, ""      # the type of `out` and the suffix of the entry points that take it (MXBatch: _MX_SUFFIX)
 
     def __init__(self, seg_table, item_seg, nseg, nitems, scratch=(), **sizes):
         """scratch: ((field of the struct, int32 / float tensor or None, its dtype), ...); sizes: further integer fields."""
-        self.L = _load(self.LIBRARY)
+        self.L = self.LIBRARY.load()
         self.keep = (seg_table, item_seg) + tuple(t for _, t, _ in scratch)
         self.s = self.STRUCT(struct_bytes=ctypes.sizeof(self.STRUCT), nseg=int(nseg), nitems=int(nitems),
                              seg_table=_dev_ptr(seg_table, torch.int64, "seg_table").value,
@@ -629,6 +651,7 @@ class _ItemBatch(_Tables):
             if t is not None:
                 setattr(self.s, name, _dev_ptr(t, dtype, name).value)
         self.ref = ctypes.byref(self.s)
+        self._compress_name = self.LIBRARY.prefix + "compress_batched" + self._suffix
         self._decode_name = self.LIBRARY.prefix + "decode_sum_batched" + self._suffix
         self._decode = getattr(self.L, self._decode_name)
 
@@ -636,23 +659,37 @@ class _ItemBatch(_Tables):
         """A decode-only descriptor of a run of the tensors (a split / pipelined exchange)."""
         return type(self)(seg_table, item_seg, nseg, nitems)
 
+    def _entry(self, name, rotation, stream):
+        """Which of an entry point's forms a launch takes, and what it takes first: `name` (the descriptor), with a rotation --
+        the { seed, step } pair of DriveBatch / EdenBatch -- `name`_stepped (the descriptor, the pair), with a stream as well (an
+        int, needs the pair) `name`_streams (the descriptor, the pair, the stream by value).  -> (its name, the function, those)."""
+        first = (self.ref,)
+        if stream is not None:
+            name, first = name + "_streams", (self.ref, _rotation_ptr(rotation), _stream_arg(stream))
+        elif rotation is not None:
+            name, first = name + "_stepped", (self.ref, _rotation_ptr(rotation))
+        return name, getattr(self.L, name), first
+
+    def _compress(self, wire, out, ef_scale, lead=(), rotation=None, stream=None):
+        """The one compress call: (descriptor, [rotation, [stream,]] wire, *lead, ef_scale or NaN, out or null, stream handle)."""
+        name, entry, first = self._entry(self._compress_name, rotation, stream)
+        _check(entry(*first, _dev_ptr(wire, torch.uint8, "wire"), *lead, ctypes.c_float(_NAN if ef_scale is None else ef_scale),
+                     _dev_ptr(out, self.dtype, "out") if out is not None else ctypes.c_void_p(0), _stream()), name, self.LIBRARY)
+
+    def compress(self, wire, out=None, ef_scale=None):
+        """out: the dense decoded tensors (the batch's dtype, at the table's out offsets); ef_scale given: error feedback in the same
+        launches (seg_table[:, 7] = error buffers; the sparsifiers need out for it)."""
+        self._compress(wire, out, ef_scale)
+
     def decode(self, gathered, R, out, plain=False, rotation=None, first_stream=None):
         """gathered: [R, bytes] uint8, rows contiguous (the table's wire offsets count from the start of a row), any row stride.
         rotation (DriveBatch / EdenBatch only): the { seed, step } pair -- the <prefix>decode_sum_batched_stepped launch; with
         first_stream (an int, needs the pair) the <prefix>decode_sum_batched_streams launch: payload r under stream first_stream + r."""
         assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.stride(1) == 1
         stride = int(gathered.stride(0)) if R > 1 else int(gathered.shape[1])
-        args = (_dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R), _dev_ptr(out, self.dtype, "out"),
-                ctypes.c_int(1 if plain else 0), _stream())
-        if first_stream is not None:
-            name = self._decode_name + "_streams"
-            rc = getattr(self.L, name)(self.ref, _rotation_ptr(rotation), _stream_arg(first_stream), *args)
-        elif rotation is None:
-            name, rc = self._decode_name, self._decode(self.ref, *args)
-        else:
-            name = self._decode_name + "_stepped"
-            rc = getattr(self.L, name)(self.ref, _rotation_ptr(rotation), *args)
-        _check(rc, name, self.LIBRARY)
+        name, entry, first = self._entry(self._decode_name, rotation, first_stream)
+        _check(entry(*first, _dev_ptr(gathered[0], torch.uint8, "gathered"), ctypes.c_int64(stride), ctypes.c_int(R),
+                     _dev_ptr(out, self.dtype, "out"), ctypes.c_int(1 if plain else 0), _stream()), name, self.LIBRARY)
 
 
 # ---- top-k sparsification: libgq_topk.so (include/gq_topk.h) ----------------------------------------------------------
@@ -662,17 +699,16 @@ TOPK_CHUNK = 4096           # GQ_TOPK_CHUNK: elements per item
 TOPK_HIST_BINS = 2048       # GQ_TOPK_HIST_BINS: histogram words per tensor
 
 TOPK_LIBRARY = Library("libgq_topk.so", "GQ_TOPK_LIB_PATH", "gq_topk_", TOPK_ABI_VERSION, TOPK_EXPORTS)
-TOPK_LIB_PATH = TOPK_LIBRARY.path
-
-
-def topk_lib():
-    return TOPK_LIBRARY.handle or _load(TOPK_LIBRARY)
+TOPK_LIB_PATH, topk_lib = TOPK_LIBRARY.path, TOPK_LIBRARY.load
 
 
 class _TopKBatchStruct(ctypes.Structure):     # gq_topk_batch (include/gq_topk.h)
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
                 ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("hist", ctypes.c_void_p), ("state", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_TopKBatchStruct) == 72      # (csrc/topk.hip asserts the same of gq_topk_batch)
 
 
 class TopKBatch(_ItemBatch):
@@ -686,30 +722,20 @@ class TopKBatch(_ItemBatch):
         _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems,
                             (("hist", hist, torch.int32), ("state", state, torch.int32), ("counts", counts, torch.int32)))
 
-    def compress(self, wire, out=None, ef_scale=None):
-        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
-        launches (seg_table[:, 7] = error buffers; needs out)."""
-        rc = self.L.gq_topk_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
-                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_topk_compress_batched", TOPK_LIBRARY)
-
-
 # ---- momentum correction around the top-k select: libgq_dgc.so (include/gq_dgc.h) --------------------------------------------
 DGC_ABI_VERSION = 1
 DGC_EXPORTS = ["gq_dgc_abi_version", "gq_dgc_last_error", "gq_dgc_accumulate_batched", "gq_dgc_mask_batched"]
 
 DGC_LIBRARY = Library("libgq_dgc.so", "GQ_DGC_LIB_PATH", "gq_dgc_", DGC_ABI_VERSION, DGC_EXPORTS)
-DGC_LIB_PATH = DGC_LIBRARY.path
-
-
-def dgc_lib():
-    return DGC_LIBRARY.handle or _load(DGC_LIBRARY)
+DGC_LIB_PATH, dgc_lib = DGC_LIBRARY.path, DGC_LIBRARY.load
 
 
 class _DGCBatchStruct(ctypes.Structure):      # gq_dgc_batch (include/gq_dgc.h)
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
                 ("grad_table", ctypes.c_void_p), ("state_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(_DGCBatchStruct) == 40      # (csrc/dgc.hip asserts the same of gq_dgc_batch)
 
 
 class DGCBatch(TopKBatch):
@@ -765,11 +791,7 @@ SIGN_EXPORTS = ["gq_sign_abi_version", "gq_sign_last_error", "gq_sign_compress_b
 SIGN_ITEM_BYTES = 4096      # GQ_SIGN_ITEM_BYTES: wire bytes (16384 elements) per item
 
 SIGN_LIBRARY = Library("libgq_sign.so", "GQ_SIGN_LIB_PATH", "gq_sign_", SIGN_ABI_VERSION, SIGN_EXPORTS)
-SIGN_LIB_PATH = SIGN_LIBRARY.path
-
-
-def sign_lib():
-    return SIGN_LIBRARY.handle or _load(SIGN_LIBRARY)
+SIGN_LIB_PATH, sign_lib = SIGN_LIBRARY.path, SIGN_LIBRARY.load
 
 
 class _SignBatchStruct(ctypes.Structure):     # gq_sign_batch (include/gq_sign.h)
@@ -778,31 +800,21 @@ class _SignBatchStruct(ctypes.Structure):     # gq_sign_batch (include/gq_sign.h
                 ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+assert ctypes.sizeof(_SignBatchStruct) == 48      # (csrc/sign.hip asserts the same of gq_sign_batch)
+
+
 class SignBatch(_ItemBatch):
     """The multi-tensor sign launches: gq_sign_compress_batched (2-bit codes, + the dense signs and the residual) and
     gq_sign_decode_sum_batched.  No scratch: both are one launch over the segment table."""
 
     LIBRARY, STRUCT = SIGN_LIBRARY, _SignBatchStruct
 
-    def compress(self, wire, out=None, ef_scale=None):
-        """out: the dense sign(w) (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
-        (seg_table[:, 7] = error buffers)."""
-        rc = self.L.gq_sign_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
-                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_sign_compress_batched", SIGN_LIBRARY)
-
-
 # ---- the ProbabilisticVectorCompressor's multi-tensor encode: libgq_pvq.so (include/gq_pvq.h) ------------------------------
 PVQ_ABI_VERSION = 1
 PVQ_EXPORTS = ["gq_pvq_abi_version", "gq_pvq_last_error", "gq_pvq_batched_serves", "gq_pvq_encode_batched"]
 
 PVQ_LIBRARY = Library("libgq_pvq.so", "GQ_PVQ_LIB_PATH", "gq_pvq_", PVQ_ABI_VERSION, PVQ_EXPORTS)
-PVQ_LIB_PATH = PVQ_LIBRARY.path
-
-
-def pvq_lib():
-    return PVQ_LIBRARY.handle or _load(PVQ_LIBRARY)
+PVQ_LIB_PATH, pvq_lib = PVQ_LIBRARY.path, PVQ_LIBRARY.load
 
 
 def pvq_batched_serves(d, K, code_dtype):
@@ -813,6 +825,9 @@ def pvq_batched_serves(d, K, code_dtype):
 
 class _PVQBatchStruct(ctypes.Structure):      # gq_pvq_batch (include/gq_pvq.h)
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("hsq", ctypes.c_void_p), ("c_dagger", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(_PVQBatchStruct) == 24      # (csrc/pvq_batched.hip asserts the same of gq_pvq_batch)
 
 
 class PVQBatch(HSQBatch):
@@ -847,11 +862,7 @@ RQ_EXPORTS = ["gq_rq_abi_version", "gq_rq_last_error", "gq_rq_batched_serves", "
 RQ_MEAN, RQ_PLAIN, RQ_ERROR = 0, 1, 2      # GQ_RQ_* of include/gq_rq.h
 
 RQ_LIBRARY = Library("libgq_rq.so", "GQ_RQ_LIB_PATH", "gq_rq_", RQ_ABI_VERSION, RQ_EXPORTS)
-RQ_LIB_PATH = RQ_LIBRARY.path
-
-
-def rq_lib():
-    return RQ_LIBRARY.handle or _load(RQ_LIBRARY)
+RQ_LIB_PATH, rq_lib = RQ_LIBRARY.path, RQ_LIBRARY.load
 
 
 def rq_batched_serves(d, K, code_dtype):
@@ -863,6 +874,9 @@ def rq_batched_serves(d, K, code_dtype):
 class _RQBatchStruct(ctypes.Structure):      # gq_rq_batch (include/gq_rq.h)
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("reserved", ctypes.c_int32), ("stage1", ctypes.c_void_p), ("stage2", ctypes.c_void_p),
                 ("c_dagger", ctypes.c_void_p), ("level2_words", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(_RQBatchStruct) == 40      # (csrc/rq_batched.hip asserts the same of gq_rq_batch)
 
 
 class RQBatch(object):
@@ -929,11 +943,7 @@ MAUREY_CHUNK = 4096         # GQ_MAUREY_CHUNK: elements per item
 MAUREY_HEADER_BYTES = 16    # GQ_MAUREY_HEADER_BYTES: scale + 12 zero bytes in front of a section's words
 
 MAUREY_LIBRARY = Library("libgq_maurey.so", "GQ_MAUREY_LIB_PATH", "gq_maurey_", MAUREY_ABI_VERSION, MAUREY_EXPORTS)
-MAUREY_LIB_PATH = MAUREY_LIBRARY.path
-
-
-def maurey_lib():
-    return MAUREY_LIBRARY.handle or _load(MAUREY_LIBRARY)
+MAUREY_LIB_PATH, maurey_lib = MAUREY_LIBRARY.path, MAUREY_LIBRARY.load
 
 
 class _MaureyBatchStruct(ctypes.Structure):   # gq_maurey_batch (include/gq_maurey.h)
@@ -941,6 +951,9 @@ class _MaureyBatchStruct(ctypes.Structure):   # gq_maurey_batch (include/gq_maur
                 ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("sums", ctypes.c_void_p), ("totals", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p), ("draw_item", ctypes.c_void_p), ("bucket", ctypes.c_void_p),
                 ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_MaureyBatchStruct) == 96      # (csrc/maurey.hip asserts the same of gq_maurey_batch)
 
 
 class MaureyBatch(_ItemBatch):
@@ -960,14 +973,8 @@ class MaureyBatch(_ItemBatch):
         """random_mode: RANDOM_GIVEN (r: float32 [ndraws], tensor s reads r[first draw + j]), RANDOM_DEVICE (seed) or
         RANDOM_DEVICE_COUNTER (seed = the address of a { seed, step } pair).  out: the dense decoded tensors (float32, at the
         table's out offsets); ef_scale given: error feedback in the same launches (seg_table[:, 7] = error buffers; needs out)."""
-        if r is not None:
-            assert r.numel() >= self.s.ndraws
-        rc = self.L.gq_maurey_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
-                                               _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
-                                               ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                               ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                               _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_maurey_compress_batched", MAUREY_LIBRARY)
+        assert r is None or r.numel() >= self.s.ndraws
+        self._compress(wire, out, ef_scale, _draw_args(random_mode, r, seed))
 
 
 # ---- block-scaled small floats (MXFP4 / MXFP6 / MXFP8): libgq_mx.so (include/gq_mx.h) ---------------------------------------------------
@@ -994,17 +1001,16 @@ def _mx_suffix(dtype, who):
         raise TypeError("%s: the kernels take float32 or bfloat16 tensors, got %s" % (who, dtype))
 
 MX_LIBRARY = Library("libgq_mx.so", "GQ_MX_LIB_PATH", "gq_mx_", MX_ABI_VERSION, MX_EXPORTS)
-MX_LIB_PATH = MX_LIBRARY.path
-
-
-def mx_lib():
-    return MX_LIBRARY.handle or _load(MX_LIBRARY)
+MX_LIB_PATH, mx_lib = MX_LIBRARY.path, MX_LIBRARY.load
 
 
 class _MXBatchStruct(ctypes.Structure):       # gq_mx_batch (include/gq_mx.h)
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
                 ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
                 ("ndense", ctypes.c_int32), ("format", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_MXBatchStruct) == 48      # (csrc/mx.hip asserts the same of gq_mx_batch)
 
 
 class MXBatch(_ItemBatch):
@@ -1021,8 +1027,6 @@ class MXBatch(_ItemBatch):
         """fields: what a subclass's descriptor holds behind gq_mx_batch's own fields."""
         self.dtype, self._suffix = dtype, _mx_suffix(dtype, type(self).__name__)
         _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, format=int(fmt), **fields)
-        self._compress_name = self.LIBRARY.prefix + "compress_batched" + self._suffix
-        self._compress = getattr(self.L, self._compress_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
         return type(self)(seg_table, item_seg, nseg, nitems, self.s.format, self.dtype)
@@ -1032,12 +1036,7 @@ class MXBatch(_ItemBatch):
         r[first draw + i]), RANDOM_DEVICE (seed) or RANDOM_DEVICE_COUNTER (seed = the address of a { seed, step } pair).
         out: the dense decoded tensors (the batch's dtype, at the table's out offsets); ef_scale given: error feedback in the same
         launch (seg_table[:, 7] = error buffers, float32 whatever the dtype)."""
-        rc = self._compress(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
-                            _dev_ptr(r, torch.float32, "r") if r is not None else ctypes.c_void_p(0),
-                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                            _dev_ptr(out, self.dtype, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, self._compress_name, self.LIBRARY)
+        self._compress(wire, out, ef_scale, _draw_args(random_mode, r, seed))
 
 
 # ---- the same behind a randomized Hadamard rotation: libgq_mxr.so (include/gq_mxr.h) ----------------------------------------------
@@ -1047,15 +1046,14 @@ MXR_EXPORTS = ["gq_mxr_abi_version", "gq_mxr_last_error", "gq_mxr_compress_batch
 MXR_BLOCK = 256             # GQ_MXR_BLOCK: elements of a rotation block
 
 MXR_LIBRARY = Library("libgq_mxr.so", "GQ_MXR_LIB_PATH", "gq_mxr_", MXR_ABI_VERSION, MXR_EXPORTS)
-MXR_LIB_PATH = MXR_LIBRARY.path
-
-
-def mxr_lib():
-    return MXR_LIBRARY.handle or _load(MXR_LIBRARY)
+MXR_LIB_PATH, mxr_lib = MXR_LIBRARY.path, MXR_LIBRARY.load
 
 
 class _MXRBatchStruct(ctypes.Structure):      # gq_mxr_batch (include/gq_mxr.h): gq_mx_batch's fields, then the sign words
     _fields_ = _MXBatchStruct._fields_ + [("signs", ctypes.c_uint64 * 4)]
+
+
+assert ctypes.sizeof(_MXRBatchStruct) == 80      # (csrc/mxr.hip asserts the same of gq_mxr_batch)
 
 
 class MXRBatch(MXBatch):
@@ -1085,44 +1083,7 @@ DRIVE_UNBIASED, DRIVE_MSE = 0, 1      # GQ_DRIVE_UNBIASED / GQ_DRIVE_MSE
 DRIVE_SCALES = {"unbiased": DRIVE_UNBIASED, "mse": DRIVE_MSE}
 
 DRIVE_LIBRARY = Library("libgq_drive.so", "GQ_DRIVE_LIB_PATH", "gq_drive_", DRIVE_ABI_VERSION, DRIVE_EXPORTS)
-DRIVE_LIB_PATH = DRIVE_LIBRARY.path
-
-
-def drive_lib():
-    return DRIVE_LIBRARY.handle or _load(DRIVE_LIBRARY)
-
-
-def _rotation_ptr(rotation):
-    """The { seed, step } pair of a stepped launch: a device int64 [1, 2] tensor (include/gq_drive.h: SIGNS, STEPPED)."""
-    if not (isinstance(rotation, torch.Tensor) and rotation.dtype == torch.int64 and tuple(rotation.shape) == (1, 2)):
-        raise TypeError("rotation must be a device int64 [1, 2] tensor, the { seed, step } pair")
-    return _dev_ptr(rotation, torch.int64, "rotation")
-
-
-def _stream_arg(stream):
-    """The stream of a *_streams launch (include/gq_drive.h: SIGNS, PER STREAM): an int that fits int32, passed by value.  A
-    negative one goes through: the library refuses it."""
-    if isinstance(stream, bool) or not isinstance(stream, int):
-        raise TypeError("stream must be an int, got %r" % (stream,))
-    if not -2 ** 31 <= stream < 2 ** 31:
-        raise ValueError("stream %d does not fit int32" % stream)
-    return ctypes.c_int32(stream)
-
-
-def _rotated_compress(batch, name, wire, out, ef_scale, rotation, stream=None):
-    """_RotatedBatch.compress (DriveBatch, EdenBatch): the entry point `name`, with a rotation pair `name`_stepped, with a pair and a
-    stream `name`_streams."""
-    args = (_dev_ptr(wire, torch.uint8, "wire"), ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-    if stream is not None:
-        name += "_streams"
-        rc = getattr(batch.L, name)(batch.ref, _rotation_ptr(rotation), _stream_arg(stream), *args)
-    elif rotation is None:
-        rc = getattr(batch.L, name)(batch.ref, *args)
-    else:
-        name += "_stepped"
-        rc = getattr(batch.L, name)(batch.ref, _rotation_ptr(rotation), *args)
-    _check(rc, name, batch.LIBRARY)
+DRIVE_LIB_PATH, drive_lib = DRIVE_LIBRARY.path, DRIVE_LIBRARY.load
 
 
 class _DriveBatchStruct(ctypes.Structure):    # gq_drive_batch (include/gq_drive.h): gq_mxr_batch's layout, scale_mode for format
@@ -1131,12 +1092,15 @@ class _DriveBatchStruct(ctypes.Structure):    # gq_drive_batch (include/gq_drive
                 ("ndense", ctypes.c_int32), ("scale_mode", ctypes.c_int32), ("signs", ctypes.c_uint64 * 4)]
 
 
+assert ctypes.sizeof(_DriveBatchStruct) == 80      # (csrc/drive.hip asserts the same of gq_drive_batch)
+
+
 class _RotatedBatch(_ItemBatch):
     """What DriveBatch and EdenBatch share: the four sign words last in the descriptor, a decode-only part() under the same
-    fields, and compress on <COMPRESS>, <COMPRESS>_stepped or <COMPRESS>_streams.  A subclass states LIBRARY, STRUCT, COMPRESS and,
-    in the order of its constructor's arguments, the descriptor's FIELDS in front of the sign words."""
+    fields, and a compress that takes the rotation pair and the stream (_entry: the plain, *_stepped or *_streams form).  A subclass
+    states LIBRARY, STRUCT and, in the order of its constructor's arguments, the descriptor's FIELDS in front of the sign words."""
 
-    COMPRESS, FIELDS = None, ()
+    FIELDS = ()
 
     def _bind(self, seg_table, item_seg, nseg, nitems, signs, **fields):
         signs = tuple(int(w) & (2 ** 64 - 1) for w in signs)
@@ -1152,7 +1116,7 @@ class _RotatedBatch(_ItemBatch):
     def compress(self, wire, out=None, ef_scale=None, rotation=None, stream=None):
         """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same launch
         (seg_table[:, 7] = error buffers); rotation, stream: see DriveBatch."""
-        _rotated_compress(self, self.COMPRESS, wire, out, ef_scale, rotation, stream)
+        self._compress(wire, out, ef_scale, (), rotation, stream)
 
 
 class DriveBatch(_RotatedBatch):
@@ -1164,7 +1128,7 @@ class DriveBatch(_RotatedBatch):
     first_stream= beside the pair (SIGNS, PER STREAM): the *_streams entry points -- compress under that stream's words, payload r
     of the decode-mean through its own inverse rotation under stream first_stream + r, the mean in the gradient's domain."""
 
-    LIBRARY, STRUCT, COMPRESS, FIELDS = DRIVE_LIBRARY, _DriveBatchStruct, "gq_drive_compress_batched", ("scale_mode",)
+    LIBRARY, STRUCT, FIELDS = DRIVE_LIBRARY, _DriveBatchStruct, ("scale_mode",)
 
     def __init__(self, seg_table, item_seg, nseg, nitems, scale_mode=DRIVE_UNBIASED, signs=(0, 0, 0, 0)):
         self._bind(seg_table, item_seg, nseg, nitems, signs, scale_mode=scale_mode)
@@ -1181,11 +1145,7 @@ EDEN_SCALES = {"unbiased": EDEN_UNBIASED, "mse": EDEN_MSE}
 EDEN_BITS = (2, 3, 4)       # GQ_EDEN_MIN_BITS ... GQ_EDEN_MAX_BITS (one bit is libgq_drive.so)
 
 EDEN_LIBRARY = Library("libgq_eden.so", "GQ_EDEN_LIB_PATH", "gq_eden_", EDEN_ABI_VERSION, EDEN_EXPORTS)
-EDEN_LIB_PATH = EDEN_LIBRARY.path
-
-
-def eden_lib():
-    return EDEN_LIBRARY.handle or _load(EDEN_LIBRARY)
+EDEN_LIB_PATH, eden_lib = EDEN_LIBRARY.path, EDEN_LIBRARY.load
 
 
 class _EdenBatchStruct(ctypes.Structure):     # gq_eden_batch (include/gq_eden.h): gq_drive_batch's fields plus bits, the sign words last
@@ -1195,6 +1155,9 @@ class _EdenBatchStruct(ctypes.Structure):     # gq_eden_batch (include/gq_eden.h
                 ("signs", ctypes.c_uint64 * 4)]
 
 
+assert ctypes.sizeof(_EdenBatchStruct) == 88      # (csrc/eden.hip asserts the same of gq_eden_batch)
+
+
 class EdenBatch(_RotatedBatch):
     """The two launches of libgq_eden.so: gq_eden_compress_batched (b-bit Lloyd-Max codes of the rotated blocks and one f32 scale per
     block, + the dense decode and the residual) and gq_eden_decode_sum_batched (the mean in the rotated domain, one inverse
@@ -1202,7 +1165,7 @@ class EdenBatch(_RotatedBatch):
     words (gq_mxr.h's).  rotation= (and stream= / first_stream=) on compress / decode: DriveBatch's, on gq_eden_*_stepped
     (gq_eden_*_streams)."""
 
-    LIBRARY, STRUCT, COMPRESS, FIELDS = EDEN_LIBRARY, _EdenBatchStruct, "gq_eden_compress_batched", ("bits", "scale_mode")
+    LIBRARY, STRUCT, FIELDS = EDEN_LIBRARY, _EdenBatchStruct, ("bits", "scale_mode")
 
     def __init__(self, seg_table, item_seg, nseg, nitems, bits=4, scale_mode=EDEN_UNBIASED, signs=(0, 0, 0, 0)):
         self._bind(seg_table, item_seg, nseg, nitems, signs, bits=bits, scale_mode=scale_mode)
@@ -1217,11 +1180,7 @@ THR_MAX_STAGES = 8          # GQ_THR_MAX_STAGES
 THR_NO_INDEX = 0xffffffff   # GQ_THR_NO_INDEX: the index of a slot that holds no pair
 
 THR_LIBRARY = Library("libgq_thr.so", "GQ_THR_LIB_PATH", "gq_thr_", THR_ABI_VERSION, THR_EXPORTS)
-THR_LIB_PATH = THR_LIBRARY.path
-
-
-def thr_lib():
-    return THR_LIBRARY.handle or _load(THR_LIBRARY)
+THR_LIB_PATH, thr_lib = THR_LIBRARY.path, THR_LIBRARY.load
 
 
 class _ThrBatchStruct(ctypes.Structure):      # gq_thr_batch (include/gq_thr.h)
@@ -1250,10 +1209,7 @@ class ThrBatch(_ItemBatch):
     def compress(self, wire, out=None, ef_scale=None, eta=0.0):
         """eta: the threshold of fixed mode (stages = 0; not read otherwise).  out: the dense decoded tensors (float32, at the
         table's out offsets); ef_scale given: error feedback in the same launches (seg_table[:, 7] = error buffers; needs out)."""
-        rc = self.L.gq_thr_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_float(eta),
-                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_thr_compress_batched", THR_LIBRARY)
+        self._compress(wire, out, ef_scale, (ctypes.c_float(eta),))
 
 
 # ---- sparse ternary compression: libgq_stc.so (include/gq_stc.h) -----------------------------------------------------------------
@@ -1264,11 +1220,7 @@ STC_HIST_BINS = 2048        # GQ_STC_HIST_BINS: histogram words per tensor
 STC_HEADER_BYTES = 16       # GQ_STC_HEADER_BYTES: k, bits(mu), nitems, 0 in front of a section's starts
 
 STC_LIBRARY = Library("libgq_stc.so", "GQ_STC_LIB_PATH", "gq_stc_", STC_ABI_VERSION, STC_EXPORTS)
-STC_LIB_PATH = STC_LIBRARY.path
-
-
-def stc_lib():
-    return STC_LIBRARY.handle or _load(STC_LIBRARY)
+STC_LIB_PATH, stc_lib = STC_LIBRARY.path, STC_LIBRARY.load
 
 
 class _STCBatchStruct(ctypes.Structure):      # gq_stc_batch (include/gq_stc.h)
@@ -1294,14 +1246,6 @@ class STCBatch(_ItemBatch):
                             (("hist", hist, torch.int32), ("state", state, torch.int32), ("counts", counts, torch.int32),
                              ("sums", sums, torch.float64)))
 
-    def compress(self, wire, out=None, ef_scale=None):
-        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
-        launches (seg_table[:, 7] = error buffers; needs out)."""
-        rc = self.L.gq_stc_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
-                                            ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                            _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_stc_compress_batched", STC_LIBRARY)
-
 
 # ---- low-rank compression (PowerSGD, rank 1 / 2 / 4): libgq_psgd.so (include/gq_psgd.h) ------------------------------------------
 PSGD_ABI_VERSION = 1
@@ -1313,11 +1257,7 @@ PSGD_HEADER_BYTES = 16      # GQ_PSGD_HEADER_BYTES: n, m, r, 0 in front of a sec
 PSGD_MAX_USERS = 4096       # GQ_PSGD_MAX_USERS: user < 4096 in the key of Q0; the two-phase server's warm start is user 4095
 
 PSGD_LIBRARY = Library("libgq_psgd.so", "GQ_PSGD_LIB_PATH", "gq_psgd_", PSGD_ABI_VERSION, PSGD_EXPORTS)
-PSGD_LIB_PATH = PSGD_LIBRARY.path
-
-
-def psgd_lib():
-    return PSGD_LIBRARY.handle or _load(PSGD_LIBRARY)
+PSGD_LIB_PATH, psgd_lib = PSGD_LIBRARY.path, PSGD_LIBRARY.load
 
 
 class _PSGDBatchStruct(ctypes.Structure):      # gq_psgd_batch (include/gq_psgd.h)
@@ -1355,14 +1295,6 @@ class PSGDBatch(_ItemBatch):
         self.keep_state = state_table
         self.s.state = _dev_ptr(state_table, torch.int64, "state").value if state_table is not None else None
 
-    def compress(self, wire, out=None, ef_scale=None):
-        """out: the dense decoded tensors (float32, at the table's out offsets); ef_scale given: error feedback in the same
-        launches (seg_table[:, 7] = error buffers)."""
-        rc = self.L.gq_psgd_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"),
-                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale),
-                                             _dev_ptr(out, torch.float32, "out") if out is not None else ctypes.c_void_p(0), _stream())
-        _check(rc, "gq_psgd_compress_batched", PSGD_LIBRARY)
-
 
 # ---- Lloyd k-means for training codebooks: libgq_kmeans.so (include/gq_kmeans.h) ---------------------------------------------
 KMEANS_ABI_VERSION = 1
@@ -1375,11 +1307,7 @@ KMEANS_THREADS, KMEANS_BLOCKS_PER_CU = 256, 2
 
 KMEANS_LIBRARY = Library("libgq_kmeans.so", "GQ_KMEANS_LIB_PATH", "gq_kmeans_", KMEANS_ABI_VERSION, KMEANS_EXPORTS,
                          [("gq_kmeans_workspace_bytes", ctypes.c_size_t)])
-KMEANS_LIB_PATH = KMEANS_LIBRARY.path
-
-
-def kmeans_lib():
-    return KMEANS_LIBRARY.handle or _load(KMEANS_LIBRARY)
+KMEANS_LIB_PATH, kmeans_lib = KMEANS_LIBRARY.path, KMEANS_LIBRARY.load
 
 
 def kmeans_workspace_bytes(K, d):
