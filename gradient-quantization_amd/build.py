@@ -28,6 +28,7 @@ LIBS = {
     os.path.join(HERE, "libgq_eden.so"): ["eden.hip"],            # the rotated 2- / 3- / 4-bit compressor (EDEN): Lloyd-Max codes of the rotated block and one f32 scale, on the same rotation
     os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select (top-k's compaction and decode-mean: csrc/sparse_kernels.hpp)
     os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select (the same kernels: csrc/sparse_kernels.hpp), one magnitude per tensor, a 16-bit word per kept element
+    os.path.join(HERE, "libgq_sketch.so"): ["sketch.hip"],        # count sketch: a wire that adds across users; a workgroup per chunk of a window's item list, staged through LDS, no atomics; the decode-mean recovers top-k of the mean with top-k's select (csrc/sparse_kernels.hpp)
     os.path.join(HERE, "libgq_psgd.so"): ["psgd.hip"],            # low-rank compression (PowerSGD, rank 1 / 2 / 4): project, orthogonalise, back-project, fold, residual; the decode-mean of the factors
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],    # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean

@@ -17,7 +17,8 @@ device memory, through gq_amd.native).
     BatchedHSQ / BatchedPVQ / BatchedResidual / BatchedQSGD / BatchedTopK / BatchedDGC / BatchedSign / BatchedMaurey / BatchedMX / BatchedMXR /
     STCCodec                   SparseTernaryCompressor: a 16-byte header (k, the magnitude), a uint32 start per item of 4,096 elements, then k 16-bit words
     PowerSGDCodec              PowerSGDCompressor: a 16-byte header (n, m, r), then the factors Ph (n x r) and Q' (m x r) as f32
-    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC / BatchedPowerSGD
+    SketchCodec                CountSketchCompressor: a 16-byte header (n, rows, windows), then rows x windows x 4,096 f32 cells that add across users
+    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC / BatchedPowerSGD / BatchedSketch
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -31,7 +32,7 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           PowerSGDCompressor, QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
@@ -669,6 +670,36 @@ class ThrCodec(_SparseCodec):
         w = wire_user[off:off + 12].cpu().numpy()
         kept, found = (int(x) for x in w[:8].view("<u4"))
         return kept, found, float(w[8:12].view("<f4")[0])
+
+
+def sketch_section_bytes(numel, rows=3, sketch_cr=32):
+    """Bytes of one tensor's section of the sketch wire (include/gq_sketch.h): a 16-byte header, then rows * nwin * 4,096 f32 cells,
+    nwin = max(1, ceil(items / (sketch_cr * rows))); a tensor with 2 * rows * nwin > items travels as its 4 * numel bytes."""
+    items, nwin = CountSketchCompressor.layout(numel, rows, sketch_cr)
+    if 2 * rows * nwin > items:
+        return 4 * numel
+    return native.SKETCH_HEADER_BYTES + 4 * native.SKETCH_CHUNK * rows * nwin
+
+
+class SketchCodec(_SparseCodec):
+    """CountSketchCompressor on the HIP kernels (libgq_sketch.so).  Wire per tensor: a 16-byte header { n, rows, nwin, 0 }, then
+    rows * nwin * 4,096 f32 cells -- sketch_section_bytes.  Every call is a one-tensor BatchedSketch; roundtrip / encode_decode_into
+    return the decode of this one payload.  `E`: the error table of --sketch-ef (float32 [rows * nwin * 4096], the quantizer's, read
+    and stepped by every decode-mean that is not `plain`), or None."""
+
+    def __init__(self, compressor, numel, shape):
+        if not compressor.compresses or numel != compressor.size:
+            raise ValueError("SketchCodec: a tensor of %d elements is not sketched at rows = %d, sketch_cr = %d"
+                             % (numel, compressor.rows, compressor.sketch_cr))
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.k, self.rows, self.seed, self.nwin, self.items = compressor.k, compressor.rows, compressor.seed, compressor.nwin, compressor.items
+        self.cells = self.rows * self.nwin * native.SKETCH_CHUNK
+        self.nbytes = sketch_section_bytes(numel, compressor.rows, compressor.sketch_cr)
+        self.E = None
+
+    def header(self, wire_user, off):
+        """(n, rows, nwin) of this tensor's section of one user's wire: a read of three words, with a synchronisation."""
+        return tuple(int(x) for x in wire_user[off:off + 12].cpu().numpy().view("<u4"))
 
 
 def stc_section_bytes(numel, cr):
@@ -2296,6 +2327,76 @@ class BatchedThr(_ItemGroup):
 ThrCodec.GROUP = BatchedThr
 
 
+class BatchedSketch(_ItemGroup):
+    """All CountSketchCompressor tensors of one (rows, seed) in ONE gq_sketch_compress_batched sequence (the sketch launch over the
+    units, the fold launch over the windows -- include/gq_sketch.h) and ONE gq_sketch_decode_sum_batched sequence.  The window lists
+    depend on the seed and the layout alone: built once here (gq_sketch_build_lists) and uploaded with the other tables.  No draws:
+    every launch replays from a HIP graph.  The error tables of --sketch-ef are the codecs' (SketchCodec.E, all set or none)."""
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is SketchCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.rows, codec.seed)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        import numpy as np
+        mine = [codecs[i] for i in idxs]
+        self.rows, self.seed = mine[0].rows, mine[0].seed
+        assert all((cd.rows, cd.seed) == (self.rows, self.seed) for cd in mine)
+        CH, UN = native.SKETCH_CHUNK, native.SKETCH_CHUNK_ITEMS
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense, lambda cd: cd.items,
+                                      {4: [cd.k for cd in mine], 6: [cd.nwin for cd in mine]}, 1)
+        self.random = False
+        lay, win_tab, unit_tab, lists, W, U, L = [], [], [], [], 0, 0, 0
+        for s, cd in enumerate(mine):
+            lst, starts = native.sketch_build_lists(self.seed, self.rows, cd.items, cd.nwin)
+            cnt = np.diff(starts)
+            chunks = -(-cnt // UN)
+            first = U + np.concatenate([[0], np.cumsum(chunks)[:-1]])
+            win_tab.append(np.stack([np.full_like(cnt, s), first, chunks, np.zeros_like(cnt)], 1))
+            win = np.repeat(np.arange(len(cnt)), chunks)
+            c = np.arange(int(chunks.sum())) - np.repeat(first - U, chunks)
+            unit_tab.append(np.stack([W + win, L + starts[win] + UN * c, np.minimum(UN, cnt[win] - UN * c), np.zeros_like(win)], 1))
+            lay.append(W)
+            lists.append(lst)
+            W, U, L = W + len(cnt), U + int(chunks.sum()), L + len(lst)
+        self.nwindows, self.nunits = W, U
+        as_dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).view(-1).to(device)
+        t = {"lay": as_dev(np.array(lay, dtype=np.int64), torch.int64), "win_tab": as_dev(np.concatenate(win_tab), torch.int32),
+             "unit_tab": as_dev(np.concatenate(unit_tab), torch.int32),
+             "list": as_dev(np.concatenate(lists).view(np.int32), torch.int32),
+             # scratch (include/gq_sketch.h): written before it is read, but for the histograms, which every decode leaves zero again
+             "part": torch.empty(U * CH, dtype=torch.float32, device=device), "table": torch.empty(W * CH, dtype=torch.float32, device=device),
+             "est": torch.empty(self.out_floats, dtype=torch.float32, device=device),
+             "hist": torch.zeros(nseg * native.SKETCH_HIST_BINS, dtype=torch.int32, device=device),
+             "state": torch.empty(nseg * 4, dtype=torch.int32, device=device), "counts": torch.empty(item * 2, dtype=torch.int32, device=device)}
+        dec = self._layout.clone()
+        dec[:, 0] = t["est"].data_ptr() + 4 * dec[:, 5]
+        t["dec_table"] = dec.view(-1).to(device)
+        tables = [cd.E for cd in mine]
+        if any(e is not None for e in tables):
+            if not all(e is not None and e.dtype == torch.float32 and e.is_contiguous() and e.numel() == cd.cells and e.device == t["est"].device
+                       for e, cd in zip(tables, mine)):
+                raise ValueError("BatchedSketch: the error tables must be contiguous float32 tensors of rows * nwin * 4096 cells on the "
+                                 "group's device, one for every tensor of the group")
+            t["etab"] = torch.tensor([e.data_ptr() for e in tables], dtype=torch.int64).to(device)
+        self._tables, self._errors = t, tables
+        self._batch = native.SketchBatch(self._dev[:self._table_words], self.item_seg, nseg, item, rows=self.rows, seed=self.seed,
+                                         nwindows=W, nunits=U, tables=t)
+
+    def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, **kw):
+        if errs is not None:
+            raise ValueError("BatchedSketch.encode: no per-user error feedback (the sketch accumulates its error on the decoding side: "
+                             "sketch_ef)")
+        return _ItemGroup.encode(self, tensors, wire_user, slot, salt, **kw)
+
+
+SketchCodec.GROUP = BatchedSketch
+
+
 class BatchedSTC(BatchedTopK):
     """All SparseTernaryCompressor tensors in ONE gq_stc_compress_batched sequence (top-k's eight launches: the count launch also sums
     the kept magnitudes per item, the scan launch folds them into mu, the write launch compacts 16-bit words -- include/gq_stc.h)
@@ -2409,6 +2510,9 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return ThrCodec(compressor, numel, shape)
     if isinstance(compressor, SparseTernaryCompressor):
         return STCCodec(compressor, numel, shape)
+    if isinstance(compressor, CountSketchCompressor):
+        # (too few items for two per cell window: uncompressed, as the low-rank compressor's small tensors)
+        return SketchCodec(compressor, numel, shape) if compressor.compresses else DenseCodec(compressor, numel, shape)
     if isinstance(compressor, PowerSGDCompressor):
         # (a vector, a matrix thinner than the rank, factors no smaller than the tensor: uncompressed, whatever its size)
         return PowerSGDCodec(compressor, numel, shape) if compressor.compresses else DenseCodec(compressor, numel, shape)

@@ -932,7 +932,64 @@ class PowerSGDCompressor(object):
         return signature
 
 
+class CountSketchCompressor(object):
+    """A count sketch (Sketched-SGD, Ivkin et al. 2019; FetchSGD, Rothchild et al. 2020; no counterpart in the reference's catalogue):
+    the one wire here that ADDS across users.  sketch_rows r = 1, 3 or 5 rows of nwin = max(1, ceil(items / (sketch_cr * r))) windows
+    of 4,096 cells, items = ceil(size / 4096); a hierarchical hash of (sketch_seed, row, item, position) -- include/gq_sketch.h defines
+    the hash, the order of every sum and the recovery to the bit.  The decode recovers top-k of the MEAN, k = size // cr, from the
+    cell-wise mean of the users' sketches.  A tensor with 2 * r * nwin > items travels uncompressed (`compresses`).  compress returns
+    the decode of this one tensor's own sketch and decompress is the identity, as for the sparsifiers' device paths.  HIP kernels only
+    (libgq_sketch.so): a float32 tensor on the device."""
+
+    def __init__(self, size, shape, args):
+        cr = getattr(args, "cr", None)
+        if isinstance(cr, bool) or not isinstance(cr, int) or cr < 1:
+            raise ValueError("cr must be a positive integer, got %r" % (cr,))
+        rows = getattr(args, "sketch_rows", None)
+        rows = 3 if rows is None else rows
+        if isinstance(rows, bool) or rows not in (1, 3, 5):
+            raise ValueError("sketch_rows must be 1, 3 or 5, got %r" % (rows,))
+        C = getattr(args, "sketch_cr", None)
+        C = 32 if C is None else C
+        if isinstance(C, bool) or not isinstance(C, int) or C < 1:
+            raise ValueError("sketch_cr must be a positive integer, got %r" % (C,))
+        seed = getattr(args, "sketch_seed", None)
+        seed = 0 if seed is None else seed
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError("sketch_seed must be an integer in [0, 2^64), got %r" % (seed,))
+        self.size, self.shape, self.cr, self.rows, self.sketch_cr, self.seed = size, tuple(shape), cr, rows, C, seed
+        self.ef = bool(getattr(args, "sketch_ef", False))
+        self.k = size // cr
+        self.items, self.nwin = self.layout(size, rows, C)
+
+    @staticmethod
+    def layout(size, rows, C):
+        """(items, nwin) of a tensor (include/gq_sketch.h)."""
+        items = -(-size // 4096)
+        return items, max(1, -(-items // (C * rows)))
+
+    @property
+    def compresses(self):
+        """Whether a tensor of this size is sketched at all (otherwise it travels as it is)."""
+        return 2 * self.rows * self.nwin <= self.items and self.size < 2 ** 31
+
+    def compress(self, vec):
+        from .codecs import SketchCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("CountSketchCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), "
+                            "got %s on %s" % (vec.dtype, vec.device))
+        if vec.numel() != self.size or not self.compresses:
+            return vec.clone()
+        codec = self.__dict__.get("_codec")
+        if codec is None:
+            codec = self._codec = SketchCodec(self, self.size, (self.size,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
            "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor",
-           "PowerSGDCompressor"]
+           "PowerSGDCompressor", "CountSketchCompressor"]

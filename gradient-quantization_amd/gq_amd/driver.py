@@ -32,7 +32,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           PowerSGDCompressor, QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
@@ -50,6 +50,7 @@ quantizer_choices = {          # main.py:20-26
     'eden': EdenCompressor,                    # the rotated 2- / 3- / 4-bit compressor (--eden-bits, --eden-scale, --eden-seed): bits + 0.125, likewise
     'threshold': ThresholdSparsificationCompressor,      # what exceeds a fitted or a given threshold (--thr-stages, --thr-value, --thr-cap-percent, --thr-fit-stride, --cr), likewise
     'stc': SparseTernaryCompressor,            # sparse ternary compression: top-k's kept set (--cr) at one magnitude, a 16-bit word per kept element, likewise
+    'sketch': CountSketchCompressor,           # a count sketch (--sketch-rows, --sketch-cr, --sketch-seed, --sketch-ef, --cr): the one wire that adds across users; top-k of the mean is recovered once, likewise
     'powersgd': PowerSGDCompressor,            # low-rank compression (--psgd-rank, --psgd-seed): one power iteration per record from a warm start, the two factors on the wire, likewise
 }
 
@@ -220,6 +221,16 @@ def build_parser():
                         'factors would not shrink, travel uncompressed)')
     p.add_argument('--psgd-seed', dest='psgd_seed', type=int, default=0,
                    help="--quantizer powersgd: the seed of the warm starts' first values (per parameter and user, from the counter hash)")
+    p.add_argument('--sketch-rows', dest='sketch_rows', type=int, default=3, choices=[1, 3, 5],
+                   help='--quantizer sketch: rows of the count sketch (the estimate of an element is the median over the rows)')
+    p.add_argument('--sketch-cr', dest='sketch_cr', type=int, default=32,
+                   help='--quantizer sketch: elements per cell, about: the sketch of a tensor holds numel / sketch_cr cells (tensors too '
+                        'small for two items per window travel uncompressed); --cr sets how many elements the decode keeps')
+    p.add_argument('--sketch-seed', dest='sketch_seed', type=int, default=0,
+                   help='--quantizer sketch: the seed of the hash (every user and every rank must use the same: sketches add under one hash)')
+    p.add_argument('--sketch-ef', dest='sketch_ef', action='store_true',
+                   help="--quantizer sketch: FetchSGD's error accumulation -- what the decode does not keep stays in a table per "
+                        "parameter on the decoding side and is added to the next mean (not --ef, which keeps a residual per user)")
     p.add_argument('--thr-stages', dest='thr_stages', type=int, default=3, choices=list(range(9)),
                    help='--quantizer threshold: passes of the threshold fit (a count-adaptive multi-stage exponential fit of the tail of '
                         '|g|, aiming at numel // cr kept elements); 0: no fit, the fixed threshold --thr-value')

@@ -1247,6 +1247,62 @@ class STCBatch(_ItemBatch):
                              ("sums", sums, torch.float64)))
 
 
+# ---- count sketch, a wire that adds across users: libgq_sketch.so (include/gq_sketch.h) -----------------------------------------
+SKETCH_ABI_VERSION = 1
+SKETCH_EXPORTS = ["gq_sketch_abi_version", "gq_sketch_last_error", "gq_sketch_build_lists", "gq_sketch_compress_batched",
+                  "gq_sketch_decode_sum_batched"]
+SKETCH_CHUNK = 4096         # GQ_SKETCH_CHUNK: elements per item, cells per window
+SKETCH_CHUNK_ITEMS = 8      # GQ_SKETCH_CHUNK_ITEMS: list entries per chunk
+SKETCH_HEADER_BYTES = 16    # GQ_SKETCH_HEADER_BYTES: n, r, nwin, 0 in front of a section's cells
+SKETCH_HIST_BINS = 2048     # GQ_SKETCH_HIST_BINS: histogram words per tensor
+
+SKETCH_LIBRARY = Library("libgq_sketch.so", "GQ_SKETCH_LIB_PATH", "gq_sketch_", SKETCH_ABI_VERSION, SKETCH_EXPORTS)
+SKETCH_LIB_PATH, sketch_lib = SKETCH_LIBRARY.path, SKETCH_LIBRARY.load
+
+
+def sketch_build_lists(seed, rows, items, nwin):
+    """The window lists of one tensor (gq_sketch_build_lists, host memory only): (list uint32 [rows * items], starts int64
+    [rows * nwin + 1]) as numpy arrays."""
+    import numpy as np
+    lst, starts = np.empty(rows * items, dtype=np.uint32), np.empty(rows * nwin + 1, dtype=np.int64)
+    _check(sketch_lib().gq_sketch_build_lists(ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.c_int(rows), ctypes.c_int64(items),
+                                              ctypes.c_int64(nwin), lst.ctypes.data_as(ctypes.c_void_p),
+                                              starts.ctypes.data_as(ctypes.c_void_p)), "gq_sketch_build_lists", SKETCH_LIBRARY)
+    return lst, starts
+
+
+class _SketchBatchStruct(ctypes.Structure):      # gq_sketch_batch (include/gq_sketch.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("lay", ctypes.c_void_p), ("win_tab", ctypes.c_void_p),
+                ("unit_tab", ctypes.c_void_p), ("list", ctypes.c_void_p), ("part", ctypes.c_void_p), ("table", ctypes.c_void_p),
+                ("est", ctypes.c_void_p), ("dec_table", ctypes.c_void_p), ("hist", ctypes.c_void_p), ("state", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p), ("etab", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32),
+                ("rows", ctypes.c_int32), ("nwindows", ctypes.c_int64), ("nunits", ctypes.c_int64), ("seed", ctypes.c_uint64)]
+
+
+assert ctypes.sizeof(_SketchBatchStruct) == 168      # (csrc/sketch.hip asserts the same of gq_sketch_batch)
+
+
+class SketchBatch(_ItemBatch):
+    """The launches of libgq_sketch.so: gq_sketch_compress_batched (the sketch launch over the units, the fold launch over the windows)
+    and gq_sketch_decode_sum_batched (sum, estimate, top-k's select on the estimates, store, and with `etab` the error accumulation).
+    `tables`: {field: tensor} of everything the descriptor names beside the segment and item tables (include/gq_sketch.h)."""
+
+    LIBRARY, STRUCT = SKETCH_LIBRARY, _SketchBatchStruct
+    _DTYPES = {"lay": torch.int64, "win_tab": torch.int32, "unit_tab": torch.int32, "list": torch.int32, "part": torch.float32,
+               "table": torch.float32, "est": torch.float32, "dec_table": torch.int64, "hist": torch.int32, "state": torch.int32,
+               "counts": torch.int32, "etab": torch.int64}
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, rows=3, seed=0, nwindows=0, nunits=0, tables=None):
+        tables = tables or {}
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, tuple((f, tables.get(f), dt) for f, dt in self._DTYPES.items()),
+                            rows=int(rows), seed=int(seed) & (2 ** 64 - 1), nwindows=int(nwindows), nunits=int(nunits))
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        raise GQNativeError("the sketch compressor's decode-mean runs over the whole group: it takes no split or pipelined exchange "
+                            "(set GQ_EXCHANGE=allgather or direct)")
+
+
 # ---- low-rank compression (PowerSGD, rank 1 / 2 / 4): libgq_psgd.so (include/gq_psgd.h) ------------------------------------------
 PSGD_ABI_VERSION = 1
 PSGD_EXPORTS = ["gq_psgd_abi_version", "gq_psgd_last_error", "gq_psgd_compress_batched", "gq_psgd_decode_sum_batched"]

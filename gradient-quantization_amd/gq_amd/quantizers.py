@@ -31,7 +31,7 @@ import warnings
 import torch
 
 from . import exchange, native
-from .compressors import (DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, PowerSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
+from .compressors import (CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, PowerSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
                           TopKSparsificationCompressor, _next_seed, shared_seeds)
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
@@ -48,7 +48,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
     BatchedDGC, BatchedDrive, BatchedEden, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
-    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec, BatchedPowerSGD, PowerSGDCodec,
+    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec, BatchedPowerSGD, PowerSGDCodec, BatchedSketch, SketchCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -200,6 +200,24 @@ class PSQuantizer(object):
             if int(args.num_users) >= PowerSGDCodec.SERVER_USER:
                 raise ValueError("the low-rank compressor keeps a warm start per user for fewer than %d users, got %d"
                                  % (PowerSGDCodec.SERVER_USER, int(args.num_users)))
+        self.sketch_ef = False
+        if isinstance(Compressor, type) and issubclass(Compressor, CountSketchCompressor):
+            # (include/gq_sketch.h: float32 tensors only; the error accumulates in the sketch, on the decoding side)
+            odd = sorted(set(str(p.dtype) for p in self.parameters if p.dtype != torch.float32))
+            if odd:
+                raise ValueError("the sketch compressor takes float32 parameters only (its kernels read and write float32 "
+                                 "gradients), got %s" % ", ".join(odd))
+            if self.error_feedback:
+                raise ValueError("ef is not available with the sketch compressor: it keeps no per-user residual; its error accumulates in "
+                                 "the sketch on the decoding side (sketch_ef)")
+            if self.two_phase:
+                raise ValueError("two_phase is not available with the sketch compressor: the mean it decodes is sparse already, and a "
+                                 "second sketch of it would be decoded against other tensors' collisions")
+            self.sketch_ef = bool(getattr(args, "sketch_ef", False))
+            if exchange.configured_mode() not in ("allgather", "direct"):
+                raise ValueError("the sketch compressor's decode-mean runs over the whole gathered wire: GQ_EXCHANGE must be allgather "
+                                 "or direct, got %r" % (exchange.configured_mode(),))
+        self._sketch_checked = set()
         factory = codec_factory or quantizer_codec_factory
         self.aggregate_fma = aggregate_fma(args)     # opt-in fused accumulation of the decode-mean (R >= 2 only)
         self.wire_levels = wire_levels_mode(args, _dist_world(process_group)[0])      # "bytes" | "packed6" (6-bit levels where the configuration allows)
@@ -229,6 +247,10 @@ class PSQuantizer(object):
             if self.dgc_m is not None and isinstance(comp, TopKSparsificationCompressor):
                 param.dgc_u = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
                 param.dgc_v = [torch.zeros(param.shape, dtype=torch.float32, device=param.device) for _ in range(args.num_users)]
+            if self.sketch_ef and isinstance(self.codecs[-1], SketchCodec):
+                # FetchSGD's error accumulation (include/gq_sketch.h: E): one table per sketched parameter, zero at the start, the
+                # same on every rank (every rank decodes the same gathered wire); sketch_errors() / set_sketch_errors() for a resume.
+                self.codecs[-1].E = torch.zeros(self.codecs[-1].cells, dtype=torch.float32, device=param.device)
             if isinstance(self.codecs[-1], PowerSGDCodec):
                 # the warm starts (include/gq_psgd.h: Q, m x r), per parameter and user like param.dgc_u: param.psgd_q[user], and
                 # the server's for the two-phase re-compress of the mean, like param.server_error.  They start at Q0 of (seed,
@@ -239,6 +261,7 @@ class PSQuantizer(object):
                 if self.two_phase:
                     param.psgd_server_q = codec.warm_start(i, codec.SERVER_USER, param.device)
         self._psgd = any(isinstance(c, PowerSGDCodec) for c in self.codecs)
+        self._sketch = any(isinstance(c, SketchCodec) for c in self.codecs)
         # wire layout of one user: 16-byte aligned sections for the compressed tensors first, then ONE
         # packed region with the raw f32 of all identity-compressed (<= 1000 element) tensors
         self.offsets = [0] * self.num_layers
@@ -276,7 +299,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC, BatchedPowerSGD):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC, BatchedPowerSGD, BatchedSketch):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -382,6 +405,9 @@ class PSQuantizer(object):
         if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
             raise ValueError("momentum_correction is not available with the sparse ternary compressor: momentum factor masking is built "
                              "on the top-k wire (--quantizer topk)")
+        if isinstance(Compressor, type) and issubclass(Compressor, CountSketchCompressor):
+            raise ValueError("momentum_correction is not available with the sketch compressor: momentum factor masking is built "
+                             "on the top-k wire (--quantizer topk)")
         if isinstance(Compressor, type) and issubclass(Compressor, PowerSGDCompressor):
             raise ValueError("momentum_correction is not available with the low-rank compressor: momentum factor masking is built "
                              "on the top-k wire (--quantizer topk)")
@@ -443,6 +469,50 @@ class PSQuantizer(object):
                 raise ValueError("set_warm_starts: parameter %d: %d users of float32 %r expected%s" % (i, len(p.psgd_q), tuple(p.psgd_q[0].shape), ", and the server's" if srv is not None else ""))
             for q, s in pairs:
                 q.copy_(s)
+
+    def sketch_errors(self):
+        """The sketch compressor's error tables (sketch_ef) for a checkpoint: {parameter index: E}, copies on the host ({} without
+        them).  A read of device memory: it synchronises."""
+        return {i: c.E.detach().cpu().clone() for i, c in self._sketch_tables()}
+
+    def set_sketch_errors(self, state):
+        """Restore what sketch_errors() returned (a resume).  The values are copied INTO the quantizer's tables, whose addresses the
+        launches' tables and the captured graphs hold; ValueError for a state of another model or configuration."""
+        tables = dict(self._sketch_tables())
+        mine = set(tables)
+        if set(state) != mine:
+            raise ValueError("set_sketch_errors: the state names the parameters %r, this quantizer's error tables are %r" % (sorted(state), sorted(mine)))
+        for i in sorted(mine):
+            e, t = tables[i].E, state[i]
+            if t is None or tuple(t.shape) != tuple(e.shape) or t.dtype != torch.float32:
+                raise ValueError("set_sketch_errors: parameter %d: float32 %r expected" % (i, tuple(e.shape)))
+        for i in sorted(mine):
+            tables[i].E.copy_(state[i])
+
+    def _sketch_tables(self):
+        """(parameter index, codec) of every sketched parameter that has an error table (sketch_ef)."""
+        return [(i, c) for i, c in enumerate(self.codecs) if isinstance(c, SketchCodec) and c.E is not None]
+
+    def _check_sketch_headers(self, gathered, pending):
+        """The sketch compressor: the payloads of one mean add cell by cell, so they must be sketches of ONE layout.  The first
+        apply() of every (users, gathered wire) reads the { n, rows, nwin } headers of every payload's sections (include/gq_sketch.h)
+        -- one small copy to the host, with a synchronisation -- and refuses payloads that differ from this quantizer's layout.  (The
+        seed is not in the header: a user with another seed is NOT detected.)"""
+        key = (int(gathered.shape[0]), gathered.data_ptr())
+        if key in self._sketch_checked:
+            return
+        for pnd in pending:
+            pnd.wait()
+        at = [(i, c) for i, c in enumerate(self.codecs) if isinstance(c, SketchCodec)]
+        words = torch.stack([gathered[:, self.offsets[i]:self.offsets[i] + 12] for i, _ in at], 1).cpu().numpy().view("<u4")
+        for k, (i, c) in enumerate(at):
+            for r in range(words.shape[0]):
+                got = tuple(int(x) for x in words[r, k])
+                if got != (c.numel, c.rows, c.nwin):
+                    raise ValueError("the sketch compressor: payload %d of this mean carries a sketch of (n, rows, windows) = %r for "
+                                     "parameter %d, this quantizer's is %r: the users of one mean must share the shapes, the rows and "
+                                     "the cell ratio (their sketches add cell by cell)" % (r, got, i, (c.numel, c.rows, c.nwin)))
+        self._sketch_checked.add(key)
 
     def _record_dgc_single(self, i, grad, wire, user):
         """The per-tensor route of a record with momentum correction: the same three launches over a one-tensor group, for a
@@ -1254,6 +1324,8 @@ class PSQuantizer(object):
             gathered, pending = ex.start(self.exchange_mode, self.recorded, self.cut, cuts=self.cuts)
         else:
             gathered, pending = self._wire[:self.recorded], ()
+        if self._sketch:
+            self._check_sketch_headers(gathered, pending)
         decoded = None
         graph_key = None
         fused, self._fused = self._fused, None
@@ -1340,6 +1412,9 @@ class RingQuantizer(PSQuantizer):
         if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
             raise ValueError("the sparse ternary compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
                              "itself, and its wire carries one magnitude for the whole kept set")
+        if isinstance(Compressor, type) and issubclass(Compressor, CountSketchCompressor):
+            raise ValueError("the sketch compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
+                             "and a sketch's decode keeps the heavy hitters only")
         if isinstance(Compressor, type) and issubclass(Compressor, PowerSGDCompressor):
             raise ValueError("the low-rank compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
                              "itself, and its warm start belongs to one user's gradients, not to the running sum of the users before it")
