@@ -238,6 +238,8 @@ static int check_qsgd(const gq_qsgd_batch *b, const char *what) {
     if (!b->seg_table || !b->item_seg) return fail(GQ_ERR_INVALID_ARG, "%s: null pointer in the descriptor", what);
     if (b->wide && !b->norm_bits) return fail(GQ_ERR_INVALID_ARG, "%s: wide buckets need norm_bits", what);
     if (b->ndense < 0 || (b->ndense > 0 && !b->dense_table)) return fail(GQ_ERR_INVALID_ARG, "%s: ndense = %d without a dense_table", what, b->ndense);
+    if (b->tensor_type != GQ_QSGD_TENSOR_F32 && b->tensor_type != GQ_QSGD_TENSOR_BF16)
+        return fail(GQ_ERR_INVALID_ARG, "%s: tensor_type %d is neither GQ_QSGD_TENSOR_F32 nor GQ_QSGD_TENSOR_BF16", what, b->tensor_type);
     return GQ_OK;
 }
 }  // namespace gq
@@ -254,6 +256,13 @@ GQ_API int gq_qsgd_compress_batched(const gq_qsgd_batch *b, uint8_t *wire, int r
         return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_compress_batched: GQ_RANDOM_DEVICE_COUNTER takes the address of two device words as `seed`");
     const int ef = isnan(ef_scale) ? 0 : 1;
     const float scale = ef ? ef_scale : 0.0f;
+    if (b->tensor_type == GQ_QSGD_TENSOR_BF16) {      // bf16 gradients (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE): the bf16 kernels
+        if (b->wide)
+            return gqi_qsgd_wide_compress_bf16(b->seg_table, b->item_seg, b->nseg, b->nitems, b->n_bit, random_mode, seed, ef, scale,
+                                               b->norm_bits, wire, b->dense_table, b->ndense, stream);
+        return gqi_qsgd_compress_batched_bf16(b->seg_table, b->item_seg, b->nseg, b->nitems, b->n_bit, random_mode, seed, ef, scale, wire,
+                                              b->dense_table, b->ndense, b->bucket_hint, stream);
+    }
     if (b->wide)
         return gqi_qsgd_wide_compress(b->seg_table, b->item_seg, b->nseg, b->nitems, b->n_bit, random_mode, seed, ef, scale,
                                       b->norm_bits, wire, b->dense_table, b->ndense, stream);
@@ -267,6 +276,14 @@ static int qsgd_decode_sum_batched(const gq_qsgd_batch *b, const uint8_t *gather
     if (tail_taken) *tail_taken = 0;
     const int rc = check_qsgd(b, "gq_qsgd_decode_sum_batched");
     if (rc != GQ_OK) return rc;
+    if (b->tensor_type == GQ_QSGD_TENSOR_BF16) {      // `out` holds bf16: the bf16 kernels, every one of which takes the tail
+        uint16_t *out16 = reinterpret_cast<uint16_t *>(out);
+        if (b->wide)
+            return gqi_qsgd_wide_decode_sum_bf16(b->seg_table, b->item_seg, b->nseg, b->nitems, b->n_bit, b->bits, gathered,
+                                                 user_stride_bytes, R, out16, plain, tail, tail_taken, stream);
+        return gqi_qsgd_decode_sum_batched_bf16(b->seg_table, b->item_seg, b->nseg, b->nitems, b->n_bit, b->bits, gathered,
+                                                user_stride_bytes, R, out16, plain, tail, tail_taken, b->bucket_hint, stream);
+    }
     if (b->wide)
         return gqi_qsgd_wide_decode_sum(b->seg_table, b->item_seg, b->nseg, b->nitems, b->n_bit, b->bits, gathered,
                                         user_stride_bytes, R, out, plain, tail, tail_taken, stream);

@@ -563,3 +563,288 @@ GQ_INTERNAL int gqi_qsgd_decode_sum_batched(const int64_t *seg_table, const int3
     GQ_CHECK_LAUNCH("gq_qsgd_decode_sum_batched");
     return GQ_OK;
 }
+
+// ---- bf16 gradients and bf16 `out` (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE) ----------------------------------------------------
+// The same wire from the same arithmetic: a bucket's elements are widened (bits << 16) behind the load, and everything up to the
+// stores is the float32 kernels' (norm, quotient window, draws, levels, signs, packing).  What changes is how a bucket lies on its
+// lanes.  A unit of 8 elements is ONE 16-byte load here, so a lane takes TWO ADJACENT units -- elements [16 c0, 16 c0 + 16) -- and
+// a bucket d / 16 lanes (the launcher halves the float32 kernel's count): a lane keeps the float32 kernel's 32 bytes of gradient
+// in flight, a wave covers twice the buckets, the norm's butterfly is one step shorter, and a lane's codes are one contiguous
+// 2 * BITS bytes.  Under error feedback the lane reads 64 contiguous bytes of the float32 residual, stores narrow(w) as two
+// 16-byte stores and err = w - decode(code), from the UNROUNDED w, as four.  Buckets wider than 16 LPB elements are walked twice, a
+// unit per lane and trip; a width that is no multiple of 8, or a view that does not start on 16 bytes, takes the element-pair
+// walk with 2-byte accesses (qsgd_compress_pair_walk_bf16).  The segment table comes from LDS when it fits, else from memory.
+namespace gq {
+template <bool EF, int BITS, int LPB>
+__global__ __launch_bounds__(QB_THREADS) void qsgd_compress_batched_bf16_kernel(
+    const int64_t *__restrict__ seg_table, const int32_t *__restrict__ bucket_seg, int nseg, int64_t nbuckets, int n_bit,
+    int random_mode, uint64_t seed, float ef_scale, uint8_t *__restrict__ wire, const int64_t *__restrict__ dense_table, int ndense) {
+    resolve_seed(random_mode, seed);
+    copy_dense_segments_bf16(dense_table, ndense, wire);
+    __shared__ int64_t s_seg[QB_LDS_SEGS * 8];
+    const bool lds = nseg <= QB_LDS_SEGS;
+    if (lds) {
+        for (int i = threadIdx.x; i < nseg * 8; i += QB_THREADS) s_seg[i] = seg_table[i];
+        __syncthreads();
+    }
+    constexpr int BPW = 64 / LPB;   // buckets per wave
+    const int lane = threadIdx.x & 63, sub = lane / LPB, c0 = lane & (LPB - 1);
+    const int64_t nw = (int64_t)gridDim.x * (QB_THREADS / 64);
+    const float s = (float)(1 << n_bit), smax = s - 1.0f, inv_s = 1.0f / s;
+    const bool draws = random_mode >= GQ_RANDOM_DEVICE;
+    const int64_t nquads = (nbuckets + BPW - 1) / BPW;
+    int64_t qd = (int64_t)blockIdx.x * (QB_THREADS / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int seg_next = (qd < nquads && BPW * qd + sub < nbuckets) ? bucket_seg[BPW * qd + sub] : 0;
+    for (; qd < nquads; qd += nw) {
+        const int64_t b = BPW * qd + sub;
+        const bool live = b < nbuckets;
+        const int seg = seg_next;
+        {
+            const int64_t bn = BPW * (qd + nw) + sub;
+            seg_next = (qd + nw < nquads && bn < nbuckets) ? bucket_seg[bn] : 0;   // the next item's tensor
+        }
+        if (!live) continue;
+        int64_t rec[8];
+        if (lds) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) rec[i] = s_seg[8 * seg + i];
+        } else {
+            typedef const int64_t __attribute__((address_space(1))) *grec_ptr;
+            const grec_ptr gr = (grec_ptr)(seg_table + 8 * (int64_t)seg);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) rec[i] = gr[i];
+        }
+        const int d = (int)rec[1];
+        const int64_t lb = b - rec[2];
+        const gh_ptr v = (gh_ptr)(uintptr_t)rec[0] + lb * d;
+        const gf_ptr err = (EF && rec[7]) ? (gf_ptr)(uintptr_t)rec[7] + lb * d : (gf_ptr)0;
+        float *const norm_dst = reinterpret_cast<float *>(wire + rec[3]) + lb;
+        uint8_t *const dst = wire + rec[4] + ((lb * d * BITS) >> 3);
+        if ((d & 7) != 0 || !aligned16(v) || (((uintptr_t)err) & 15) != 0) {
+            qsgd_compress_pair_walk_bf16<EF>(LPB, c0, v, err, d, ef_scale, b, BITS, n_bit, random_mode, seed, norm_dst, dst);
+            continue;   // (the other buckets of this wave go on with their own lanes)
+        }
+        // unit u = elements [8 u, 8 u + 8): widened, with error feedback w = widen(grad) + ef_scale * err (product rounded, then the add)
+        auto load8 = [&](int u, f32x4 (&x)[2]) {
+            bf16_load8(v + 8 * u, x[0], x[1]);
+            if (EF && err) {
+                const f32x4 q0 = *(gv_ptr)(err + 8 * u);
+                const f32x4 q1 = *(gv_ptr)(err + 8 * u + 4);
+                x[0] = x[0] + q0 * ef_scale;
+                x[1] = x[1] + q1 * ef_scale;
+            }
+        };
+        auto fold = [&](const f32x4 (&x)[2], float &mx, float &mn) {
+#pragma unroll
+            for (int k = 0; k < 8; k += 2) {
+                mx = absmax3_nan(mx, x[k >> 2][k & 3], x[k >> 2][(k & 3) + 1]);   // NaN-propagating, like torch.max
+                mn = fminf(fminf(mn, fabsf(x[k >> 2][k & 3])), fabsf(x[k >> 2][(k & 3) + 1]));
+            }
+        };
+        // the unit's codes, packed; with error feedback narrow(w) over grad and err = w - decode(code) (ps_quantizer.py:39)
+        auto code8 = [&](int u, const f32x4 (&x)[2], float norm, float y, bool fast, uint32_t key) {
+            unsigned code[8];
+            auto val = [&](int k) { return x[k >> 2][k & 3]; };
+            auto quick = [&](int k) { return shared_quotient(fabsf(val(k)), norm * inv_s, y * s); };
+            auto draw = [&](int k) { return [=] { return bucket_draw(key, (uint32_t)(8 * u + k)); }; };
+            if (fast && draws) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) code[k] = qsgd_code<true, 1>(val(k), quick(k), smax, true, draw(k), BITS);
+            } else if (fast) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) code[k] = qsgd_code<true, 0>(val(k), quick(k), smax, false, draw(k), BITS);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) code[k] = qsgd_code<false>(val(k), qsgd_quotient(val(k), norm, s), smax, draws, draw(k), BITS);
+            }
+            store_unit<BITS>(dst + BITS * u, code);
+            if (EF && err) {
+                f32x4 dec[2];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) dec[k >> 2][k & 3] = qsgd_dequant(code[k], BITS, norm, inv_s);
+                bf16_store8(v + 8 * u, x[0], x[1]);
+                *(gv_ptr)(err + 8 * u) = x[0] - dec[0];
+                *(gv_ptr)(err + 8 * u + 4) = x[1] - dec[1];
+            }
+        };
+        const int units = d >> 3;
+        const bool in_regs = units <= 2 * LPB;   // the lane's two adjacent units stay in registers: the bucket is read once
+        f32x4 x[2][2];
+        float mx = 0.0f, mn = __builtin_inff();
+        if (in_regs) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (2 * c0 + j < units) {
+                    load8(2 * c0 + j, x[j]);
+                    fold(x[j], mx, mn);
+                }
+        } else {
+            for (int u = c0; u < units; u += LPB) {
+                load8(u, x[0]);
+                fold(x[0], mx, mn);
+            }
+        }
+#pragma unroll
+        for (int o = LPB / 2; o > 0; o >>= 1) mx = max_nan(mx, __shfl_xor(mx, o, 64));   // the bucket's LPB lanes
+        if (c0 == 0) *norm_dst = mx;
+        const uint64_t sd = random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, mx, mx) : seed;   // keyed by the bucket's norm
+        const uint32_t key = bucket_draw_key(sd, b);
+        const float y = 1.0f / mx;                         // the bucket's ONE division (FAST: see qsgd_code)
+        const bool fast = !EF && quotient_window(mx, mn);   // (as the float32 kernel: error feedback is bound by its bytes)
+        if (in_regs) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (2 * c0 + j < units) code8(2 * c0 + j, x[j], mx, y, fast, key);
+        } else {
+            for (int u = c0; u < units; u += LPB) {
+                load8(u, x[0]);
+                code8(u, x[0], mx, y, fast, key);
+            }
+        }
+    }
+}
+
+// decode + mean into a bf16 `out`: a lane decodes a unit of 8 elements of the R payloads, adds in payload order in float32,
+// divides, and stores ONE 16 bytes of narrowed values (float32: two stores of 16); a bucket lies on d / 8 lanes, units past them
+// a further trip.  Widths that are no multiple of 8, an `out` view off 16 bytes and wires whose units are not aligned
+// (`units_ok` = 0) take the element-pair walk with 2-byte stores.  The step tail rides as in the float32 kernels.
+template <int BITS>
+__global__ __launch_bounds__(QB_THREADS) void qsgd_decode_sum_batched_bf16_kernel(
+    const int64_t *__restrict__ seg_table, const int32_t *__restrict__ bucket_seg, int64_t nbuckets, int nseg, int n_bit,
+    const uint8_t *__restrict__ gathered, int64_t user_stride, int R, uint16_t *__restrict__ out, int plain, const StepTail tail,
+    int lpb_log2, int units_ok) {
+    __shared__ int64_t s_seg[QB_LDS_SEGS * 8];
+    step_tail_run(tail);
+    const bool lds = nseg <= QB_LDS_SEGS;
+    if (lds) {
+        for (int i = threadIdx.x; i < nseg * 8; i += QB_THREADS) s_seg[i] = seg_table[i];
+        __syncthreads();
+    }
+    const int lpb = 1 << lpb_log2, bpw = 64 >> lpb_log2;
+    const int lane = threadIdx.x & 63, sub = lane >> lpb_log2, c0 = lane & (lpb - 1);
+    const int64_t nw = (int64_t)gridDim.x * (QB_THREADS / 64);
+    const float inv_s = 1.0f / (float)(1 << n_bit);
+    const MeanDiv md = mean_div_of(R, !plain);
+    const bool words = ((reinterpret_cast<uintptr_t>(gathered) | (uintptr_t)user_stride) & 3) == 0;   // the norms are aligned f32 words
+    const int64_t nquads = (nbuckets + bpw - 1) / bpw;
+    int64_t qd = (int64_t)blockIdx.x * (QB_THREADS / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int seg_next = (qd < nquads && bpw * qd + sub < nbuckets) ? bucket_seg[bpw * qd + sub] : 0;
+    for (; qd < nquads; qd += nw) {
+        const int64_t b = (int64_t)bpw * qd + sub;
+        const int seg = seg_next;
+        {
+            const int64_t bn = (int64_t)bpw * (qd + nw) + sub;
+            seg_next = (qd + nw < nquads && bn < nbuckets) ? bucket_seg[bn] : 0;
+        }
+        if (b >= nbuckets) continue;
+        const int64_t *rec = lds ? s_seg + 8 * seg : seg_table + 8 * (int64_t)seg;
+        const int d = (int)rec[1];
+        const int64_t lb = b - rec[2];
+        const int64_t norm_at = rec[3] + 4 * lb, codes = rec[4] + ((lb * d * BITS) >> 3);
+        uint16_t *o = out + rec[5] + lb * d;
+        if (units_ok && (d & 7) == 0 && aligned16(o)) {
+            for (int u = c0; 8 * u < d; u += lpb) {
+                f32x4 acc[2];
+                qsgd_decode_unit<BITS>(gathered, user_stride, R, norm_at, codes + (int64_t)BITS * u, inv_s, md, acc);
+                bf16_store8((gh_ptr)(uintptr_t)(o + 8 * u), acc[0], acc[1]);
+            }
+        } else {
+            auto norm_of = [&](const uint8_t *p) {
+                const uint8_t *q = p + norm_at;
+                if (words) return *reinterpret_cast<const float *>(q);
+                return __uint_as_float((unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24));
+            };
+            qsgd_decode_pair_walk_bf16(lpb, c0, d, BITS, gathered, user_stride, R, norm_of, codes, inv_s, md, o);
+        }
+    }
+}
+
+// the bf16 compress takes d / 16 lanes per bucket: half the float32 kernel's count, at least 2
+static inline int lpb_log2_bf16(int bucket_hint) {
+    const int l = lpb_log2_of(bucket_hint);
+    return (bucket_hint > 0 && l > 1) ? l - 1 : l;
+}
+
+// qb_grid_resident for one instantiation of the bf16 compress kernel.  (qb_grid_resident keeps its occupancy figure per kernel TYPE,
+// and this kernel has the float32 kernel's signature: through it, whichever of the two launched first in a process would size the
+// other's grid -- a float32 group behind a bf16 one ran 7 - 10 % slower.)
+template <bool EF, int BITS, int LPB>
+static int64_t qch_grid(int64_t nitems) {
+    static const int bpc = [] {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, qsgd_compress_batched_bf16_kernel<EF, BITS, LPB>, QB_THREADS, 0) != hipSuccess || n < 1) n = 8;
+        return n;
+    }();
+    int64_t blocks = (nitems + (QB_THREADS / 64) - 1) / (QB_THREADS / 64);
+    const int64_t cap = (int64_t)cu_count() * bpc;
+    if (blocks > cap) blocks = cap;
+    return blocks < 1 ? 1 : blocks;
+}
+
+template <bool EF>
+static int qsgd_compress_batched_bf16(const char *what, const int64_t *seg_table, const int32_t *bucket_seg, int nseg,
+                                      int64_t nbuckets, int n_bit, int random_mode, uint64_t seed, float ef_scale,
+                                      uint8_t *wire, const int64_t *dense_table, int ndense, int bucket_hint, void *stream) {
+    int bits;
+    if (const int rc = qsgd_compress_check(what, seg_table && bucket_seg && wire, nseg, nbuckets, n_bit, random_mode, &bits)) return rc;
+    const int lpb_log2 = lpb_log2_bf16(bucket_hint);
+#define GQ_QCH_LAUNCH(BITSV, LPBV)                                                                                                    \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(qsgd_compress_batched_bf16_kernel<EF, BITSV, LPBV>),                                           \
+                       dim3((unsigned)qch_grid<EF, BITSV, LPBV>((nbuckets + 64 / LPBV - 1) / (64 / LPBV))),                           \
+                       dim3(QB_THREADS), 0, as_stream(stream), seg_table, bucket_seg, nseg, nbuckets, n_bit, random_mode, seed,      \
+                       ef_scale, wire, dense_table, ndense)
+#define GQ_QCH_BITS(BITSV)                                  \
+    do {                                                    \
+        if (lpb_log2 == 1) GQ_QCH_LAUNCH(BITSV, 2);         \
+        else if (lpb_log2 == 2) GQ_QCH_LAUNCH(BITSV, 4);    \
+        else if (lpb_log2 == 3) GQ_QCH_LAUNCH(BITSV, 8);    \
+        else GQ_QCH_LAUNCH(BITSV, 16);                      \
+    } while (0)
+    if (bits == 4) GQ_QCH_BITS(4);
+    else if (bits == 8) GQ_QCH_BITS(8);
+    else GQ_QCH_BITS(16);
+#undef GQ_QCH_BITS
+#undef GQ_QCH_LAUNCH
+    GQ_CHECK_LAUNCH(what);
+    return GQ_OK;
+}
+}  // namespace gq
+
+GQ_INTERNAL int gqi_qsgd_compress_batched_bf16(const int64_t *seg_table, const int32_t *bucket_seg, int nseg, int64_t nbuckets,
+                                               int n_bit, int random_mode, uint64_t seed, int ef, float ef_scale, uint8_t *wire,
+                                               const int64_t *dense_table, int ndense, int bucket_hint, void *stream) {
+    if (ef)
+        return gq::qsgd_compress_batched_bf16<true>("gq_qsgd_compress_batched (bf16)", seg_table, bucket_seg, nseg, nbuckets, n_bit,
+                                                    random_mode, seed, ef_scale, wire, dense_table, ndense, bucket_hint, stream);
+    return gq::qsgd_compress_batched_bf16<false>("gq_qsgd_compress_batched (bf16)", seg_table, bucket_seg, nseg, nbuckets, n_bit,
+                                                 random_mode, seed, 0.0f, wire, dense_table, ndense, bucket_hint, stream);
+}
+
+GQ_INTERNAL int gqi_qsgd_decode_sum_batched_bf16(const int64_t *seg_table, const int32_t *bucket_seg, int nseg, int64_t nbuckets,
+                                                 int n_bit, int bits, const uint8_t *gathered, int64_t user_stride_bytes, int R,
+                                                 uint16_t *out, int plain, const gq::StepTail *tail_or_null, int *tail_taken,
+                                                 int bucket_hint, void *stream) {
+    plain = plain ? 1 : 0;
+    if (tail_taken) *tail_taken = 0;
+    if (const int rc = gq::qsgd_decode_check("gq_qsgd_decode_sum_batched (bf16)", seg_table && bucket_seg && gathered && out, nseg, nbuckets, n_bit, bits, R))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(out) & 1) != 0)
+        return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum_batched (bf16): out must be 2-byte aligned");
+    const gq::StepTail tail = tail_or_null ? *tail_or_null : gq::StepTail{};
+    const int lpb_log2 = gq::lpb_log2_of(bucket_hint);
+    const int bpw = 64 >> lpb_log2;
+    // a unit of 8 codes is one aligned load of 4, 8 or 16 bytes in every payload
+    const uintptr_t unit_mask = bits == 4 ? 3 : 15;
+    const int units_ok = ((reinterpret_cast<uintptr_t>(gathered) | (uintptr_t)user_stride_bytes) & unit_mask) == 0 ? 1 : 0;
+    const dim3 grid((unsigned)gq::grid_cap((nbuckets + bpw - 1) / bpw, gq::QB_THREADS / 64)), block(gq::QB_THREADS);
+#define GQ_QDH_LAUNCH(BITSV)                                                                                                   \
+    hipLaunchKernelGGL(gq::qsgd_decode_sum_batched_bf16_kernel<BITSV>, grid, block, 0, gq::as_stream(stream), seg_table,        \
+                       bucket_seg, nbuckets, nseg, n_bit, gathered, user_stride_bytes, R, out, plain, tail, lpb_log2, units_ok)
+    if (bits == 4) GQ_QDH_LAUNCH(4);
+    else if (bits == 8) GQ_QDH_LAUNCH(8);
+    else GQ_QDH_LAUNCH(16);
+#undef GQ_QDH_LAUNCH
+    GQ_CHECK_LAUNCH("gq_qsgd_decode_sum_batched (bf16)");
+    if (tail_taken) *tail_taken = 1;
+    return GQ_OK;
+}

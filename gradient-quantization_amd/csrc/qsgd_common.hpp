@@ -256,6 +256,128 @@ __device__ __forceinline__ void qsgd_decode_unit_walk(int lanes, int first, int 
     }
 }
 
+// ---- bf16 on the tensor side (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE) ----------------------------------------------------------
+// The *_bf16 launches read gradients and write `out` (and, under error feedback, the gradient) as bf16; norms, draws, codes, the
+// wire and the residuals are the float32 launches'.  widen: bits << 16, exact.  narrow: ONE integer round to nearest even, every
+// NaN -> 0x7FC0; the carry runs into the exponent and reaches +-inf at the top.
+typedef uint16_t __attribute__((address_space(1))) *gh_ptr;
+typedef uv4 __attribute__((address_space(1))) *guv4_ptr;
+__device__ __forceinline__ float bf16_widen(unsigned h) { return __uint_as_float(h << 16); }
+__device__ __forceinline__ unsigned bf16_narrow(float x) {
+    const uint32_t b = __float_as_uint(x);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7FC0u;
+    return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ unsigned bf16_narrow2(float lo, float hi) { return bf16_narrow(lo) | (bf16_narrow(hi) << 16); }
+// A lane's unit of 8 elements is ONE 16-byte access (float32: two).  p + e must be 16-byte aligned: the kernels test the bucket's
+// (chunk's) first address and take the element walks (2-byte accesses) for a view that is not.
+__device__ __forceinline__ void bf16_load8(gh_ptr p, f32x4 &a, f32x4 &b) {
+    const uv4 w = *(guv4_ptr)p;
+    a = f32x4{__uint_as_float(w[0] << 16), __uint_as_float(w[0] & 0xffff0000u), __uint_as_float(w[1] << 16), __uint_as_float(w[1] & 0xffff0000u)};
+    b = f32x4{__uint_as_float(w[2] << 16), __uint_as_float(w[2] & 0xffff0000u), __uint_as_float(w[3] << 16), __uint_as_float(w[3] & 0xffff0000u)};
+}
+__device__ __forceinline__ void bf16_store8(gh_ptr p, const f32x4 &a, const f32x4 &b) {
+    *(guv4_ptr)p = uv4{bf16_narrow2(a[0], a[1]), bf16_narrow2(a[2], a[3]), bf16_narrow2(b[0], b[1]), bf16_narrow2(b[2], b[3])};
+}
+// copy_dense_segments with bf16 sources: the identity-compressed tensors travel as float32, widened here
+__device__ __forceinline__ void copy_dense_segments_bf16(const int64_t *__restrict__ dense_table, int ndense, uint8_t *__restrict__ wire) {
+    for (int t = blockIdx.x; t < ndense; t += gridDim.x) {
+        const gh_ptr src = (gh_ptr)(uintptr_t)dense_table[3 * t];
+        float *dst = reinterpret_cast<float *>(wire + dense_table[3 * t + 1]);
+        const int64_t n = dense_table[3 * t + 2];
+        for (int64_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = bf16_widen(src[i]);
+    }
+}
+__device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+__device__ __forceinline__ bool aligned16(gh_ptr p) { return ((uintptr_t)p & 15) == 0; }
+
+// qsgd_compress_pair_walk over a bf16 bucket at any 2-byte alignment: the same walk, norm, draws and codes, the elements read one
+// 2-byte load each.  Under error feedback the bucket is read as w = widen(grad) + ef_scale * err BOTH times (the float32 walk
+// reads the stored sum back; a stored bf16 sum is rounded), and the second trip stores narrow(w) and err = w - decode(code).
+template <bool EF>
+__device__ __forceinline__ void qsgd_compress_pair_walk_bf16(int lanes, int lane, gh_ptr v, gf_ptr err, int d, float ef_scale, int64_t b,
+                                                             int bits, int n_bit, int random_mode, uint64_t seed, float *norm_dst, uint8_t *dst) {
+    const float s = (float)(1 << n_bit), smax = s - 1.0f, inv_s = 1.0f / s;
+    auto load = [&](int e) {
+        v2f p = {bf16_widen(v[e]), bf16_widen(v[e + 1])};
+        if (EF && err) {
+            const float p0 = ef_scale * err[e], p1 = ef_scale * err[e + 1];
+            p[0] = p[0] + p0;
+            p[1] = p[1] + p1;
+        }
+        return p;
+    };
+    float mx = 0.0f;
+    for (int e = 2 * lane; e < d; e += 2 * lanes) {
+        const v2f p = load(e);
+        mx = absmax3_nan(mx, p[0], p[1]);
+    }
+#pragma unroll
+    for (int o = lanes / 2; o > 0; o >>= 1) mx = max_nan(mx, __shfl_xor(mx, o, 64));
+    if (lane == 0) *norm_dst = mx;
+    const uint64_t sd = random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, mx, mx) : seed;
+    const uint32_t key = bucket_draw_key(sd, b);
+    const bool draws = random_mode >= GQ_RANDOM_DEVICE;
+    for (int e = 2 * lane; e < d; e += 2 * lanes) {
+        const v2f p = load(e);
+        const unsigned c0 = qsgd_code<false>(p[0], qsgd_quotient(p[0], mx, s), smax, draws, [&] { return bucket_draw(key, (uint32_t)e); }, bits);
+        const unsigned c1 = qsgd_code<false>(p[1], qsgd_quotient(p[1], mx, s), smax, draws, [&] { return bucket_draw(key, (uint32_t)e + 1u); }, bits);
+        store_pair(dst + pair_at(e, bits), bits, c0, c1);
+        if (EF && err) {
+            v[e] = (uint16_t)bf16_narrow(p[0]);
+            v[e + 1] = (uint16_t)bf16_narrow(p[1]);
+            err[e] = p[0] - qsgd_dequant(c0, bits, mx, inv_s);
+            err[e + 1] = p[1] - qsgd_dequant(c1, bits, mx, inv_s);
+        }
+    }
+}
+
+// qsgd_decode_pair_walk with a bf16 `o` at any 2-byte alignment: the float32 sum and mean, narrowed once at the store
+template <class NormOf, class Off>
+__device__ __forceinline__ void qsgd_decode_pair_walk_bf16(int lanes, int lane, int d, int bits, const uint8_t *gathered, int64_t user_stride,
+                                                           int R, NormOf &&norm_of, Off codes, float inv_s, const MeanDiv &md, uint16_t *o) {
+    for (int e = 2 * lane; e < d; e += 2 * lanes) {
+        float a0 = 0.0f, a1 = 0.0f;
+        for (int r = 0; r < R; ++r) {
+            const uint8_t *p = gathered + (int64_t)r * user_stride;
+            const float norm = norm_of(p);
+            unsigned c0, c1;
+            load_pair(p + (codes + (Off)pair_at(e, bits)), bits, c0, c1);
+            const float t0 = qsgd_dequant(c0, bits, norm, inv_s), t1 = qsgd_dequant(c1, bits, norm, inv_s);
+            a0 = (r == 0) ? t0 : a0 + t0;
+            a1 = (r == 0) ? t1 : a1 + t1;
+        }
+        if (md.apply) {
+            a0 = mean_div(a0, md);
+            a1 = mean_div(a1, md);
+        }
+        o[e] = (uint16_t)bf16_narrow(a0);
+        o[e + 1] = (uint16_t)bf16_narrow(a1);
+    }
+}
+// a lane's unit of 8 codes of R payloads -> the 8 float32 means (the arithmetic of qsgd_decode_unit_walk's trip)
+template <int BITS, class Off>
+__device__ __forceinline__ void qsgd_decode_unit(const uint8_t *gathered, int64_t user_stride, int R, Off norm_at, Off unit_at, float inv_s,
+                                                 const MeanDiv &md, f32x4 (&acc)[2]) {
+    for (int r = 0; r < R; ++r) {
+        const uint8_t *p = gathered + (int64_t)r * user_stride;
+        const float norm = *reinterpret_cast<const float *>(p + norm_at);
+        unsigned w[BITS / 4], nw[BITS / 4];
+        load_unit<BITS>((gbyte_ptr)(p + unit_at), w);
+#pragma unroll
+        for (int i = 0; i < BITS / 4; ++i) nw[i] = ~w[i];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float t = qsgd_scale(unit_signed_level<BITS>(w, nw, k), norm, inv_s);
+            acc[k >> 2][k & 3] = r == 0 ? t : acc[k >> 2][k & 3] + t;
+        }
+    }
+    if (md.apply) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k >> 2][k & 3] = mean_div(acc[k >> 2][k & 3], md);
+    }
+}
+
 // ---- host: what the multi-tensor launchers refuse (bucketed and wide alike; `what` names the entry point) ------------------------
 // compress: -> GQ_OK and the code width, or the refusal
 static inline int qsgd_compress_check(const char *what, bool pointers, int nseg, int64_t nitems, int n_bit, int random_mode, int *bits) {

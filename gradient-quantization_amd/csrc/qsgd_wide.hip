@@ -326,3 +326,277 @@ GQ_INTERNAL int gqi_qsgd_wide_decode_sum(const int64_t *seg_table, const int32_t
     if (tail_taken) *tail_taken = 1;
     return GQ_OK;
 }
+
+// ---- bf16 gradients and bf16 `out` (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE) ----------------------------------------------------
+// The same chunks, runs, norm words, draws and wire.  In BOTH passes a lane owns the units [8 lane + 512 i, + 8), i = 0, 1, of the
+// chunk: a unit is ONE 16-byte load, a wave's load 1,024 contiguous bytes (the float32 absmax pass takes element pairs 512 bytes
+// apart to get contiguous 8-byte loads; 16-byte pieces of bf16 are contiguous as they lie).  Under error feedback pass 1 does NOT
+// store the sum back: the stored bf16 would be rounded, and pass 2 needs the unrounded w.  Pass 2 forms w = widen(grad) +
+// ef_scale * err again from the untouched gradient and residual (the same two float32 operations: the same bits), and the lane
+// that owns a unit stores narrow(w) over the gradient and err = w - decode(code).  A chunk whose first address is off 16 bytes,
+// and a chunk's ragged last unit, take 2-byte loads and stores.
+namespace gq {
+
+template <bool EF>
+__device__ __forceinline__ void wide_load8_bf16(gh_ptr v, gf_ptr err, int e0, int n, bool quads, float ef_scale, float (&val)[8]) {
+    if (e0 + 8 <= n && quads) {
+        f32x4 a, b;
+        bf16_load8(v + e0, a, b);
+        if (EF && err) {   // product rounded, then the add
+            const f32x4 q0 = *(gv_ptr)(err + e0), q1 = *(gv_ptr)(err + e0 + 4);
+            a = a + q0 * ef_scale;
+            b = b + q1 * ef_scale;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            val[k] = a[k];
+            val[4 + k] = b[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float x = 0.0f;   // (behind the chunk: +0, which no max and no store sees)
+            if (e0 + k < n) {
+                x = bf16_widen(v[e0 + k]);
+                if (EF && err) {
+                    const float p = ef_scale * err[e0 + k];
+                    x = x + p;
+                }
+            }
+            val[k] = x;
+        }
+    }
+}
+
+template <bool EF>
+__global__ __launch_bounds__(QW_THREADS) void qsgd_wide_absmax_bf16_kernel(const int64_t *__restrict__ seg_table,
+                                                                          const int32_t *__restrict__ chunk_seg,
+                                                                          int64_t nchunks, float ef_scale,
+                                                                          unsigned *__restrict__ norm_bits) {
+    const int lane = threadIdx.x & 63;
+    int64_t c_begin, c_end;
+    wide_run(nchunks, c_begin, c_end);
+    unsigned *cur = nullptr;     // the bucket word the running max belongs to
+    float run_mx = 0.0f;
+    auto flush = [&]() {
+        const float m = wave_max_nan(run_mx);
+        if (lane == 0 && cur) {
+            const unsigned mine = __float_as_uint(m);
+            if (mine > __hip_atomic_load(cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(cur, mine);
+        }
+        run_mx = 0.0f;
+    };
+    WideItem nxt = wide_item(seg_table, chunk_seg, c_begin < c_end ? c_begin : 0);
+    for (int64_t c = c_begin; c < c_end; ++c) {
+        const WideItem it = nxt;
+        if (c + 1 < c_end) nxt = wide_item(seg_table, chunk_seg, c + 1);
+        const int64_t at = it.b * it.d + it.first;
+        const gh_ptr v = (gh_ptr)(uintptr_t)it.rec[0] + at;
+        const gf_ptr err = (EF && it.rec[7]) ? (gf_ptr)(uintptr_t)it.rec[7] + at : (gf_ptr)0;
+        const bool quads = aligned16(v) && (((uintptr_t)err) & 15) == 0;
+        unsigned *word = norm_bits + it.rec[6] + it.b;
+        if (word != cur) {
+            flush();
+            cur = word;
+        }
+        float mx = run_mx;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e0 = 8 * lane + 512 * i;
+            if (e0 >= it.n) continue;
+            float val[8];
+            wide_load8_bf16<EF>(v, err, e0, it.n, quads, ef_scale, val);
+#pragma unroll
+            for (int k = 0; k < 8; k += 2) mx = absmax3_nan(mx, val[k], val[k + 1]);   // NaN-propagating
+        }
+        run_mx = mx;
+    }
+    flush();
+}
+
+template <bool EF, int BITS>
+__global__ __launch_bounds__(QW_THREADS) void qsgd_wide_quantise_bf16_kernel(
+    const int64_t *__restrict__ seg_table, const int32_t *__restrict__ chunk_seg, int64_t nchunks, int n_bit,
+    int random_mode, uint64_t seed, float ef_scale, const unsigned *__restrict__ norm_bits, uint8_t *__restrict__ wire,
+    const int64_t *__restrict__ dense_table, int ndense) {
+    resolve_seed(random_mode, seed);
+    copy_dense_segments_bf16(dense_table, ndense, wire);
+    const int lane = threadIdx.x & 63;
+    const float s = (float)(1 << n_bit), smax = s - 1.0f, inv_s = 1.0f / s;
+    int64_t c_begin, c_end;
+    wide_run(nchunks, c_begin, c_end);
+    WideItem nxt = wide_item(seg_table, chunk_seg, c_begin < c_end ? c_begin : 0);
+    for (int64_t c = c_begin; c < c_end; ++c) {
+        const WideItem it = nxt;
+        if (c + 1 < c_end) nxt = wide_item(seg_table, chunk_seg, c + 1);
+        const int64_t at = it.b * it.d + it.first;                 // first element of the chunk inside the tensor
+        const gh_ptr v = (gh_ptr)(uintptr_t)it.rec[0] + at;
+        const gf_ptr err = (EF && it.rec[7]) ? (gf_ptr)(uintptr_t)it.rec[7] + at : (gf_ptr)0;
+        const float norm = __uint_as_float(norm_bits[it.rec[6] + it.b]);
+        if (it.first == 0 && lane == 0) reinterpret_cast<float *>(wire + it.rec[3])[it.b] = norm;
+        uint8_t *dst = wire + it.rec[4] + ((at * BITS) >> 3);
+        const bool dwords = ((at & 7) == 0);                       // code dwords of whole 8-element groups are aligned
+        const bool quads = aligned16(v) && (((uintptr_t)err) & 15) == 0;
+        const uint64_t g0 = ((uint64_t)(it.rec[6] + it.b) << 32) + (uint64_t)it.first;   // RNG index: (bucket, element)
+        const uint64_t sd = random_mode == GQ_RANDOM_DEVICE_KEYED ? keyed_seed(seed, norm, norm) : seed;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e0 = 8 * lane + 512 * i;
+            if (e0 >= it.n) continue;
+            unsigned code[8];
+            float val[8];
+            const bool whole = e0 + 8 <= it.n;
+            wide_load8_bf16<EF>(v, err, e0, it.n, quads, ef_scale, val);
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                code[k] = qsgd_code<false>(val[k], qsgd_quotient(val[k], norm, s), smax, random_mode >= GQ_RANDOM_DEVICE,
+                                           [&] { return uniform01(sd, g0 + (uint64_t)(e0 + k)); }, BITS);
+            if (EF && err) {
+                float res[8];   // the element's own code decoded, then ps_quantizer.py:39 -- from the unrounded w
+#pragma unroll
+                for (int k = 0; k < 8; ++k) res[k] = val[k] - qsgd_dequant(code[k], BITS, norm, inv_s);
+                if (whole && quads) {
+                    bf16_store8(v + e0, f32x4{val[0], val[1], val[2], val[3]}, f32x4{val[4], val[5], val[6], val[7]});
+                    *(gv_ptr)(err + e0) = f32x4{res[0], res[1], res[2], res[3]};
+                    *(gv_ptr)(err + e0 + 4) = f32x4{res[4], res[5], res[6], res[7]};
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (e0 + k < it.n) {
+                            v[e0 + k] = (uint16_t)bf16_narrow(val[k]);
+                            err[e0 + k] = res[k];
+                        }
+                }
+            }
+            uint8_t *unit = dst + BITS * (e0 >> 3);   // the lane's unit; a partial one pair by pair
+            if (whole && dwords) {
+                store_unit<BITS>(unit, code);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (e0 + 2 * k < it.n) store_pair(unit + pair_at(2 * k, BITS), BITS, code[2 * k], code[2 * k + 1]);
+            }
+        }
+    }
+}
+
+template <int BITS>
+__global__ __launch_bounds__(QW_THREADS) void qsgd_wide_decode_bf16_kernel(const int64_t *__restrict__ seg_table,
+                                                                          const int32_t *__restrict__ chunk_seg,
+                                                                          int64_t nchunks, int n_bit,
+                                                                          const uint8_t *__restrict__ gathered,
+                                                                          int64_t user_stride, int R,
+                                                                          uint16_t *__restrict__ out, int plain, const StepTail tail) {
+    step_tail_run(tail);
+    const int lane = threadIdx.x & 63;
+    const float inv_s = 1.0f / (float)(1 << n_bit);
+    const MeanDiv md = mean_div_of(R, !plain);
+    int64_t c_begin, c_end;
+    wide_run(nchunks, c_begin, c_end);
+    WideItem nxt = wide_item(seg_table, chunk_seg, c_begin < c_end ? c_begin : 0);
+    for (int64_t c = c_begin; c < c_end; ++c) {
+        const WideItem it = nxt;
+        if (c + 1 < c_end) nxt = wide_item(seg_table, chunk_seg, c + 1);
+        const int64_t at = it.b * it.d + it.first;
+        uint16_t *o = out + it.rec[5] + at;
+        const int64_t code_off = it.rec[4] + ((at * BITS) >> 3);
+        const bool dwords = ((at & 7) == 0);
+        const bool quads = aligned16(o);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int e0 = 8 * lane + 512 * i;
+            if (e0 >= it.n) continue;
+            const bool whole = e0 + 8 <= it.n;
+            float acc[8];
+            for (int r = 0; r < R; ++r) {
+                const uint8_t *p = gathered + (int64_t)r * user_stride;
+                const float norm = reinterpret_cast<const float *>(p + it.rec[3])[it.b];
+                unsigned w[BITS / 4] = {}, nw[BITS / 4];   // the lane's unit; a partial one pair by pair (codes 0 behind the chunk)
+                const uint8_t *unit = p + code_off + BITS * (e0 >> 3);
+                if (whole && dwords) {
+                    load_unit<BITS>((gbyte_ptr)unit, w);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (e0 + 2 * k < it.n) {
+                            unsigned c0, c1;
+                            load_pair(unit + pair_at(2 * k, BITS), BITS, c0, c1);
+                            w[2 * k * BITS / 32] |= (c0 | (c1 << BITS)) << (2 * k * BITS % 32);
+                        }
+                }
+#pragma unroll
+                for (int j = 0; j < BITS / 4; ++j) nw[j] = ~w[j];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const float t = qsgd_scale(unit_signed_level<BITS>(w, nw, k), norm, inv_s);
+                    acc[k] = (r == 0) ? t : acc[k] + t;
+                }
+            }
+            if (md.apply) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) acc[k] = mean_div(acc[k], md);
+            }
+            if (whole && quads) {   // the unit narrowed into ONE 16-byte store
+                bf16_store8((gh_ptr)(uintptr_t)(o + e0), f32x4{acc[0], acc[1], acc[2], acc[3]}, f32x4{acc[4], acc[5], acc[6], acc[7]});
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (e0 + k < it.n) o[e0 + k] = (uint16_t)bf16_narrow(acc[k]);
+            }
+        }
+    }
+}
+
+}  // namespace gq
+
+GQ_INTERNAL int gqi_qsgd_wide_compress_bf16(const int64_t *seg_table, const int32_t *chunk_seg, int nseg, int64_t nchunks,
+                                            int n_bit, int random_mode, uint64_t seed, int ef, float ef_scale,
+                                            uint32_t *norm_bits, uint8_t *wire, const int64_t *dense_table, int ndense, void *stream) {
+    int bits;
+    if (const int rc = gq::qsgd_compress_check("gq_qsgd_compress_batched (bf16, wide)", seg_table && chunk_seg && norm_bits && wire, nseg, nchunks,
+                                               n_bit, random_mode, &bits))
+        return rc;
+    hipStream_t st = gq::as_stream(stream);
+    const dim3 grid((unsigned)gq::grid_cap(nchunks, gq::QW_THREADS / 64)), block(gq::QW_THREADS);
+    if (ef)
+        hipLaunchKernelGGL(gq::qsgd_wide_absmax_bf16_kernel<true>, grid, block, 0, st, seg_table, chunk_seg, nchunks, ef_scale, norm_bits);
+    else
+        hipLaunchKernelGGL(gq::qsgd_wide_absmax_bf16_kernel<false>, grid, block, 0, st, seg_table, chunk_seg, nchunks, 0.0f, norm_bits);
+#define GQ_QWH_LAUNCH(EFV, BITSV)                                                                                                 \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gq::qsgd_wide_quantise_bf16_kernel<EFV, BITSV>), grid, block, 0, st, seg_table, chunk_seg, \
+                       nchunks, n_bit, random_mode, seed, ef_scale, norm_bits, wire, dense_table, ndense)
+    if (ef && bits == 4) GQ_QWH_LAUNCH(true, 4);
+    else if (ef && bits == 8) GQ_QWH_LAUNCH(true, 8);
+    else if (ef) GQ_QWH_LAUNCH(true, 16);
+    else if (bits == 4) GQ_QWH_LAUNCH(false, 4);
+    else if (bits == 8) GQ_QWH_LAUNCH(false, 8);
+    else GQ_QWH_LAUNCH(false, 16);
+#undef GQ_QWH_LAUNCH
+    GQ_CHECK_LAUNCH("gq_qsgd_compress_batched (bf16, wide)");
+    return GQ_OK;
+}
+
+GQ_INTERNAL int gqi_qsgd_wide_decode_sum_bf16(const int64_t *seg_table, const int32_t *chunk_seg, int nseg, int64_t nchunks,
+                                              int n_bit, int bits, const uint8_t *gathered, int64_t user_stride_bytes, int R,
+                                              uint16_t *out, int plain, const gq::StepTail *tail_or_null, int *tail_taken, void *stream) {
+    plain = plain ? 1 : 0;
+    if (tail_taken) *tail_taken = 0;
+    const gq::StepTail tail = tail_or_null ? *tail_or_null : gq::StepTail{};
+    if (const int rc = gq::qsgd_decode_check("gq_qsgd_decode_sum_batched (bf16, wide)", seg_table && chunk_seg && gathered && out, nseg, nchunks, n_bit, bits, R))
+        return rc;
+    if ((user_stride_bytes & 3) != 0 || (reinterpret_cast<uintptr_t>(gathered) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 1) != 0)
+        return gq::fail(GQ_ERR_INVALID_ARG, "gq_qsgd_decode_sum_batched (bf16, wide): wires must be 4-byte, out 2-byte aligned");
+    const dim3 grid((unsigned)gq::grid_cap(nchunks, gq::QW_THREADS / 64)), block(gq::QW_THREADS);
+    if (bits == 4)
+        hipLaunchKernelGGL(gq::qsgd_wide_decode_bf16_kernel<4>, grid, block, 0, gq::as_stream(stream), seg_table, chunk_seg,
+                           nchunks, n_bit, gathered, user_stride_bytes, R, out, plain, tail);
+    else if (bits == 16)
+        hipLaunchKernelGGL(gq::qsgd_wide_decode_bf16_kernel<16>, grid, block, 0, gq::as_stream(stream), seg_table, chunk_seg,
+                           nchunks, n_bit, gathered, user_stride_bytes, R, out, plain, tail);
+    else
+        hipLaunchKernelGGL(gq::qsgd_wide_decode_bf16_kernel<8>, grid, block, 0, gq::as_stream(stream), seg_table, chunk_seg,
+                           nchunks, n_bit, gathered, user_stride_bytes, R, out, plain, tail);
+    GQ_CHECK_LAUNCH("gq_qsgd_decode_sum_batched (bf16, wide)");
+    if (tail_taken) *tail_taken = 1;
+    return GQ_OK;
+}

@@ -457,10 +457,13 @@ class ResidualCodec(object):
 class QSGDCodec(object):
     """QSGDCompressor on the HIP kernels.  Wire per user, packed form (even bucket size and a
     top level that fits 3, 7 or 15 bits):  norm f32[Mb] | one code per element = sign<<(bits-1) | level,
-    4-bit codes two per byte.  Otherwise the plain form  norm f32[Mb] | signs u8[n] | levels u8|i32 [n]."""
+    4-bit codes two per byte.  Otherwise the plain form  norm f32[Mb] | signs u8[n] | levels u8|i32 [n].
+    dtype: torch.float32 or torch.bfloat16 (packed form only) -- what the gradients are and what every decode returns
+    (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE); the wire and the residuals are the float32 ones."""
 
-    def __init__(self, compressor, numel, shape):
+    def __init__(self, compressor, numel, shape, dtype=torch.float32):
         self.c, self.numel, self.shape = compressor, numel, shape
+        self.dtype = torch.float32
         self.Mb, self.d = compressor.M, compressor.dim
         mode = native.RANDOM_DEVICE if compressor.random else native.RANDOM_OFF
         self.bits = 0
@@ -480,6 +483,17 @@ class QSGDCodec(object):
             self.levels_off = self.signs_off + _up(numel)
             self.nbytes = self.levels_off + _up(numel * lb)
         self._mode = mode
+        if dtype != torch.float32:
+            self.set_dtype(dtype)
+
+    def set_dtype(self, dtype):
+        """(the quantizers: a codec factory is not told the parameter's dtype)"""
+        if dtype not in native.QSGD_DTYPES:
+            raise TypeError("QSGDCodec: the kernels take float32 or bfloat16 tensors, got %s" % (dtype,))
+        if dtype != torch.float32 and not self.bits:
+            raise TypeError("QSGDCodec: %s gradients need the packed wire (an even bucket width, no gq_rng 'reference', a top level "
+                            "that fits 15 bits); this tensor takes the plain form, which is float32 only" % (dtype,))
+        self.dtype, self._single = dtype, None
 
     # ---- packed form: a single-segment instance of the batched kernels ----------------------
     def _batched1(self, dev):
@@ -495,13 +509,18 @@ class QSGDCodec(object):
         levels = wire_user[off + self.levels_off:off + self.levels_off + self.numel * lb].view(self.level_dtype)
         return norm, signs, levels
 
-    def encode_into(self, grad, wire_user, off, salt):
+    def encode_into(self, grad, wire_user, off, salt, err=None, ef_scale=None):
+        """err, ef_scale (packed form): error feedback in the same launch -- grad <- grad + ef_scale * err (narrowed where grad is
+        bfloat16) and err <- the unrounded sum - decoded, both in place; grad must then be contiguous itself."""
         _require_device(grad, "QSGDCodec.encode_into")
+        if err is not None and not (self.bits and grad.is_contiguous()):
+            raise ValueError("QSGDCodec.encode_into: error feedback in the launch needs the packed form and a contiguous gradient")
         flat = grad.contiguous().view(-1)
         c = self.c
         if self.bits:
-            ok = self._batched1(flat.device).encode([flat], wire_user[off:off + self.nbytes], 0, salt)
-            assert ok, "QSGDCodec: gradient storage must be 8-byte aligned"
+            ok = self._batched1(flat.device).encode([flat], wire_user[off:off + self.nbytes], 0, salt,
+                                                    [err.view(-1)] if err is not None else None, ef_scale)
+            assert ok, "QSGDCodec: the gradient must be a %s tensor, its storage %d-byte aligned" % (self.dtype, self._single.align)
             return
         norm, signs, levels = self._views(wire_user, off)
         if not c.random:
@@ -529,10 +548,13 @@ class QSGDCodec(object):
             .view(self.level_dtype)
         native.qsgd_decode_sum(norm.view(-1), signs.view(-1), levels.view(-1), self.d, self.c.bit, out, R=R)
 
-    def roundtrip(self, grad, salt):
+    def roundtrip(self, grad, salt, err=None, ef_scale=None):
         tmp = torch.empty(self.nbytes, dtype=torch.uint8, device=grad.device)
-        self.encode_into(grad, tmp, 0, salt)
-        out = torch.empty(self.numel, dtype=torch.float32, device=grad.device)
+        if err is not None:
+            self.encode_into(grad, tmp, 0, salt, err, ef_scale)
+        else:
+            self.encode_into(grad, tmp, 0, salt)
+        out = torch.empty(self.numel, dtype=self.dtype, device=grad.device)
         self._decode_rows(tmp.view(1, -1), 0, 1, out, plain=True)     # decompress(compress(g)): no aggregate
         return out.view(self.shape)
 
@@ -540,7 +562,7 @@ class QSGDCodec(object):
         self._decode_rows(wire_user.view(1, -1), off, 1, out, plain=True)
 
     def decode_mean(self, gathered, off, R, plain=False):
-        out = torch.empty(self.numel, dtype=torch.float32, device=gathered.device)
+        out = torch.empty(self.numel, dtype=self.dtype, device=gathered.device)
         self._decode_rows(gathered, off, R, out, plain=plain)
         if R == 1 and not plain:
             out.add_(0.0)   # as HSQCodec.decode_mean: torch.stack(...).mean(0) of one payload turns -0 into +0
@@ -1679,7 +1701,8 @@ class BatchedQSGD(_BatchedBase):
 
     @staticmethod
     def group_key(codec):
-        return (codec.bits, codec.c.bit, int(BatchedQSGD.is_wide(codec)))
+        # (the dtype by name: the keys are sorted.  A model with float32 norms and bfloat16 weights gets two groups.)
+        return (codec.bits, codec.c.bit, int(BatchedQSGD.is_wide(codec)), str(getattr(codec, "dtype", torch.float32)))
 
     @staticmethod
     def place_lone_buckets(codecs):
@@ -1698,7 +1721,7 @@ class BatchedQSGD(_BatchedBase):
             if not BatchedQSGD.eligible(cd):
                 continue
             cd._wide = cd.d >= BatchedQSGD.WIDE_MIN
-            fmt = (cd.bits, cd.c.bit)
+            fmt = (cd.bits, cd.c.bit, str(getattr(cd, "dtype", torch.float32)))      # (a group holds one dtype: group_key)
             if cd._wide:
                 wide.setdefault(fmt, []).append(cd)
             elif cd.Mb == 1 and cd.d > BatchedQSGD.LONE_MIN:
@@ -1725,7 +1748,13 @@ class BatchedQSGD(_BatchedBase):
         self.counter = bool(self.random and c0.c._rng == "device")
         self.wide = self.is_wide(c0)
         assert all(cd.bits == self.bits and cd.c.bit == self.n_bit and self.is_wide(cd) == self.wide for cd in self.codecs)
-        self.align = 8
+        dtype = getattr(c0, "dtype", torch.float32)
+        assert all(getattr(cd, "dtype", torch.float32) == dtype for cd in self.codecs)
+        # the tensor-side type (include/gq_hsq.h): 8-byte aligned float32 gradients, views in `out` on multiples of 4 elements;
+        # bfloat16: 2-byte aligned gradients and dense-copy sources, views on multiples of 8 -- either way a view starts on 16 bytes
+        bf16 = dtype == torch.bfloat16
+        self.dtype, self._dtypes = dtype, {dtype}
+        self.align, self._dense_align, out_pad = (2, 2, 8) if bf16 else (8, 4, 4)
         nseg = len(self.idxs)
         table = torch.zeros((nseg, 8), dtype=torch.int64)
         item_seg = []
@@ -1743,7 +1772,7 @@ class BatchedQSGD(_BatchedBase):
             item += items
             word += (cd.Mb + 31) & ~31 if self.wide else 0     # a tensor's norm words start on their own 128-byte line
             self.out_off.append(out_off)
-            out_off += (cd.numel + 3) & ~3          # tensors start 16-byte aligned in `out` (dwordx4 stores)
+            out_off += (cd.numel + out_pad - 1) & ~(out_pad - 1)          # tensors start 16-byte aligned in `out` (dwordx4 stores)
         self.nbuckets, self.out_floats = item, out_off
         self.bucket_seg = torch.tensor(item_seg, dtype=torch.int32, device=device)
         self._item_seg, self._nitems = self.bucket_seg, item
@@ -1758,7 +1787,7 @@ class BatchedQSGD(_BatchedBase):
         self._batch = native.QSGDBatch(self._dev[:self._table_words], self.bucket_seg, self.nseg, self.nbuckets, self.n_bit,
                                        self.bits, self.wide,
                                        self._dev[self._table_words:self._dense_at].view(torch.int32) if self.wide else None,
-                                       bucket_hint=hint)
+                                       bucket_hint=hint, dtype=self.dtype)
 
     def graphable(self):
         """The compress launch takes a fresh seed per record when it rounds stochastically: only the deterministic form
@@ -1770,7 +1799,7 @@ class BatchedQSGD(_BatchedBase):
         """With `errs`: error feedback in the same launch (t += ef_scale*err, err = t - decoded, both in place).
         graph_header, table_current: see _choose_header; dense, rng_slot: see BatchedHSQ.encode."""
         counter_seed = self._counter_seed(slot) if rng_slot is None else self._counter_seed(rng_slot, reserved=True)
-        if not self._choose_header(tensors, slot, 8, errs, dense, graph_header, table_current):
+        if not self._choose_header(tensors, slot, self.align, errs, dense, graph_header, table_current):
             return False
         if self.keyed:      # gq_rng = "keyed": every bucket's draws keyed by its norm, the seed never changes
             mode, seed = native.RANDOM_DEVICE_KEYED, (salt * 0x2545F4914F6CDD1D + 0x5851F42D4C957F2D) & (2 ** 63 - 1)

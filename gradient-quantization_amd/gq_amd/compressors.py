@@ -284,8 +284,21 @@ class QSGDCompressor(object):
         self.code_dtype = torch.int32
         self._rng = _rng_mode(args)
 
+    def _bf16_codec(self):
+        """A bfloat16 tensor goes through the multi-tensor launches (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE) as a group of one:
+        the per-tensor entry points are float32 only.  Its signature is the packed wire, [uint8 tensor]."""
+        if getattr(self, "_bf16", None) is None:
+            from .codecs import QSGDCodec      # (codecs imports this module)
+            self._bf16 = QSGDCodec(self, self.size, self.shape, torch.bfloat16)
+        return self._bf16
+
     def compress(self, vec):
         _require_device(vec, "QSGDCompressor.compress")
+        if vec.dtype == torch.bfloat16:
+            codec = self._bf16_codec()
+            wire = torch.empty(codec.nbytes, dtype=torch.uint8, device=vec.device)
+            codec.encode_into(vec, wire, 0, 0)
+            return [wire]
         dev = vec.device
         flat = vec.contiguous().view(-1)
         norm = torch.empty(self.M, dtype=torch.float32, device=dev)
@@ -303,6 +316,12 @@ class QSGDCompressor(object):
         return [norm.view(self.M, 1), signs.view(self.shape), levels.view(self.shape)]
 
     def decompress(self, signature):
+        if len(signature) == 1:      # the packed wire of a bfloat16 tensor (compress): decoded as bfloat16
+            codec = self._bf16_codec()
+            _require_device(signature[0], "QSGDCompressor.decompress")
+            out = torch.empty(self.size, dtype=torch.bfloat16, device=signature[0].device)
+            codec.decode_wire(signature[0], 0, out)
+            return out.view(self.shape)
         norm, signs, l = signature
         assert l.shape == signs.shape
         _require_device(l, "QSGDCompressor.decompress")

@@ -243,8 +243,9 @@ def build_parser():
                    help='--quantizer threshold: fit on every m-th chunk of 4,096 elements, m the largest power of two <= M that leaves a '
                         'tensor at least 16 chunks (else 1)')
     p.add_argument('--param-dtype', dest='param_dtype', type=str, default='float32', choices=['float32', 'bfloat16'],
-                   help='the dtype the model is cast to.  bfloat16 needs --quantizer mx: its kernels read bfloat16 gradients and write '
-                        'bfloat16 means in place (the wire is the float32 one); no other compressor takes them')
+                   help='the dtype the model is cast to.  bfloat16 needs --quantizer mx or qsgd (TernGrad, --c-dim 0, included): their '
+                        'kernels read bfloat16 gradients and write bfloat16 means in place (the wire is the float32 one); no other '
+                        'compressor takes them, nor does --mode ring or --momentum-correction')
     p.add_argument('--seed', type=int, default=1)
     p.add_argument('--train-size', type=int, default=4096, help='synthetic samples per epoch')
     p.add_argument('--log-interval', type=int, default=8, help='iterations between JSON log lines')
@@ -310,9 +311,14 @@ def one_iter(model, loss_func, optimizer, quantizer, train_data, epoch, spans=No
 def check_param_dtype(args):
     """--param-dtype bfloat16 with a quantizer whose kernels take float32 only: refused before anything is built."""
     dtype = getattr(args, "param_dtype", None) or "float32"
-    if dtype == "bfloat16" and args.quantizer != "mx":
-        raise ValueError("--param-dtype bfloat16 needs --quantizer mx: the %s compressor's kernels take float32 gradients only"
+    if dtype == "bfloat16" and args.quantizer not in ("mx", "qsgd"):
+        raise ValueError("--param-dtype bfloat16 needs --quantizer mx or qsgd: the %s compressor's kernels take float32 gradients only"
                          % args.quantizer)
+    if dtype == "bfloat16" and args.quantizer == "qsgd":
+        if getattr(args, "mode", "ps") == "ring":
+            raise ValueError("--param-dtype bfloat16 with --quantizer qsgd is not available in --mode ring")
+        if getattr(args, "momentum_correction", None) is not None:
+            raise ValueError("--param-dtype bfloat16 is not available with --momentum-correction")
     return {"float32": torch.float32, "bfloat16": torch.bfloat16}[dtype]
 
 

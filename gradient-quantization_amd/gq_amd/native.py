@@ -463,30 +463,42 @@ class _QSGDBatchStruct(ctypes.Structure):     # gq_qsgd_batch (include/gq_hsq.h)
     _fields_ = [("struct_bytes", ctypes.c_uint32), ("n_bit", ctypes.c_int32), ("bits", ctypes.c_int32),
                 ("wide", ctypes.c_int32), ("nseg", ctypes.c_int32), ("bucket_hint", ctypes.c_int32), ("nitems", ctypes.c_int64),
                 ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("norm_bits", ctypes.c_void_p),
-                ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("reserved2", ctypes.c_int32)]
+                ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32), ("tensor_type", ctypes.c_int32)]
+
+
+# the tensor-side element types of the multi-tensor QSGD launches (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE): the dtype of the
+# gradients, of `out` and of the dense-copy sources -> gq_qsgd_batch.tensor_type (GQ_QSGD_TENSOR_F32 / GQ_QSGD_TENSOR_BF16)
+_QSGD_TENSOR_TYPE = {torch.float32: 0, torch.bfloat16: 1}
+QSGD_DTYPES = tuple(_QSGD_TENSOR_TYPE)
 
 
 class QSGDBatch(_Tables):
     """The multi-tensor QSGD launches on the packed wire (buckets, or chunks of wide buckets: `wide`)."""
 
-    def __init__(self, seg_table, item_seg, nseg, nitems, n_bit, bits, wide=False, norm_bits=None, bucket_hint=0):
-        """bucket_hint: the bucket width most elements have (0: unknown) -- picks the lanes the bucketed kernels give a bucket."""
+    def __init__(self, seg_table, item_seg, nseg, nitems, n_bit, bits, wide=False, norm_bits=None, bucket_hint=0, dtype=torch.float32):
+        """bucket_hint: the bucket width most elements have (0: unknown) -- picks the lanes the bucketed kernels give a bucket.
+        dtype: float32 or bfloat16 gradients and `out`."""
+        if dtype not in _QSGD_TENSOR_TYPE:
+            raise TypeError("QSGDBatch: the kernels take float32 or bfloat16 tensors, got %s" % (dtype,))
         self.L = lib()
+        self.dtype = dtype
         self.keep = (seg_table, item_seg, norm_bits)
         self.s = _QSGDBatchStruct(ctypes.sizeof(_QSGDBatchStruct), int(n_bit), int(bits), 1 if wide else 0, int(nseg), int(bucket_hint),
                                   int(nitems), _dev_ptr(seg_table, torch.int64, "seg_table").value,
                                   _dev_ptr(item_seg, torch.int32, "item_seg").value,
-                                  _dev_ptr(norm_bits, torch.int32, "norm_bits").value if norm_bits is not None else None, None, 0, 0)
+                                  _dev_ptr(norm_bits, torch.int32, "norm_bits").value if norm_bits is not None else None, None, 0,
+                                  _QSGD_TENSOR_TYPE[dtype])
         self.ref = ctypes.byref(self.s)
 
     def part(self, seg_table, item_seg, nseg, nitems):
-        return QSGDBatch(seg_table, item_seg, nseg, nitems, self.s.n_bit, self.s.bits, bool(self.s.wide), self.keep[2], self.s.bucket_hint)
+        return QSGDBatch(seg_table, item_seg, nseg, nitems, self.s.n_bit, self.s.bits, bool(self.s.wide), self.keep[2], self.s.bucket_hint,
+                         self.dtype)
 
     def compress(self, wire, random_mode, seed, ef_scale=None):
         """ef_scale given: error feedback in the same pass (seg_table[:, 7] = error buffers)."""
         rc = self.L.gq_qsgd_compress_batched(self.ref, _dev_ptr(wire, torch.uint8, "wire"), ctypes.c_int(random_mode),
-                                             ctypes.c_uint64(seed & (2 ** 64 - 1)),
-                                             ctypes.c_float(_NAN if ef_scale is None else ef_scale), _stream())
+                            ctypes.c_uint64(seed & (2 ** 64 - 1)),
+                            ctypes.c_float(_NAN if ef_scale is None else ef_scale), _stream())
         _check(rc, "gq_qsgd_compress_batched")
 
     def decode(self, gathered, R, out, plain=False, tail=None):
@@ -494,13 +506,13 @@ class QSGDBatch(_Tables):
         assert gathered.dtype == torch.uint8 and gathered.dim() == 2 and gathered.shape[0] == R and gathered.is_contiguous()
         if tail is not None:
             rc = self.L.gq_qsgd_decode_sum_batched_tail(self.ref, _dev_ptr(gathered, torch.uint8, "gathered"),
-                                                        ctypes.c_int64(gathered.shape[1]), ctypes.c_int(R),
-                                                        _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0), tail.ref, _stream())
+                                   ctypes.c_int64(gathered.shape[1]), ctypes.c_int(R),
+                                   _dev_ptr(out, self.dtype, "out"), ctypes.c_int(1 if plain else 0), tail.ref, _stream())
             _check(rc, "gq_qsgd_decode_sum_batched_tail")
             return
         rc = self.L.gq_qsgd_decode_sum_batched(self.ref, _dev_ptr(gathered, torch.uint8, "gathered"),
-                                               ctypes.c_int64(gathered.shape[1]), ctypes.c_int(R),
-                                               _dev_ptr(out, torch.float32, "out"), ctypes.c_int(1 if plain else 0), _stream())
+                          ctypes.c_int64(gathered.shape[1]), ctypes.c_int(R),
+                          _dev_ptr(out, self.dtype, "out"), ctypes.c_int(1 if plain else 0), _stream())
         _check(rc, "gq_qsgd_decode_sum_batched")
 
 

@@ -236,10 +236,13 @@ class PSQuantizer(object):
             # A bfloat16 parameter (MXCompressor only: include/gq_mx.h, TENSOR-SIDE TYPE): its codec reads bfloat16 gradients and
             # returns bfloat16 means; its residuals stay float32, whatever the parameter's dtype -- the launches compute them
             # from the unrounded sum.
+            # QSGDCompressor's packed wire likewise (include/gq_hsq.h, QSGD: TENSOR-SIDE TYPE).
             mx = isinstance(self.codecs[-1], MXCodec)
-            if mx and param.dtype != torch.float32:
+            typed = mx or isinstance(self.codecs[-1], QSGDCodec)
+            if typed and param.dtype != torch.float32:
                 self.codecs[-1].set_dtype(param.dtype)
-            err_like = (lambda: torch.zeros(param.shape, dtype=torch.float32, device=param.device)) if mx else (lambda: torch.zeros_like(param))
+            f32_err = mx or (typed and param.dtype != torch.float32)
+            err_like = (lambda: torch.zeros(param.shape, dtype=torch.float32, device=param.device)) if f32_err else (lambda: torch.zeros_like(param))
             if self.error_feedback:
                 param.error = [err_like() for _ in range(args.num_users)]
             if self.error_feedback and self.two_phase:
@@ -854,7 +857,7 @@ class PSQuantizer(object):
                 self._record_dgc_single(i, grad, wire, user)
             elif isinstance(codec, PowerSGDCodec):
                 self._record_psgd_single(i, grad, wire, user, scale)
-            elif self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
+            elif self.error_feedback and isinstance(codec, (MXCodec, QSGDCodec)) and codec.dtype != torch.float32:
                 # a bfloat16 gradient: the sum and the residual in the compress launch itself, which keeps them unrounded (a torch
                 # add_ would narrow grad + scale*error before the residual is taken)
                 flat = grad if grad.is_contiguous() else grad.contiguous()
@@ -1284,6 +1287,9 @@ class PSQuantizer(object):
                         codec.encode_into(g, tmp, 0, 0, out=out, err=param.server_error if ef else None, ef_scale=1.0 if ef else None,
                                           q=param.psgd_server_q, user=codec.SERVER_USER)
                         g = out.view(codec.shape)
+                    elif self.error_feedback and isinstance(codec, QSGDCodec) and codec.dtype != torch.float32:
+                        # (a bfloat16 mean: sum and residual inside the launch, unrounded -- see record(); the launch updates a copy)
+                        g = codec.roundtrip(g.contiguous().clone(), 0, err=param.server_error, ef_scale=1.0)
                     elif self.error_feedback and isinstance(codec, MXCodec) and codec.dtype != torch.float32:
                         # (a bfloat16 mean: sum and residual inside the launch, unrounded -- see record())
                         g = g.contiguous()

@@ -427,8 +427,26 @@ int gq_qsgd_decode_sum(const float *norm, const uint8_t *signs, const void *leve
  * Alignment of the decode: the bucketed form takes any even `gathered` and user_stride_bytes and an `out` that is 8-byte aligned;
  * alignment only picks the kernel, the results are the same.  Wide buckets: `gathered` and user_stride_bytes multiples of 4, `out`
  * of 16, GQ_ERR_INVALID_ARG otherwise.
+ *
+ * TENSOR-SIDE TYPE.  gq_qsgd_batch.tensor_type = GQ_QSGD_TENSOR_BF16 puts bf16 on the tensor side of the three launches below: the
+ * gradients the segment table points at, and `out` (passed as float *, holding uint16_t bf16 bits; the table's `out` offset counts
+ * elements).  A field of the descriptor and not three more entry points: the ABI keeps descriptor structs instead of variants.
+ * Everything else is as above, to the byte: the norms, the draws, the codes -- the wire of a bf16 gradient is the wire of the
+ * float32 tensor with the bits h << 16; error buffers are float32; the dense_table's sources are bf16 and travel as float32
+ * (widened); gq_step_tail is untouched (its rows and `out` are float32).
+ *   widen:  the float32 with the bits h << 16 -- exact, NaNs and signed zeros included.
+ *   narrow: ONE integer round to nearest even, (b + 0x7FFF + ((b >> 16) & 1)) >> 16 of the float32's bits b; every NaN -> 0x7FC0.
+ *   compress: reads widened gradients; between load and store it is the float32 launch.  Under error feedback
+ *     w = widen(grad) + ef_scale * error in float32, narrow(w) is written over grad, and error = w - decode(code) from the
+ *     UNROUNDED w.  (Wide buckets: the norm pass stores nothing; the code pass forms w again from the untouched operands.)
+ *   decode: the float32 sum in payload order and the division as above, narrow() once at the store.
+ * Alignment with bf16: gradients and `out` 2-byte aligned, any even d.  A bucket (chunk) whose first element lies on 16 bytes and
+ * whose width is a multiple of 8 is moved as 16-byte units of 8 elements; every other one by 2-byte accesses -- the results are
+ * the same.  The wire's alignment as above (wide: `gathered` and user_stride_bytes multiples of 4, GQ_ERR_INVALID_ARG otherwise).
  */
 #define GQ_QSGD_WIDE_CHUNK 1024
+#define GQ_QSGD_TENSOR_F32 0
+#define GQ_QSGD_TENSOR_BF16 1
 typedef struct gq_qsgd_batch {
     uint32_t struct_bytes;     /* sizeof(gq_qsgd_batch) */
     int32_t n_bit;             /* qsgd_compressor.py:10 */
@@ -443,7 +461,7 @@ typedef struct gq_qsgd_batch {
     uint32_t *norm_bits;       /* wide only */
     const int64_t *dense_table; /* as gq_hsq_batch.dense_table: copied by gq_qsgd_compress_batched's launch */
     int32_t ndense;
-    int32_t reserved2;
+    int32_t tensor_type;       /* GQ_QSGD_TENSOR_F32 (0; was `reserved2`) or GQ_QSGD_TENSOR_BF16: see TENSOR-SIDE TYPE */
 } gq_qsgd_batch;
 int gq_qsgd_code_bits(int n_bit, int random_mode);
 int gq_qsgd_compress_batched(const gq_qsgd_batch *b, uint8_t *wire, int random_mode, uint64_t seed, float ef_scale,
