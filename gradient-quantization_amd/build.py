@@ -29,7 +29,7 @@ LIBS = {
     os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select (top-k's compaction and decode-mean: csrc/sparse_kernels.hpp)
     os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select (the same kernels: csrc/sparse_kernels.hpp), one magnitude per tensor, a 16-bit word per kept element
     os.path.join(HERE, "libgq_sketch.so"): ["sketch.hip"],        # count sketch: a wire that adds across users; a workgroup per chunk of a window's item list, staged through LDS, no atomics; the decode-mean recovers top-k of the mean with top-k's select (csrc/sparse_kernels.hpp)
-    os.path.join(HERE, "libgq_psgd.so"): ["psgd.hip"],            # low-rank compression (PowerSGD, rank 1 / 2 / 4): project, orthogonalise, back-project, fold, residual; the decode-mean of the factors
+    os.path.join(HERE, "libgq_psgd.so"): ["psgd.hip", "psgd_wide.hip"],      # low-rank compression (PowerSGD): project, orthogonalise, back-project, fold, residual; the decode-mean of the factors.  psgd.hip: rank 1 / 2 / 4 and the entry points; psgd_wide.hip: rank 16 / 32 on the matrix cores
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],    # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)
     os.path.join(HERE, "libgq_rq.so"): ["rq_batched.hip"],        # the ResidualCompressor's stage-2 encode (the same walk) and two-stage decode-mean
     os.path.join(HERE, "libgq_maurey.so"): ["maurey.hip"],        # Maurey sparsification: the sampler's six launches and the decode-mean

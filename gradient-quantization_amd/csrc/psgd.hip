@@ -1,4 +1,4 @@
-// Low-rank gradient compression (PowerSGD, rank 1 / 2 / 4), multi-tensor (segment table) form -- libgq_psgd.so
+// Low-rank gradient compression (PowerSGD, rank 1 / 2 / 4; ranks 16 / 32: csrc/psgd_wide.hip), multi-tensor (segment table) form -- libgq_psgd.so
 // (include/gq_psgd.h: every operation and the shape of every reduction).
 //
 // A record is four launches, five where the residual or the dense decode is asked for:
@@ -22,6 +22,7 @@
 #include "gq_common.hpp"
 #include "gq_lib_prelude.hpp"
 #include "gq_psgd.h"
+#include "psgd_wide.hpp"
 
 #define GQP_API extern "C" __attribute__((visibility("default")))
 
@@ -324,7 +325,8 @@ static int check_batch(const gq_psgd_batch *b, const char *what, bool compress) 
     if (!b || b->struct_bytes != sizeof(gq_psgd_batch)) return fail(GQ_ERR_INVALID_ARG, "%s: descriptor missing or of another size", what);
     if (b->nseg < 1 || b->nitems < 1 || b->nitems > 0x7fffffff || b->ndense < 0)
         return fail(GQ_ERR_INVALID_ARG, "%s: bad sizes (nseg %d, tiles %lld, ndense %d)", what, b->nseg, (long long)b->nitems, b->ndense);
-    if (b->rank != 1 && b->rank != 2 && b->rank != 4) return fail(GQ_ERR_INVALID_ARG, "%s: rank %d (1, 2 or 4)", what, b->rank);
+    if (b->rank != 1 && b->rank != 2 && b->rank != 4 && b->rank != 16 && b->rank != 32)
+        return fail(GQ_ERR_INVALID_ARG, "%s: rank %d (1, 2, 4, 16 or 32)", what, b->rank);
     if (!b->seg_table || !b->item_seg) return fail(GQ_ERR_INVALID_ARG, "%s: null table", what);
     if (compress) {
         if (b->naitems < 1 || b->naitems > 0x7fffffff) return fail(GQ_ERR_INVALID_ARG, "%s: %lld items", what, (long long)b->naitems);
@@ -378,6 +380,11 @@ GQP_API int gq_psgd_compress_batched(const gq_psgd_batch *b, uint8_t *wire, floa
     if (out && (reinterpret_cast<uintptr_t>(out) & 3) != 0) return fail(GQ_ERR_INVALID_ARG, "gq_psgd_compress_batched: out must be 4-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool ef = !isnan(ef_scale);
+    if (b->rank >= 16) {      // the matrix-core launches (csrc/psgd_wide.hip)
+        const char *launch = "";
+        const hipError_t e = gq_psgd_wide_compress(b, wire, ef, ef_scale, out, st, &launch);
+        return e == hipSuccess ? GQ_OK : fail(GQ_ERR_HIP, "gq_psgd_compress_batched (%s): %s", launch, hipGetErrorString(e));
+    }
     switch (b->rank * 2 + (ef ? 1 : 0)) {
     case 2: return compress<1, false>(b, wire, 0.0f, out, st);
     case 3: return compress<1, true>(b, wire, ef_scale, out, st);
@@ -400,6 +407,10 @@ GQP_API int gq_psgd_decode_sum_batched(const gq_psgd_batch *b, const uint8_t *ga
     if ((reinterpret_cast<uintptr_t>(gathered) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 3) != 0)
         return fail(GQ_ERR_INVALID_ARG, "gq_psgd_decode_sum_batched: the gathered wire and out must be 4-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (b->rank >= 16) {
+        const hipError_t e = gq_psgd_wide_decode(b, gathered, user_stride_bytes, R, out, st);
+        return e == hipSuccess ? GQ_OK : fail(GQ_ERR_HIP, "gq_psgd_decode_sum_batched: %s", hipGetErrorString(e));
+    }
     if (b->rank == 1) return decode<1>(b, gathered, user_stride_bytes, R, out, st);
     if (b->rank == 2) return decode<2>(b, gathered, user_stride_bytes, R, out, st);
     return decode<4>(b, gathered, user_stride_bytes, R, out, st);

@@ -2473,9 +2473,14 @@ class BatchedPowerSGD(_ItemGroup):
         self.random = False
         lay = torch.zeros((nseg, 4), dtype=torch.int64)
         aitem_seg, aitem, pw, cp = [], 0, 0, 0
+        wide = R >= 16      # (include/gq_psgd.h, RANKS 16 AND 32: an item of the project launch is 64 rows x one piece of 1,024 columns)
         for s, cd in enumerate(mine):
-            pieces = 1 if cd.m <= P else -(-cd.m // P)
-            items = -(-cd.n // max(1, P // cd.m)) if cd.m <= P else cd.n * pieces
+            if wide:
+                pieces = -(-cd.m // native.PSGD_WIDE_PIECE)
+                items = -(-cd.n // RB) * pieces
+            else:
+                pieces = 1 if cd.m <= P else -(-cd.m // P)
+                items = -(-cd.n // max(1, P // cd.m)) if cd.m <= P else cd.n * pieces
             lay[s, 0], lay[s, 1], lay[s, 2], lay[s, 3] = aitem, pw, cp, cd.param_index << 12
             aitem_seg += [s] * items
             aitem += items
@@ -2486,7 +2491,7 @@ class BatchedPowerSGD(_ItemGroup):
         # scratch (include/gq_psgd.h): written before it is read in every compress
         self._pwork = torch.empty(pw, dtype=torch.float32, device=device)
         self._cpart = torch.empty(cp, dtype=torch.float32, device=device)
-        self._flags = torch.empty(nseg * 4, dtype=torch.int32, device=device)
+        self._flags = torch.empty(nseg * max(4, R), dtype=torch.int32, device=device)
         self._batch = native.PSGDBatch(self._dev[:self._table_words], self.item_seg, nseg, tiles, rank=R, seed=self.seed, lay=self._lay,
                                        aitem_seg=self._aitem_seg, naitems=aitem, pwork=self._pwork, cpart=self._cpart, flags=self._flags)
         self._state_tables = {}

@@ -901,15 +901,18 @@ class SparseTernaryCompressor(object):
 class PowerSGDCompressor(object):
     """Low-rank compression (PowerSGD: Vogels, Karimireddy, Jaggi 2019; no counterpart in the reference's catalogue): the tensor as
     the matrix M of shape[0] rows, one power iteration M Q -> orthogonalise -> M^T Ph from a warm start Q the caller of the kernels
-    owns, rank psgd_rank = 1, 2 or 4 -- include/gq_psgd.h defines every operation's order and rounding.  A tensor that is not a matrix,
+    owns, rank psgd_rank = 1, 2 or 4 -- include/gq_psgd.h defines every operation's order and rounding -- or 16 or 32, on the matrix
+    cores, where the header defines the operations and float64 holds the accuracy.  A tensor that is not a matrix,
     has a side below the rank, or whose factors would be no smaller than the tensor itself, travels uncompressed (`compresses`).
     compress returns the dense decode Ph Q'^T and steps this object's own warm start (user 0, parameter 0); decompress is the
     identity.  HIP kernels only (libgq_psgd.so): a float32 tensor on the device."""
 
+    RANKS = (1, 2, 4, 16, 32)
+
     def __init__(self, size, shape, args):
         r = getattr(args, "psgd_rank", 2)
-        if isinstance(r, bool) or r not in (1, 2, 4):
-            raise ValueError("psgd_rank must be 1, 2 or 4, got %r" % (r,))
+        if isinstance(r, bool) or r not in self.RANKS:
+            raise ValueError("psgd_rank must be 1, 2, 4, 16 or 32, got %r" % (r,))
         seed = getattr(args, "psgd_seed", 0)
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
             raise ValueError("psgd_seed must be an integer in [0, 2^64), got %r" % (seed,))

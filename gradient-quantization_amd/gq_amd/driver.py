@@ -216,9 +216,9 @@ def build_parser():
                         "not in ring mode")
     p.add_argument('--eden-seed', dest='eden_seed', type=int, default=1,
                    help='--quantizer eden: the seed of the four sign words of its rotation (every rank must use the same)')
-    p.add_argument('--psgd-rank', dest='psgd_rank', type=int, default=2, choices=[1, 2, 4],
+    p.add_argument('--psgd-rank', dest='psgd_rank', type=int, default=2, choices=[1, 2, 4, 16, 32],
                    help='--quantizer powersgd: the rank of the two factors a matrix-shaped tensor travels as (vectors, and matrices the '
-                        'factors would not shrink, travel uncompressed)')
+                        'factors would not shrink, travel uncompressed); 16 and 32 run on the matrix cores')
     p.add_argument('--psgd-seed', dest='psgd_seed', type=int, default=0,
                    help="--quantizer powersgd: the seed of the warm starts' first values (per parameter and user, from the counter hash)")
     p.add_argument('--sketch-rows', dest='sketch_rows', type=int, default=3, choices=[1, 3, 5],

@@ -1315,10 +1315,11 @@ class SketchBatch(_ItemBatch):
                             "(set GQ_EXCHANGE=allgather or direct)")
 
 
-# ---- low-rank compression (PowerSGD, rank 1 / 2 / 4): libgq_psgd.so (include/gq_psgd.h) ------------------------------------------
+# ---- low-rank compression (PowerSGD, rank 1 / 2 / 4 / 16 / 32): libgq_psgd.so (include/gq_psgd.h) ------------------------------------------
 PSGD_ABI_VERSION = 1
 PSGD_EXPORTS = ["gq_psgd_abi_version", "gq_psgd_last_error", "gq_psgd_compress_batched", "gq_psgd_decode_sum_batched"]
 PSGD_PIECE = 4096           # GQ_PSGD_PIECE: columns per piece of a long row
+PSGD_WIDE_PIECE = 1024      # GQ_PSGD_WIDE_PIECE: ranks 16 and 32, columns per piece of every row
 PSGD_ROW_BLOCK = 64         # GQ_PSGD_ROW_BLOCK: rows per block of the back-projection, and of a tile
 PSGD_TILE_COLS = 256        # GQ_PSGD_TILE_COLS: columns per tile
 PSGD_HEADER_BYTES = 16      # GQ_PSGD_HEADER_BYTES: n, m, r, 0 in front of a section's factors

@@ -1,7 +1,7 @@
 /*
  * libgq_psgd.so -- low-rank gradient compression (Vogels, Karimireddy, Jaggi, "PowerSGD: Practical Low-Rank Gradient
  * Compression for Distributed Optimization", NeurIPS 2019) on gfx950, rank r = 1, 2 or 4: one power iteration per record
- * from a warm start, modified Gram-Schmidt, error feedback.
+ * from a warm start, modified Gram-Schmidt, error feedback.  Rank 16 and 32 run on the matrix cores: RANKS 16 AND 32 below.
  *
  * A library of its own with the conventions of include/gq_topk.h:
  *   - return value: GQ_OK (0) or a negative GQ_ERR_* code (values of include/gq_hsq.h); gq_psgd_last_error() gives text;
@@ -51,6 +51,26 @@
  *     zero bytes up to a multiple of 16            GQ_PSGD_SECTION_BYTES(n, m, r)
  *
  * No float atomics anywhere: the bytes depend on M, e, Q and the arguments alone, not on the grid or on scheduling.
+ *
+ * RANKS 16 AND 32 (csrc/psgd_wide.hip).  The record is steps 1 - 7 above and the same five launches.  Unchanged: the wire section
+ * { n, m, r, 0 }, Ph[n][r], Q'[m][r], zero bytes, every byte written; the warm-start rule and Q0 (step 6); the reset flags; the
+ * error-feedback placement (M' stored into e by the first launch, e = M' - D by the last); NaN travel (a NaN in M, e or Q reaches
+ * the factors; a column whose pivot is not finite resets); `out`; the dense table; graph replay with no data-dependent launch
+ * argument.  What differs:
+ *   - The ORDER of additions inside a dot product is the kernels' own (the matrix instructions' and the fixed folds of
+ *     csrc/psgd_wide.hip), not THE TREE.  No float atomics: the bytes depend on M, e, Q and the arguments alone, and two compresses
+ *     of the same input and state give the same wire.  Accuracy is held against float64 (tests/test_gpu_psgd_wide.py), not bit for bit.
+ *   - Step 2: every row is cut into pieces of GQ_PSGD_WIDE_PIECE columns; the pieces' sums are added in piece order.
+ *   - Step 3 is the Cholesky form of the same factorisation: G = P^T P accumulated in float64, G = L L^T, Ph = P L^-T with column j
+ *     scaled by nrm[j] / (nrm[j] + 1e-8f), nrm[j] = (float)L[j][j] -- the norm of what the earlier columns leave of column j.
+ *     reset[j] where L[j][j]^2 is not above 2^-40 of G[j][j] (a column that depends on the earlier ones leaves rounding dust of
+ *     float64 there, never exactly nothing), or nrm[j] is 0, infinite or NaN; that column of Ph is written as zeros and plays no
+ *     part in the later columns.
+ *   - Step 4: the row blocks' partial sums are added in block order, as above.  Step 7 and the decode-mean: D, or the sum over the
+ *     payloads, is ONE contraction over k = R * r in payload order, then a true division by (float)R.
+ * Scratch at these ranks: pwork -- a tensor owns n * ceil(m / GQ_PSGD_WIDE_PIECE) * r values; cpart -- ceil(n / 64) * m * r values,
+ * as above; flags -- int32[nseg][r].  An ITEM of launch (A) is one block of 64 rows x one piece: a tensor has
+ * ceil(n / 64) * ceil(m / GQ_PSGD_WIDE_PIECE) items, item = row block * pieces + piece.  Nothing else is new.
  */
 #ifndef GQ_PSGD_H
 #define GQ_PSGD_H
@@ -63,6 +83,7 @@ extern "C" {
 
 #define GQ_PSGD_ABI_VERSION 1
 #define GQ_PSGD_PIECE 4096          /* columns per piece of a long row */
+#define GQ_PSGD_WIDE_PIECE 1024     /* ranks 16 and 32: columns per piece of EVERY row */
 #define GQ_PSGD_ROW_BLOCK 64        /* rows per block of the back-projection; also the rows of a tile */
 #define GQ_PSGD_TILE_COLS 256       /* columns per tile */
 #define GQ_PSGD_HEADER_BYTES 16
@@ -104,7 +125,8 @@ typedef struct gq_psgd_batch {
     int32_t *flags;
     const int64_t *dense_table;
     int32_t ndense;
-    int32_t rank;              /* r: 1, 2 or 4, of every tensor of the group */
+    int32_t rank;              /* r: 1, 2, 4, 16 or 32, of every tensor of the group (16, 32: the item table of (A), pwork and flags
+                                  as RANKS 16 AND 32 states them) */
     uint64_t seed;             /* of Q0 */
 } gq_psgd_batch;
 

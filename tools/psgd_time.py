@@ -18,6 +18,9 @@ Rows (one JSON line each), N(0, 1) gradients:
   resnet50_step   PSQuantizer record + apply over the whole ResNet-50 parameter list, one user, default launches (graph replay),
                   gradients at fixed addresses: --quantizer powersgd --psgd-rank 4 and the same with --ef next to --quantizer sign
                   and --quantizer stc (the in-tree libraries), alternated, three rounds each.  No bar.
+  wide            --rank 16|32 (with --parent-lib DIR holding the parent commit's libgq_psgd.so; replaces only the rows of this case): this
+                  build's launches at that rank on the same two tensor lists against the PARENT's rank 4 launches in the same run --
+                  compress, compress_ef, decode_mean_R1 / _R8; targets at rank 16: compress and decode_mean_R8 <= 1.0 x the parent's.
 Times: tools/mx_time.py's method (HIP events around windows of back-to-back calls, the median window; paths alternated round by
 round, the minimum over the rounds next to every round)."""
 import argparse
@@ -128,6 +131,51 @@ def launches_row(name, shapes, dev, parent_dir):
     return row
 
 
+def wide_row(name, shapes, rank, dev, parent_dir):
+    """This build's rank 16 / 32 launches against the parent build's rank 4 launches on the same tensors, alternated."""
+    torch.manual_seed(1)
+    sizes = [int(torch.Size(s).numel()) for s in shapes]
+    ts = [torch.randn(n, device=dev) for n in sizes]
+    paths = {}
+
+    def build(tag, r):
+        pargs = _args(psgd_rank=r, psgd_seed=1)
+        codecs = [PowerSGDCodec(PowerSGDCompressor(n, tuple(s), pargs), n, tuple(s), param_index=i) for i, (n, s) in enumerate(zip(sizes, shapes))]
+        grp, ub = _group(BatchedPowerSGD, codecs, dev)
+        qs = [cd.warm_start(i, 0, dev) for i, cd in enumerate(codecs)]
+        errs = [torch.zeros(n, device=dev) for n in sizes]
+        wire = torch.zeros((8, ub), dtype=torch.uint8, device=dev)
+        assert grp.encode(ts, wire[0], 0, 0, (None, qs, 0), None)
+        for r8 in range(1, 8):
+            wire[r8].copy_(wire[0])
+        out = torch.empty(grp.out_floats, device=dev)
+        paths[tag + "_compress"] = lambda: grp.encode(ts, wire[0], 0, 0, (None, qs, 0), None)
+        paths[tag + "_compress_ef"] = lambda: grp.encode(ts, wire[0], 0, 0, (errs, qs, 0), 1.0)
+        for R in (1, 8):
+            paths[tag + "_decode_mean_R%d" % R] = lambda R=R: grp._batch.decode(wire[:R], R, out)
+        return errs
+
+    errs = list(build("wide", rank))
+    with other_library(os.path.join(parent_dir, "libgq_psgd.so"), native.PSGDBatch, "libgq_psgd.so", "gq_psgd_", native.PSGD_EXPORTS):
+        errs += build("parent_r4", 4)
+    torch.cuda.synchronize()
+    times = {}
+    for rnd in range(3):
+        for key, fn in paths.items():
+            times.setdefault(key, []).append(graphed(fn))
+            for e in errs:      # (the residual grows with every call: back to zero between the measurements)
+                e.zero_()
+    row = {"case": "wide", "tensors_of": name, "tensors": len(sizes), "elements": sum(sizes), "rank": rank, "yardstick": "the parent build's rank 4 launches, same run",
+           "targets": {"compress": 1.0, "decode_mean_R8": 1.0} if rank == 16 else {}}
+    for key, tt in times.items():
+        row[key + "_us_rounds"] = [round(x, 2) for x in tt]
+        row[key + "_us"] = round(min(tt), 2)
+    for kind in ("compress", "compress_ef", "decode_mean_R1", "decode_mean_R8"):
+        row["%s_over_parent_r4" % kind] = round(row["wide_%s_us" % kind] / row["parent_r4_%s_us" % kind], 3)
+    row["missed"] = [k for k, bar in row["targets"].items() if row["%s_over_parent_r4" % k] > bar]
+    return row
+
+
 def resnet50_rows(dev, shapes):
     torch.manual_seed(0)
     src = [torch.randn(s, device=dev) * 1e-2 for s in shapes]
@@ -160,6 +208,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "psgd_time.jsonl"))
     ap.add_argument("--parent-lib", default=None,
                     help="a directory with an older libgq_sign.so and libgq_drive.so: their launches are the yardsticks; without it the in-tree ones")
+    ap.add_argument("--rank", type=int, default=None, choices=[16, 32],
+                    help="case `wide` alone: this build at that rank against --parent-lib's libgq_psgd.so at rank 4")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     with open(os.path.join(ROOT, "tests", "golden", "resnet50_cifar_shapes.json")) as f:
@@ -167,6 +217,18 @@ def main():
     args = _args(psgd_rank=RANK)
     r50 = [s for s in shapes if PowerSGDCompressor(int(torch.Size(s).numel()), s, args).compresses]
     parent = os.path.abspath(a.parent_lib) if a.parent_lib else None
+    if a.rank is not None:
+        if parent is None:
+            ap.error("--rank needs --parent-lib: the yardstick is the parent build's libgq_psgd.so")
+        wide = [s for s in shapes if PowerSGDCompressor(int(torch.Size(s).numel()), s, _args(psgd_rank=a.rank)).compresses]
+        rows = [wide_row("single_25m", [(4096, 6144)], a.rank, dev, parent), wide_row("resnet50_list", wide, a.rank, dev, parent)]
+        kept = []
+        if os.path.exists(a.out):      # (this rank's rows are replaced, the other rank's and the other cases stay)
+            with open(a.out) as f:
+                kept = [json.loads(ln) for ln in f if ln.strip()]
+            kept = [r for r in kept if not (r.get("case") == "wide" and r.get("rank") == a.rank)]
+        write_rows(a.out, kept + rows)
+        return
     write_rows(a.out, [launches_row("single_25m", [(4096, 6144)], dev, parent), launches_row("resnet50_list", r50, dev, parent)]
                + resnet50_rows(dev, shapes))
 
