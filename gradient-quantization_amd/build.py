@@ -28,6 +28,7 @@ LIBS = {
     os.path.join(HERE, "libgq_eden.so"): ["eden.hip"],            # the rotated 2- / 3- / 4-bit compressor (EDEN): Lloyd-Max codes of the rotated block and one f32 scale, on the same rotation
     os.path.join(HERE, "libgq_thr.so"): ["thr.hip"],              # threshold sparsification: a fitted or given threshold, a sparse wire with a variable count, no select (top-k's compaction and decode-mean: csrc/sparse_kernels.hpp)
     os.path.join(HERE, "libgq_stc.so"): ["stc.hip"],              # sparse ternary compression: top-k's select (the same kernels: csrc/sparse_kernels.hpp), one magnitude per tensor, a 16-bit word per kept element
+    os.path.join(HERE, "libgq_ctk.so"): ["ctk.hip"],              # chunked top-k: every item of 4,096 elements keeps its own largest len // cr; the select runs inside one workgroup's LDS, one launch, no scratch
     os.path.join(HERE, "libgq_sketch.so"): ["sketch.hip"],        # count sketch: a wire that adds across users; a workgroup per chunk of a window's item list, staged through LDS, no atomics; the decode-mean recovers top-k of the mean with top-k's select (csrc/sparse_kernels.hpp)
     os.path.join(HERE, "libgq_psgd.so"): ["psgd.hip", "psgd_wide.hip"],      # low-rank compression (PowerSGD): project, orthogonalise, back-project, fold, residual; the decode-mean of the factors.  psgd.hip: rank 1 / 2 / 4 and the entry points; psgd_wide.hip: rank 16 / 32 on the matrix cores
     os.path.join(HERE, "libgq_pvq.so"): ["pvq_batched.hip"],    # the multi-tensor ProbabilisticVectorCompressor encode; shares the walk with pvq.hip (csrc/pvq_walk.hpp)

@@ -18,7 +18,8 @@ device memory, through gq_amd.native).
     STCCodec                   SparseTernaryCompressor: a 16-byte header (k, the magnitude), a uint32 start per item of 4,096 elements, then k 16-bit words
     PowerSGDCodec              PowerSGDCompressor: a 16-byte header (n, m, r), then the factors Ph (n x r) and Q' (m x r) as f32
     SketchCodec                CountSketchCompressor: a 16-byte header (n, rows, windows), then rows x windows x 4,096 f32 cells that add across users
-    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC / BatchedPowerSGD / BatchedSketch
+    ChunkTopKCodec             ChunkTopKCompressor: per item of 4,096 elements len // cr uint16 positions at static offsets, then their f32 values
+    BatchedDrive / BatchedEden / BatchedThr / BatchedSTC / BatchedChunkTopK / BatchedPowerSGD / BatchedSketch
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
 
@@ -32,7 +33,7 @@ import os
 import torch
 
 from . import exchange, native
-from .compressors import (CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (ChunkTopKCompressor, CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           PowerSGDCompressor, QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor, _next_seed,
                           _require_device)
 
@@ -751,6 +752,35 @@ class STCCodec(_SparseCodec):
         """(k, mu) of this tensor's section of one user's wire: a read of two words, with a synchronisation."""
         w = wire_user[off:off + 8].cpu().numpy()
         return int(w[:4].view("<u4")[0]), float(w[4:8].view("<f4")[0])
+
+
+def ctk_kept(numel, cr):
+    """K of include/gq_ctk.h: what a tensor's items keep between them, len // cr each."""
+    return (numel // native.CTK_CHUNK) * (native.CTK_CHUNK // cr) + (numel % native.CTK_CHUNK) // cr
+
+
+def ctk_section_bytes(numel, cr):
+    """Bytes of one tensor's section of the chunked top-k wire (include/gq_ctk.h): K uint16 positions and K f32 values, each array
+    with zero bytes up to a multiple of 16; no header."""
+    k = ctk_kept(numel, cr)
+    return _up(2 * k) + _up(4 * k)
+
+
+class ChunkTopKCodec(TopKCodec):
+    """ChunkTopKCompressor on the HIP kernels (libgq_ctk.so).  Wire per tensor: the items' kept positions (uint16, inside the item)
+    at static offsets, then their f32 values -- ctk_section_bytes.  Every call is a one-tensor BatchedChunkTopK; roundtrip /
+    encode_decode_into return the compress launch's own dense decode (w * mask).  A tensor shorter than cr keeps nothing: its section
+    is empty, which TopKCodec's handling of k = 0 covers."""
+
+    def __init__(self, compressor, numel, shape, cr=None):
+        """cr: the ratio where there is no compressor object to ask."""
+        self.c, self.numel, self.shape = compressor, numel, shape
+        self.cr = int(compressor.cr if cr is None else cr)
+        if not native.CTK_MIN_CR <= self.cr <= native.CTK_MAX_CR or not 1 <= numel < 2 ** 31:
+            raise ValueError("ChunkTopKCodec: cr = %d (%d ... %d) for a tensor of %d elements (1 ... 2^31 - 1)"
+                             % (self.cr, native.CTK_MIN_CR, native.CTK_MAX_CR, numel))
+        self.k = ctk_kept(numel, self.cr)
+        self.nbytes = ctk_section_bytes(numel, self.cr)
 
 
 def psgd_section_bytes(n, m, r):
@@ -2446,6 +2476,36 @@ class BatchedSTC(BatchedTopK):
 STCCodec.GROUP = BatchedSTC
 
 
+class BatchedChunkTopK(_ItemGroup):
+    """All ChunkTopKCompressor tensors of one cr in ONE gq_ctk_compress_batched launch and ONE gq_ctk_decode_sum_batched launch
+    (include/gq_ctk.h).  No draws and no scratch: both replay from a HIP graph.  The compress also writes the dense decode (w * mask)
+    where a caller asks for it (the two-phase re-compress returns it); with error feedback it updates the gradient and the residual
+    in the same launch, from the values it holds in registers."""
+
+    WIRE_ALIGN = 16
+
+    @staticmethod
+    def eligible(codec):
+        return type(codec) is ChunkTopKCodec
+
+    @staticmethod
+    def group_key(codec):
+        return (codec.cr,)
+
+    def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
+        mine = [codecs[i] for i in idxs]
+        self.cr = mine[0].cr
+        assert all(cd.cr == self.cr for cd in mine)
+        # an item is a chunk of elements; 16-byte aligned views in the output buffer: the launches store float4 there
+        nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
+                                      lambda cd: -(-cd.numel // native.CTK_CHUNK), {4: [native.CTK_CHUNK // self.cr] * len(mine)}, 4)
+        self.random = False
+        self._batch = native.CTKBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.cr)
+
+
+ChunkTopKCodec.GROUP = BatchedChunkTopK
+
+
 class BatchedPowerSGD(_ItemGroup):
     """All PowerSGDCompressor tensors of one rank in ONE gq_psgd_compress_batched sequence (project, orthogonalise, back-project,
     fold, + the residual launch under error feedback or where the dense decode is asked for -- include/gq_psgd.h) and ONE
@@ -2544,6 +2604,8 @@ def default_codec_factory(compressor, numel, shape, packed6=False):
         return ThrCodec(compressor, numel, shape)
     if isinstance(compressor, SparseTernaryCompressor):
         return STCCodec(compressor, numel, shape)
+    if isinstance(compressor, ChunkTopKCompressor):
+        return ChunkTopKCodec(compressor, numel, shape)
     if isinstance(compressor, CountSketchCompressor):
         # (too few items for two per cell window: uncompressed, as the low-rank compressor's small tensors)
         return SketchCodec(compressor, numel, shape) if compressor.compresses else DenseCodec(compressor, numel, shape)

@@ -898,6 +898,38 @@ class SparseTernaryCompressor(object):
         return signature
 
 
+class ChunkTopKCompressor(object):
+    """Chunked (block-wise) top-k (no counterpart in the reference's catalogue): every item of 4,096 consecutive elements keeps its
+    own largest len // cr elements, top-k's key and tie rule inside the item -- include/gq_ctk.h.  The select needs nothing outside
+    one workgroup: one launch, the gradient read once.  An item whose scale is small keeps elements a global top-k would drop (use
+    error feedback).  compress returns the dense decode and decompress is the identity, as for TopKSparsificationCompressor's device
+    path.  HIP kernels only (libgq_ctk.so): a float32 tensor on the device."""
+
+    MIN_CR, MAX_CR = 2, 4096      # GQ_CTK_MIN_CR / GQ_CTK_MAX_CR
+
+    def __init__(self, size, shape, args):
+        cr = getattr(args, "cr", None)
+        if isinstance(cr, bool) or not isinstance(cr, int) or not self.MIN_CR <= cr <= self.MAX_CR:
+            raise ValueError("cr must be an integer in [%d, %d] for the chunked top-k compressor, got %r" % (self.MIN_CR, self.MAX_CR, cr))
+        self.size, self.shape, self.cr = size, shape, cr
+        self.k = (size // 4096) * (4096 // cr) + (size % 4096) // cr
+
+    def compress(self, vec):
+        from .codecs import ChunkTopKCodec      # (codecs imports this module)
+        if vec.device.type != "cuda" or vec.dtype != torch.float32:
+            raise TypeError("ChunkTopKCompressor: the kernels take float32 tensors on the HIP device (there is no CPU path), "
+                            "got %s on %s" % (vec.dtype, vec.device))
+        n = vec.numel()
+        codecs = self.__dict__.setdefault("_codecs", {})
+        codec = codecs.get(n)
+        if codec is None:
+            codec = codecs[n] = ChunkTopKCodec(self, n, (n,))
+        return codec.roundtrip(vec.reshape(-1), 0).view(vec.shape)
+
+    def decompress(self, signature):
+        return signature
+
+
 class PowerSGDCompressor(object):
     """Low-rank compression (PowerSGD: Vogels, Karimireddy, Jaggi 2019; no counterpart in the reference's catalogue): the tensor as
     the matrix M of shape[0] rows, one power iteration M Q -> orthogonalise -> M^T Ph from a warm start Q the caller of the kernels
@@ -1014,4 +1046,4 @@ class CountSketchCompressor(object):
 __all__ = ["IdenticalCompressor", "QSGDCompressor", "NearestNeighborCompressor", "ProbabilisticScalarCompressor",
            "ProbabilisticVectorCompressor", "ResidualCompressor", "SignSGDCompressor", "TopKSparsificationCompressor",
            "MaureySparsification", "MXCompressor", "DriveCompressor", "EdenCompressor", "ThresholdSparsificationCompressor", "SparseTernaryCompressor",
-           "PowerSGDCompressor", "CountSketchCompressor"]
+           "PowerSGDCompressor", "CountSketchCompressor", "ChunkTopKCompressor"]

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 import torch.optim as optim
 
 from .datasets import OnDiskClassification
-from .compressors import (CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
+from .compressors import (ChunkTopKCompressor, CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MaureySparsification, MXCompressor, NearestNeighborCompressor, ProbabilisticVectorCompressor,
                           PowerSGDCompressor, QSGDCompressor, ResidualCompressor, SignSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor, TopKSparsificationCompressor)
 from .quantizers import Quantizer
 
@@ -50,6 +50,7 @@ quantizer_choices = {          # main.py:20-26
     'eden': EdenCompressor,                    # the rotated 2- / 3- / 4-bit compressor (--eden-bits, --eden-scale, --eden-seed): bits + 0.125, likewise
     'threshold': ThresholdSparsificationCompressor,      # what exceeds a fitted or a given threshold (--thr-stages, --thr-value, --thr-cap-percent, --thr-fit-stride, --cr), likewise
     'stc': SparseTernaryCompressor,            # sparse ternary compression: top-k's kept set (--cr) at one magnitude, a 16-bit word per kept element, likewise
+    'chunktopk': ChunkTopKCompressor,          # chunked top-k: every item of 4,096 elements keeps its own largest len // cr (--cr, 2 ... 4096): one launch, the gradient read once, likewise
     'sketch': CountSketchCompressor,           # a count sketch (--sketch-rows, --sketch-cr, --sketch-seed, --sketch-ef, --cr): the one wire that adds across users; top-k of the mean is recovered once, likewise
     'powersgd': PowerSGDCompressor,            # low-rank compression (--psgd-rank, --psgd-seed): one power iteration per record from a warm start, the two factors on the wire, likewise
 }

@@ -1259,6 +1259,39 @@ class STCBatch(_ItemBatch):
                              ("sums", sums, torch.float64)))
 
 
+# ---- chunked top-k, a select per item of 4,096 elements: libgq_ctk.so (include/gq_ctk.h) -----------------------------------------
+CTK_ABI_VERSION = 1
+CTK_EXPORTS = ["gq_ctk_abi_version", "gq_ctk_last_error", "gq_ctk_compress_batched", "gq_ctk_decode_sum_batched"]
+CTK_CHUNK = 4096            # GQ_CTK_CHUNK: elements per item
+CTK_MIN_CR, CTK_MAX_CR = 2, 4096      # GQ_CTK_MIN_CR / GQ_CTK_MAX_CR
+
+CTK_LIBRARY = Library("libgq_ctk.so", "GQ_CTK_LIB_PATH", "gq_ctk_", CTK_ABI_VERSION, CTK_EXPORTS)
+CTK_LIB_PATH, ctk_lib = CTK_LIBRARY.path, CTK_LIBRARY.load
+
+
+class _CTKBatchStruct(ctypes.Structure):      # gq_ctk_batch (include/gq_ctk.h)
+    _fields_ = [("struct_bytes", ctypes.c_uint32), ("nseg", ctypes.c_int32), ("nitems", ctypes.c_int64),
+                ("seg_table", ctypes.c_void_p), ("item_seg", ctypes.c_void_p), ("dense_table", ctypes.c_void_p),
+                ("ndense", ctypes.c_int32), ("cr", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(_CTKBatchStruct) == 48      # (csrc/ctk.hip asserts the same of gq_ctk_batch)
+
+
+class CTKBatch(_ItemBatch):
+    """The two launches of libgq_ctk.so: gq_ctk_compress_batched (a workgroup per item selects the item's own len // cr largest
+    elements in LDS and writes its run of the section, + the dense decode and the residual) and gq_ctk_decode_sum_batched.  No
+    scratch: both are one launch over the segment table."""
+
+    LIBRARY, STRUCT = CTK_LIBRARY, _CTKBatchStruct
+
+    def __init__(self, seg_table, item_seg, nseg, nitems, cr=256):
+        _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, cr=int(cr))
+
+    def part(self, seg_table, item_seg, nseg, nitems):
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.cr)
+
+
 # ---- count sketch, a wire that adds across users: libgq_sketch.so (include/gq_sketch.h) -----------------------------------------
 SKETCH_ABI_VERSION = 1
 SKETCH_EXPORTS = ["gq_sketch_abi_version", "gq_sketch_last_error", "gq_sketch_build_lists", "gq_sketch_compress_batched",

@@ -31,7 +31,7 @@ import warnings
 import torch
 
 from . import exchange, native
-from .compressors import (CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, PowerSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
+from .compressors import (ChunkTopKCompressor, CountSketchCompressor, DriveCompressor, EdenCompressor, IdenticalCompressor, MXCompressor, PowerSGDCompressor, SparseTernaryCompressor, ThresholdSparsificationCompressor,
                           TopKSparsificationCompressor, _next_seed, shared_seeds)
 
 # The C++ walks of the parameter list (csrc/host_ext.cpp -> gq_amd/_gq_host.so, built by build.py): the grads, their
@@ -48,7 +48,7 @@ if os.environ.get("GQ_HOST_EXT", "1") != "0":
 
 from .codecs import (  # noqa: F401  (re-exported: tests and tools import the codecs from here)
     BatchedDGC, BatchedDrive, BatchedEden, BatchedHSQ, BatchedMaurey, BatchedMX, BatchedMXR, BatchedPVQ, BatchedQSGD, BatchedResidual, BatchedSign, BatchedTopK, DenseCodec, GenericCodec, HSQCodec,
-    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec, BatchedPowerSGD, PowerSGDCodec, BatchedSketch, SketchCodec,
+    MaureyCodec, MXCodec, QSGDCodec, ResidualCodec, SignCodec, TopKCodec, BatchedThr, ThrCodec, BatchedSTC, STCCodec, BatchedChunkTopK, ChunkTopKCodec, BatchedPowerSGD, PowerSGDCodec, BatchedSketch, SketchCodec,
     _BatchedBase, _DATA_PTR, _DTYPE_OF, _F32_ONLY, _GET_DEVICE, _IS_CONTIGUOUS, _esize, _kernel_copy, _up, aggregate_fma, default_codec_factory,
     quantizer_codec_factory,
     wire_levels_mode)
@@ -191,6 +191,12 @@ class PSQuantizer(object):
             if odd:
                 raise ValueError("the sparse ternary compressor takes float32 parameters only (its kernels read and write float32 "
                                  "gradients), got %s" % ", ".join(odd))
+        if isinstance(Compressor, type) and issubclass(Compressor, ChunkTopKCompressor):
+            # (include/gq_ctk.h: float32 tensors only)
+            odd = sorted(set(str(p.dtype) for p in self.parameters if p.dtype != torch.float32))
+            if odd:
+                raise ValueError("the chunked top-k compressor takes float32 parameters only (its kernels read and write float32 "
+                                 "gradients), got %s" % ", ".join(odd))
         if isinstance(Compressor, type) and issubclass(Compressor, PowerSGDCompressor):
             # (include/gq_psgd.h: float32 tensors only; a user is 12 bits of the warm starts' key, the last one the server's)
             odd = sorted(set(str(p.dtype) for p in self.parameters if p.dtype != torch.float32))
@@ -302,7 +308,7 @@ class PSQuantizer(object):
         BatchedQSGD.place_lone_buckets(self.codecs)
         self._dgc_single = {}       # parameter index -> its one-tensor BatchedDGC (the per-tensor route of a record)
         topk_group = BatchedTopK if self.dgc_m is None else BatchedDGC
-        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC, BatchedPowerSGD, BatchedSketch):
+        for cls in (BatchedHSQ, BatchedPVQ, BatchedResidual, BatchedQSGD, topk_group, BatchedSign, BatchedMaurey, BatchedMX, BatchedMXR, BatchedDrive, BatchedEden, BatchedThr, BatchedSTC, BatchedChunkTopK, BatchedPowerSGD, BatchedSketch):
             keyed = {}
             for i, c in enumerate(self.codecs):
                 if cls.eligible(c):
@@ -407,6 +413,9 @@ class PSQuantizer(object):
                              "the top-k wire (--quantizer topk)")
         if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
             raise ValueError("momentum_correction is not available with the sparse ternary compressor: momentum factor masking is built "
+                             "on the top-k wire (--quantizer topk)")
+        if isinstance(Compressor, type) and issubclass(Compressor, ChunkTopKCompressor):
+            raise ValueError("momentum_correction is not available with the chunked top-k compressor: momentum factor masking is built "
                              "on the top-k wire (--quantizer topk)")
         if isinstance(Compressor, type) and issubclass(Compressor, CountSketchCompressor):
             raise ValueError("momentum_correction is not available with the sketch compressor: momentum factor masking is built "
@@ -1418,6 +1427,9 @@ class RingQuantizer(PSQuantizer):
         if isinstance(Compressor, type) and issubclass(Compressor, SparseTernaryCompressor):
             raise ValueError("the sparse ternary compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
                              "itself, and its wire carries one magnitude for the whole kept set")
+        if isinstance(Compressor, type) and issubclass(Compressor, ChunkTopKCompressor):
+            raise ValueError("the chunked top-k compressor is not available in ring mode: a hop ships the wire as the decoded tensor "
+                             "itself, and its wire drops the signed zeros and NaNs of the dense decode")
         if isinstance(Compressor, type) and issubclass(Compressor, CountSketchCompressor):
             raise ValueError("the sketch compressor is not available in ring mode: a hop ships the wire as the decoded tensor itself, "
                              "and a sketch's decode keeps the heavy hitters only")
