@@ -19,6 +19,7 @@ device memory, through gq_amd.native).
     PowerSGDCodec              PowerSGDCompressor: a 16-byte header (n, m, r), then the factors Ph (n x r) and Q' (m x r) as f32
     SketchCodec                CountSketchCompressor: a 16-byte header (n, rows, windows), then rows x windows x 4,096 f32 cells that add across users
     ChunkTopKCodec             ChunkTopKCompressor: per item of 4,096 elements len // cr uint16 positions at static offsets, then their f32 values
+                               (ctk_values = "packed16": two uint32 bounds per item, then one 16-bit word of position, level and sign per kept element)
     BatchedDrive / BatchedEden / BatchedThr / BatchedSTC / BatchedChunkTopK / BatchedPowerSGD / BatchedSketch
                                every tensor of a model in one launch per stage (descriptor tables, HIP-graph friendly)
     GenericCodec               any other compressor object: its own compress / decompress, tensors on the wire as they are
@@ -766,21 +767,37 @@ def ctk_section_bytes(numel, cr):
     return _up(2 * k) + _up(4 * k)
 
 
+def ctk_packed_section_bytes(numel, cr):
+    """Bytes of one tensor's PACKED16 section (include/gq_ctk.h): two uint32 bounds per item of 4,096 elements and K 16-bit words,
+    each array with zero bytes up to a multiple of 16."""
+    return _up(8 * -(-numel // native.CTK_CHUNK)) + _up(2 * ctk_kept(numel, cr))
+
+
 class ChunkTopKCodec(TopKCodec):
     """ChunkTopKCompressor on the HIP kernels (libgq_ctk.so).  Wire per tensor: the items' kept positions (uint16, inside the item)
-    at static offsets, then their f32 values -- ctk_section_bytes.  Every call is a one-tensor BatchedChunkTopK; roundtrip /
-    encode_decode_into return the compress launch's own dense decode (w * mask).  A tensor shorter than cr keeps nothing: its section
-    is empty, which TopKCodec's handling of k = 0 covers."""
+    at static offsets, then their f32 values -- ctk_section_bytes; values = "packed16": the items' bounds { T, H }, then a 16-bit
+    word of position, level and sign per kept element -- ctk_packed_section_bytes.  Every call is a one-tensor BatchedChunkTopK;
+    roundtrip / encode_decode_into return the compress launch's own dense decode (w * mask; packed16: the quantised values).  A
+    tensor shorter than cr keeps nothing: its f32 section is empty, which TopKCodec's handling of k = 0 covers (a packed16 section
+    still holds the item's bounds, zero)."""
 
-    def __init__(self, compressor, numel, shape, cr=None):
-        """cr: the ratio where there is no compressor object to ask."""
+    def __init__(self, compressor, numel, shape, cr=None, values=None):
+        """cr, values: the ratio and the value format where there is no compressor object to ask."""
         self.c, self.numel, self.shape = compressor, numel, shape
         self.cr = int(compressor.cr if cr is None else cr)
+        self.values = (getattr(compressor, "values", "f32") if values is None else values)
+        if self.values not in native.CTK_VALUES:
+            raise ValueError("ChunkTopKCodec: ctk_values must be one of %s, got %r" % (", ".join(native.CTK_VALUES), self.values))
         if not native.CTK_MIN_CR <= self.cr <= native.CTK_MAX_CR or not 1 <= numel < 2 ** 31:
             raise ValueError("ChunkTopKCodec: cr = %d (%d ... %d) for a tensor of %d elements (1 ... 2^31 - 1)"
                              % (self.cr, native.CTK_MIN_CR, native.CTK_MAX_CR, numel))
         self.k = ctk_kept(numel, self.cr)
-        self.nbytes = ctk_section_bytes(numel, self.cr)
+        self.nbytes = (ctk_packed_section_bytes if self.values == "packed16" else ctk_section_bytes)(numel, self.cr)
+
+    def _decode_rows(self, gathered, off, R, out, plain=False):
+        if self.values == "packed16":      # (k = 0: the section is not empty, and the launch writes the +0)
+            return _SparseCodec._decode_rows(self, gathered, off, R, out, plain=plain)
+        return TopKCodec._decode_rows(self, gathered, off, R, out, plain=plain)
 
 
 def psgd_section_bytes(n, m, r):
@@ -2477,10 +2494,11 @@ STCCodec.GROUP = BatchedSTC
 
 
 class BatchedChunkTopK(_ItemGroup):
-    """All ChunkTopKCompressor tensors of one cr in ONE gq_ctk_compress_batched launch and ONE gq_ctk_decode_sum_batched launch
-    (include/gq_ctk.h).  No draws and no scratch: both replay from a HIP graph.  The compress also writes the dense decode (w * mask)
-    where a caller asks for it (the two-phase re-compress returns it); with error feedback it updates the gradient and the residual
-    in the same launch, from the values it holds in registers."""
+    """All ChunkTopKCompressor tensors of one (cr, value format) in ONE gq_ctk_compress_batched launch and ONE
+    gq_ctk_decode_sum_batched launch, or their *_packed_batched forms (include/gq_ctk.h).  No draws and no scratch: both replay from a
+    HIP graph.  The compress also writes the dense decode (w * mask; packed16: the quantised values) where a caller asks for it (the
+    two-phase re-compress returns it); with error feedback it updates the gradient and the residual in the same launch, from the
+    values it holds in registers."""
 
     WIRE_ALIGN = 16
 
@@ -2490,17 +2508,17 @@ class BatchedChunkTopK(_ItemGroup):
 
     @staticmethod
     def group_key(codec):
-        return (codec.cr,)
+        return (codec.cr, codec.values)
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         mine = [codecs[i] for i in idxs]
-        self.cr = mine[0].cr
-        assert all(cd.cr == self.cr for cd in mine)
+        self.cr, self.values = mine[0].cr, mine[0].values
+        assert all((cd.cr, cd.values) == (self.cr, self.values) for cd in mine)
         # an item is a chunk of elements; 16-byte aligned views in the output buffer: the launches store float4 there
         nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense,
                                       lambda cd: -(-cd.numel // native.CTK_CHUNK), {4: [native.CTK_CHUNK // self.cr] * len(mine)}, 4)
         self.random = False
-        self._batch = native.CTKBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.cr)
+        self._batch = native.CTKBatch(self._dev[:self._table_words], self.item_seg, nseg, item, self.cr, self.values)
 
 
 ChunkTopKCodec.GROUP = BatchedChunkTopK

@@ -903,15 +903,21 @@ class ChunkTopKCompressor(object):
     own largest len // cr elements, top-k's key and tie rule inside the item -- include/gq_ctk.h.  The select needs nothing outside
     one workgroup: one launch, the gradient read once.  An item whose scale is small keeps elements a global top-k would drop (use
     error feedback).  compress returns the dense decode and decompress is the identity, as for TopKSparsificationCompressor's device
-    path.  HIP kernels only (libgq_ctk.so): a float32 tensor on the device."""
+    path.  ctk_values = "packed16": a kept element travels as one 16-bit word -- its position in the item, one of eight magnitudes
+    between the item's smallest and largest kept key, its sign -- and decodes to that magnitude (PACKED16 of the header): 2 bytes
+    where "f32", the default, takes 6.  HIP kernels only (libgq_ctk.so): a float32 tensor on the device."""
 
     MIN_CR, MAX_CR = 2, 4096      # GQ_CTK_MIN_CR / GQ_CTK_MAX_CR
+    VALUES = ("f32", "packed16")
 
     def __init__(self, size, shape, args):
         cr = getattr(args, "cr", None)
         if isinstance(cr, bool) or not isinstance(cr, int) or not self.MIN_CR <= cr <= self.MAX_CR:
             raise ValueError("cr must be an integer in [%d, %d] for the chunked top-k compressor, got %r" % (self.MIN_CR, self.MAX_CR, cr))
-        self.size, self.shape, self.cr = size, shape, cr
+        values = getattr(args, "ctk_values", "f32")
+        if values not in self.VALUES:
+            raise ValueError("ctk_values must be one of %s for the chunked top-k compressor, got %r" % (", ".join(self.VALUES), values))
+        self.size, self.shape, self.cr, self.values = size, shape, cr, values
         self.k = (size // 4096) * (4096 // cr) + (size % 4096) // cr
 
     def compress(self, vec):

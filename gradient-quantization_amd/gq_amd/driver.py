@@ -217,6 +217,10 @@ def build_parser():
                         "not in ring mode")
     p.add_argument('--eden-seed', dest='eden_seed', type=int, default=1,
                    help='--quantizer eden: the seed of the four sign words of its rotation (every rank must use the same)')
+    p.add_argument('--ctk-values', dest='ctk_values', default='f32', choices=['f32', 'packed16'],
+                   help='--quantizer chunktopk: what a kept element travels as -- f32: a uint16 position and the value, 6 bytes; packed16: '
+                        'one 16-bit word of position, one of eight magnitudes between the item\'s smallest and largest kept key, and sign '
+                        '(rounded to the nearest level: use --ef)')
     p.add_argument('--psgd-rank', dest='psgd_rank', type=int, default=2, choices=[1, 2, 4, 16, 32],
                    help='--quantizer powersgd: the rank of the two factors a matrix-shaped tensor travels as (vectors, and matrices the '
                         'factors would not shrink, travel uncompressed); 16 and 32 run on the matrix cores')

@@ -1261,9 +1261,11 @@ class STCBatch(_ItemBatch):
 
 # ---- chunked top-k, a select per item of 4,096 elements: libgq_ctk.so (include/gq_ctk.h) -----------------------------------------
 CTK_ABI_VERSION = 1
-CTK_EXPORTS = ["gq_ctk_abi_version", "gq_ctk_last_error", "gq_ctk_compress_batched", "gq_ctk_decode_sum_batched"]
+CTK_EXPORTS = ["gq_ctk_abi_version", "gq_ctk_last_error", "gq_ctk_compress_batched", "gq_ctk_decode_sum_batched",
+               "gq_ctk_compress_packed_batched", "gq_ctk_decode_sum_packed_batched"]
 CTK_CHUNK = 4096            # GQ_CTK_CHUNK: elements per item
 CTK_MIN_CR, CTK_MAX_CR = 2, 4096      # GQ_CTK_MIN_CR / GQ_CTK_MAX_CR
+CTK_VALUES = ("f32", "packed16")      # the value formats of a kept element: the f32 as it is; a 16-bit word of position, level and sign (PACKED16)
 
 CTK_LIBRARY = Library("libgq_ctk.so", "GQ_CTK_LIB_PATH", "gq_ctk_", CTK_ABI_VERSION, CTK_EXPORTS)
 CTK_LIB_PATH, ctk_lib = CTK_LIBRARY.path, CTK_LIBRARY.load
@@ -1281,15 +1283,22 @@ assert ctypes.sizeof(_CTKBatchStruct) == 48      # (csrc/ctk.hip asserts the sam
 class CTKBatch(_ItemBatch):
     """The two launches of libgq_ctk.so: gq_ctk_compress_batched (a workgroup per item selects the item's own len // cr largest
     elements in LDS and writes its run of the section, + the dense decode and the residual) and gq_ctk_decode_sum_batched.  No
-    scratch: both are one launch over the segment table."""
+    scratch: both are one launch over the segment table.  values = "packed16": the same two on the PACKED16 section,
+    gq_ctk_compress_packed_batched and gq_ctk_decode_sum_packed_batched (the descriptor is the same: the format is the entry point)."""
 
     LIBRARY, STRUCT = CTK_LIBRARY, _CTKBatchStruct
 
-    def __init__(self, seg_table, item_seg, nseg, nitems, cr=256):
+    def __init__(self, seg_table, item_seg, nseg, nitems, cr=256, values="f32"):
+        if values not in CTK_VALUES:
+            raise ValueError("CTKBatch: values must be one of %s, got %r" % (", ".join(CTK_VALUES), values))
         _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, cr=int(cr))
+        self.values = values
+        if values == "packed16":
+            self._compress_name, self._decode_name = "gq_ctk_compress_packed_batched", "gq_ctk_decode_sum_packed_batched"
+            self._decode = getattr(self.L, self._decode_name)
 
     def part(self, seg_table, item_seg, nseg, nitems):
-        return type(self)(seg_table, item_seg, nseg, nitems, self.s.cr)
+        return type(self)(seg_table, item_seg, nseg, nitems, self.s.cr, self.values)
 
 
 # ---- count sketch, a wire that adds across users: libgq_sketch.so (include/gq_sketch.h) -----------------------------------------

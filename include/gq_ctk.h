@@ -27,6 +27,30 @@
  * GQ_CTK_SECTION_BYTES(n, cr) bytes, 6 per kept element.  Every byte, pads included, is written by every compress, and the bytes
  * depend on the input alone.  A compress writes the tensors' sections and the dense copies of dense_table and no other byte of the
  * wire, and loads none of it.
+ *
+ * PACKED16, the second value format (gq_ctk_compress_packed_batched / gq_ctk_decode_sum_packed_batched): one 16-bit word per kept
+ * element, its magnitude as one of eight levels spaced evenly in KEY space -- roughly geometrically in magnitude: the key is a
+ * monotone, piecewise-linear stand-in for log2 |w| -- between two bounds of the item.  The kept set, the key and the tie rule are
+ * the ones above.  All of it is integer arithmetic on uint32 / uint64.  For an item with k_t > 0:
+ *     T = the k_t-th largest key (the smallest kept key), H = the largest key among the item's len_t elements, D = H - T
+ * and for a kept element with key k and value w:
+ *     level  l  = D == 0 ? 0 : ((uint64)(k - T) * 14 + D) / (2 * D)        0 ... 7, round half up in key space
+ *     dk        = T + (uint32)(((uint64)l * D + 3) / 7)                     T <= dk <= H
+ *     decoded   = float_from_bits(dk | (bits(w) & 0x80000000))
+ *     word      = pos | l << 12 | (bits(w) >> 31) << 15                     pos = the index inside the item, 0 ... 4095
+ * so that 14 * |dk - k| <= D + 6.  A dropped element decodes to w * 0 as above.  The formulas' bits are the contract for
+ * non-finite input too: a NaN's key is 0x7fffffff, so an item that holds one has H = 0x7fffffff, the NaN sits on level 7 and
+ * decodes to a NaN, and an infinity decodes to whatever level it falls on between T and H.
+ * WIRE SECTION of one tensor, items = ceil(n / 4096):
+ *     uint32 bounds[items][2]   { T, H } of every item; { 0, 0 } where k_t == 0
+ *     zero bytes up to a multiple of 16
+ *     uint16 word[K]            item t's entries at t * kf ... t * kf + k_t - 1, positions ascending
+ *     zero bytes up to a multiple of 16
+ * GQ_CTK_PACKED_SECTION_BYTES(n, cr) bytes, 2 per kept element and 8 per item.  As above: every byte, pads included, is written by
+ * every compress, the bytes depend on the input alone, and a compress loads none of the wire.
+ * Error feedback is unchanged -- w = v + ef_scale * err, err = w - decoded -- but for a kept element that difference is now the
+ * quantisation error, not zero.  Rounding is to the nearest level only.
+ * A decode computes D = H - T in uint32 arithmetic, whatever the bounds are.
  */
 #ifndef GQ_CTK_H
 #define GQ_CTK_H
@@ -43,6 +67,7 @@ extern "C" {
 #define GQ_CTK_MAX_CR 4096
 #define GQ_CTK_KEPT(n, cr) (((int64_t)(n) / GQ_CTK_CHUNK) * (GQ_CTK_CHUNK / (cr)) + ((int64_t)(n) % GQ_CTK_CHUNK) / (cr))
 #define GQ_CTK_SECTION_BYTES(n, cr) ((2 * GQ_CTK_KEPT(n, cr) + 15) / 16 * 16 + (4 * GQ_CTK_KEPT(n, cr) + 15) / 16 * 16)
+#define GQ_CTK_PACKED_SECTION_BYTES(n, cr) ((8 * (((int64_t)(n) + GQ_CTK_CHUNK - 1) / GQ_CTK_CHUNK) + 15) / 16 * 16 + (2 * GQ_CTK_KEPT(n, cr) + 15) / 16 * 16)
 
 /*
  * The tensors of one group, table-driven like gq_topk_batch: ONE launch serves all of them.
@@ -88,6 +113,15 @@ int gq_ctk_compress_batched(const gq_ctk_batch *b, uint8_t *wire, float ef_scale
  */
 int gq_ctk_decode_sum_batched(const gq_ctk_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out,
                               int plain, void *stream);
+
+/*
+ * The same two launches on the PACKED16 section (above): the same arguments, conventions and refusals.  The compress's `out` and
+ * its residual take `decoded`, the quantised value; the decode-mean rebuilds every magnitude from the item's { T, H } of that
+ * payload (read at any alignment) and adds in gq_ctk_decode_sum_batched's order.
+ */
+int gq_ctk_compress_packed_batched(const gq_ctk_batch *b, uint8_t *wire, float ef_scale, float *out, void *stream);
+int gq_ctk_decode_sum_packed_batched(const gq_ctk_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out,
+                                     int plain, void *stream);
 
 #ifdef __cplusplus
 }

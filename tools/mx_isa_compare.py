@@ -9,7 +9,9 @@ below) is a list of csrc files, the number of kernels each holds and a key funct
     rotq  drive.hip and eden.hip, 15 + 45 kernels (csrc/rotq_kernels.hpp), matched by library, kind (compress / decode /
           decode-streams), bits, scale mode, error feedback and rotation kind (Signs / Stepped / Streamed);
     sparse topk.hip, stc.hip, thr.hip and maurey.hip, 4 x 9 kernels (csrc/sparse_kernels.hpp), matched by library, the launch's
-          stage (the word in front of `_kernel`) and error feedback.
+          stage (the word in front of `_kernel`) and error feedback;
+    ctk   ctk.hip, 6 kernels, matched by stage (compress / decode), error feedback and value format (f32 / packed16).
+A tree may hold kernels the parent has not (ctk: the packed16 ones): every kernel of the parent is compared, the others are not listed.
 Both trees' files are compiled with build.py's flags + --save-temps into scratch directories (no GPU needed); a kernel's key is
 read off the template arguments in its mangled name, whatever the function itself is called.  Per kernel: the instruction count
 (the .s text of the function, labels, directives and comments dropped), the registers and the scratch / LDS bytes of the kernel's
@@ -85,12 +87,22 @@ def sparse_key(symbol):
     return stage, ("ef" if int(ef[-1]) else "noef") if ef else "-"
 
 
+def ctk_key(symbol):
+    """(stage, ef, value format) of a kernel of ctk.hip: the first bool of a compress is error feedback; the last bool behind it,
+    or a decode's only one, is the PACKED16 format (the first build's kernels have no such argument: f32)."""
+    bools = [int(v) for v in re.findall(r"Lb(\d)E", template_args(symbol)[0])]
+    if "compress_kernel" in symbol:
+        return "compress", "ef" if bools[0] else "noef", "packed16" if bools[1:] == [1] else "f32"
+    return "decode", "-", "packed16" if bools == [1] else "f32"
+
+
 # family -> ((csrc file, kernels in it), ...), the key function, the key's column names and format, whether its kernels stay in
 # registers (any scratch or LDS is an error) or use LDS by design (other bytes than the parent's are)
 FAMILIES = {
     "mx": ((("mx.hip", 56), ("mxr.hip", 56)), mx_key, "kind format mode ef type", "%-8s %-8s %-6s %-2s %-4s", True),
     "rotq": ((("drive.hip", 15), ("eden.hip", 45)), rotq_key, "kind bits scale ef rotation", "%-14s %-2s %-8s %-2s %-8s", True),
     "sparse": ((("topk.hip", 9), ("stc.hip", 9), ("thr.hip", 9), ("maurey.hip", 9)), sparse_key, "stage ef", "%-7s %-4s", False),
+    "ctk": ((("ctk.hip", 6),), ctk_key, "stage ef values", "%-8s %-4s %-8s", False),
 }
 
 
@@ -136,13 +148,14 @@ def main():
     for fam in families:
         files, key_of, columns, fmt, in_registers = FAMILIES[fam]
         text += ["# tools/mx_isa_compare.py: the kernels of %s, the parent commit against this tree (gfx950, build.py's flags)."
-                 % (", ".join(name for name, _ in files[:-1]) + " and " + files[-1][0]),
+                 % " and ".join(filter(None, [", ".join(name for name, _ in files[:-1]), files[-1][0]])),
                  "# columns: library %s | instructions parent new | VGPRs parent new | SGPRs parent new |" % columns,
                  "#          scratch bytes parent new | LDS bytes parent new | instruction text with labels renumbered"]
         for name, count in files:
             old, new = kernels(build_asm(os.path.abspath(a.parent), name), key_of), kernels(build_asm(ROOT, name), key_of)
-            assert sorted(old) == sorted(new) and len(new) == count, "%s: %d kernels against %d, %d expected" % (name, len(old), len(new), count)
-            for key in sorted(new):
+            # (a tree may add kernels: the parent's are the ones compared, every one of them)
+            assert set(old) <= set(new) and len(new) == count, "%s: %d kernels against %d, %d expected" % (name, len(old), len(new), count)
+            for key in sorted(old):
                 (t0, m0), (t1, m1) = old[key], new[key]
                 same = t0 == t1
                 total, differ = total + 1, differ + (not same)
