@@ -13,6 +13,8 @@
 //   estimate a workgroup per item: a row's window of T (which fits the L2) staged into LDS and gathered from there, the signs from a
 //            wave-uniform word (a wave's 64 elements share it, the lane is the bit), the median network -> est.
 //   select   top-k's radix select, count, scan (csrc/sparse_kernels.hpp) on est; store: est where kept, +0 elsewhere.
+//   recover  (the chunked recovery, in place of estimate, select and store) a workgroup per item: the estimates stay in registers, the
+//            item's own select runs in a 256-bin LDS histogram, the dense output is written once -- see recover_kernel.
 // Every launch's arguments depend on the layout and the seed alone.
 #include <math.h>
 
@@ -46,7 +48,8 @@ constexpr int HDR = GQ_SKETCH_HEADER_BYTES;
 constexpr int MAX_ROWS = GQ_SKETCH_MAX_ROWS;
 constexpr uint64_t G = gqk_host::G, M = gqk_host::M;
 static_assert(CHUNK == 4096 && CHUNK == 16 * THREADS, "a staging thread moves four float4; 12-bit cells");
-static_assert(sizeof(gq_sketch_batch) == 168, "gq_sketch_batch: the layout the ctypes binding declares (gq_amd/native.py)");
+static_assert(sizeof(gq_sketch_batch) == 176, "gq_sketch_batch: the layout the ctypes binding declares (gq_amd/native.py)");
+static_assert(offsetof(gq_sketch_batch, recover) == GQ_SKETCH_BATCH_BYTES_V1, "{ recover, cr } follow the whole version-1 descriptor");
 
 // what the hash needs of every row, by value in the launch: K_j, A_j and A_j^-1 mod 4096
 struct Rows {
@@ -268,6 +271,161 @@ __global__ __launch_bounds__(THREADS) void estimate_kernel(const int64_t *__rest
     }
 }
 
+// ---- the chunked recovery (include/gq_sketch.h: CHUNKED RECOVERY): estimate, select and store in ONE launch, a workgroup per item ----
+// The estimates never leave the workgroup: after the rows' gathers and the median a thread holds those of the elements t = tid + 256 q,
+// q = 0 .. 15, in registers, so ELEMENT ORDER is (q, wave, lane) -- not chunked top-k's (step, thread, slot of a float4), whose
+// select this one otherwise follows (csrc/ctk.hip):
+//   select   the item's kt-th largest key by radix, 8 + 8 + 8 + 7 bits from the top in a 256-bin LDS histogram (integer LDS adds: the
+//            counts do not depend on their order); wave 0 walks the bins from the top, four a lane, fixes the digit and the remaining
+//            rank and clears what it read.  -> the threshold key T and `need`, the ties to keep.  An element past the item's end
+//            enters as key 0 at the highest indices: it can only swell the lowest bin, below everything the select looks for, and as
+//            a tie it ranks behind every real one, of which there are at least `need`.
+//   tie rank the output is dense, so nothing is compacted and only the TIES are ranked: per q the wave's lanes with key == T as a
+//            ballot, a lane's rank inside the wave the popcount of the bits below it, the waves' totals of all sixteen q through
+//            LDS behind one barrier, q ascending as a running carry.
+//   store    estimate or +0, one 4-byte store a lane and q: a wave writes 256 consecutive bytes; the item's tail is guarded by len.
+constexpr int SELECT_BINS = 256;
+static_assert(SELECT_BINS == THREADS && SELECT_BINS == 4 * 64, "a bin a thread to clear; wave 0 walks the bins four a lane");
+
+__device__ constexpr int digit_shift(int p) { return p == 0 ? 23 : (p == 1 ? 15 : (p == 2 ? 7 : 0)); }
+__device__ constexpr int digit_bits(int p) { return p == 3 ? 7 : 8; }
+
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t x) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+
+template <int R>
+__global__ __launch_bounds__(THREADS) void recover_kernel(const int64_t *__restrict__ seg_table, const int32_t *__restrict__ item_seg,
+                                                          const int64_t *__restrict__ lay, const float *__restrict__ table,
+                                                          float *__restrict__ out, Rows rows, int cr) {
+    __shared__ __attribute__((aligned(16))) float win[CHUNK];
+    __shared__ uint32_t hist[SELECT_BINS];
+    __shared__ uint32_t picked[2];                     // the pass's prefix and remaining rank
+    __shared__ uint32_t ties[PER_THREAD][WAVES];       // per q and wave: its keys == T
+    const int64_t item = blockIdx.x;
+    const int seg = item_seg[item];
+    const int64_t *rec = seg_table + 8 * (int64_t)seg;
+    const int64_t n = rec[1], nwin = rec[6], li = item - rec[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t len = (uint32_t)(n - li * CHUNK < CHUNK ? n - li * CHUNK : CHUNK);
+    const uint32_t kt = len / (uint32_t)cr;
+    hist[tid] = 0u;
+    float est[PER_THREAD];
+    uint32_t key[PER_THREAD];
+    {      // estimate_kernel's row loop, statement for statement (that kernel keeps its own text: the global recovery's instructions stay)
+        const uint32_t uwv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wv);      // (uniform: the sign words are the wave's)
+        float val[R][PER_THREAD];
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            const uint64_t h = gqx::splitmix_fin(rows.key[j] + (uint64_t)(li + 1) * G);
+            const int64_t v = (int64_t)(((h >> 32) * (uint64_t)nwin) >> 32);
+            const float *T = table + (lay[seg] + j * nwin + v) * CHUNK;
+            if (j) __syncthreads();      // (the last row's readers)
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                *reinterpret_cast<float4 *>(win + 4 * (tid + THREADS * p)) = *reinterpret_cast<const float4 *>(T + 4 * (tid + THREADS * p));
+            __syncthreads();
+            uint32_t c = (rows.mul[j] * tid + ((uint32_t)h & (uint32_t)MASK)) & MASK;
+            const uint32_t step = (rows.mul[j] * (uint32_t)THREADS) & MASK;
+#pragma unroll
+            for (int q = 0; q < PER_THREAD; ++q) {      // element t = tid + 256 q: its sign word, t >> 6 = wv + 4 q, is the wave's
+                const uint64_t w = sign_word(rows.key[j], (uint32_t)li, uwv + 4u * q);
+                val[j][q] = flip(win[c], (uint32_t)(w >> lane) & 1u);
+                c = (c + step) & MASK;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < PER_THREAD; ++q) {
+            float p[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) p[j] = val[j][q];
+            est[q] = median<R>(p);
+            key[q] = tid + THREADS * q < len ? key_of(est[q]) : 0u;
+        }
+    }
+    // (hist was cleared in front of the first row's barrier)
+
+    // ---- the select: T = the kt-th largest key, need = how many keys == T are kept
+    uint32_t T = NO_KEY, need = 0;
+    if (kt != 0) {      // (the same for the whole workgroup)
+        uint32_t prefix = 0, kr = kt;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            constexpr uint32_t ALL = 0xffffffffu;
+            const int shift = digit_shift(p), hi = shift + digit_bits(p);
+            const uint32_t mask = ~(ALL << digit_bits(p));
+#pragma unroll
+            for (int q = 0; q < PER_THREAD; ++q) {
+                const uint32_t k = key[q];
+                if ((k >> hi) == (prefix >> hi)) atomicAdd(&hist[(k >> shift) & mask], 1u);
+            }
+            __syncthreads();
+            if (wv == 0) {      // lane l: bins 255 - 4 l downwards, the highest first; it clears what it read
+                uint32_t c[4], sum = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int b = SELECT_BINS - 1 - 4 * (int)lane - j;
+                    c[j] = hist[b];
+                    hist[b] = 0u;
+                    sum += c[j];
+                }
+                const uint32_t incl = wave_inclusive_scan(sum);
+                uint32_t cum = incl - sum;
+                if (cum < kr && kr <= incl) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        if (kr <= cum + c[j]) {
+                            picked[0] = prefix | ((uint32_t)(SELECT_BINS - 1 - 4 * (int)lane - j) << shift);
+                            picked[1] = kr - cum;
+                            break;
+                        }
+                        cum += c[j];
+                    }
+                }
+            }
+            __syncthreads();      // (the next pass writes `picked` behind its own first barrier: every read below is done by then)
+            prefix = picked[0];
+            kr = picked[1];
+        }
+        T = prefix;
+        need = kr;
+    }
+
+    // ---- the ties in element order: (q, wave, lane)
+    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    uint32_t eq_mask = 0, rank_in_wave[PER_THREAD / 4] = {};      // (a rank is at most 63: four to a register, a byte each)
+#pragma unroll
+    for (int q = 0; q < PER_THREAD; ++q) {
+        const bool is_eq = key[q] == T;
+        const uint64_t me = __ballot(is_eq);
+        eq_mask |= (is_eq ? 1u : 0u) << q;
+        rank_in_wave[q / 4] |= (uint32_t)__popcll(me & below) << (8 * (q & 3));
+        if (lane == 0) ties[q][wv] = (uint32_t)__popcll(me);
+    }
+    __syncthreads();
+    float *o = out + rec[5] + li * CHUNK;
+    uint32_t carry = 0;      // the ties of the steps before q
+#pragma unroll
+    for (int q = 0; q < PER_THREAD; ++q) {
+        uint32_t before = carry;
+#pragma unroll
+        for (int j = 0; j < WAVES; ++j) {
+            const uint32_t x = ties[q][j];
+            if (j < (int)wv) before += x;
+            carry += x;
+        }
+        before += (rank_in_wave[q / 4] >> (8 * (q & 3))) & 0xffu;
+        const bool kept = key[q] > T || (((eq_mask >> q) & 1u) && before < need);
+        if (tid + THREADS * q < len) o[tid + THREADS * q] = kept ? est[q] : 0.0f;
+    }
+}
+
 __global__ __launch_bounds__(THREADS) void count_kernel(const int64_t *__restrict__ dec_table, const int32_t *__restrict__ item_seg,
                                                         const int32_t *__restrict__ state, int32_t *__restrict__ counts) {
     __shared__ uint32_t lds[2][WAVES];
@@ -345,16 +503,32 @@ static Rows rows_of(const gq_sketch_batch *b) {
     return r;
 }
 
+// a descriptor of the version-1 size has no { recover, cr }: the global recovery
+static bool chunked(const gq_sketch_batch *b) {
+    return b->struct_bytes == sizeof(gq_sketch_batch) && b->recover == GQ_SKETCH_RECOVER_CHUNKED;
+}
+
+// (gqsp::check_batch_common's checks and texts, but for the size: this descriptor has two)
 static int check_batch(const gq_sketch_batch *b, const char *what, bool compress, bool decode) {
-    const int rc = gqsp::check_batch_common(b, what);
-    if (rc != GQ_OK) return rc;
+    if (!b || (b->struct_bytes != sizeof(gq_sketch_batch) && b->struct_bytes != GQ_SKETCH_BATCH_BYTES_V1))
+        return fail(GQ_ERR_INVALID_ARG, "%s: descriptor missing or of another size", what);
+    if (b->nseg < 1 || b->nitems < 1 || b->nitems > 0x7fffffff || b->ndense < 0)
+        return fail(GQ_ERR_INVALID_ARG, "%s: bad sizes (nseg %d, nitems %lld, ndense %d)", what, b->nseg, (long long)b->nitems, b->ndense);
+    if (!b->seg_table || !b->item_seg) return fail(GQ_ERR_INVALID_ARG, "%s: null table", what);
+    if (b->struct_bytes == sizeof(gq_sketch_batch)) {
+        if (b->recover != GQ_SKETCH_RECOVER_GLOBAL && b->recover != GQ_SKETCH_RECOVER_CHUNKED)
+            return fail(GQ_ERR_INVALID_ARG, "%s: recover = %d (0: global, 1: chunked)", what, b->recover);
+        if (chunked(b) && (b->cr < GQ_SKETCH_MIN_CR || b->cr > GQ_SKETCH_MAX_CR))
+            return fail(GQ_ERR_INVALID_ARG, "%s: cr = %d (%d ... %d with the chunked recovery)", what, b->cr, GQ_SKETCH_MIN_CR,
+                        GQ_SKETCH_MAX_CR);
+    }
     if (b->rows != 1 && b->rows != 3 && b->rows != 5) return fail(GQ_ERR_INVALID_ARG, "%s: rows = %d (1, 3 or 5)", what, b->rows);
     if (b->nwindows < 1 || b->nwindows > 0x7fffffff || b->nunits < 1 || b->nunits > 0x7fffffff)
         return fail(GQ_ERR_INVALID_ARG, "%s: bad sizes (windows %lld, units %lld)", what, (long long)b->nwindows, (long long)b->nunits);
     if (!b->lay || !b->win_tab) return fail(GQ_ERR_INVALID_ARG, "%s: null table", what);
     if (compress && (!b->unit_tab || !b->list || !b->part || (b->ndense > 0 && !b->dense_table)))
         return fail(GQ_ERR_INVALID_ARG, "%s: null table or scratch buffer", what);
-    if (decode && (!b->table || !b->est || !b->dec_table || !b->hist || !b->state || !b->counts))
+    if (decode && (!b->table || (!chunked(b) && (!b->est || !b->dec_table || !b->hist || !b->state || !b->counts))))
         return fail(GQ_ERR_INVALID_ARG, "%s: null scratch buffer", what);
     return GQ_OK;
 }
@@ -376,6 +550,14 @@ static int decode_launches(const gq_sketch_batch *b, const uint8_t *gathered, in
     hipLaunchKernelGGL(sum_kernel, dim3((unsigned)b->nwindows), block, 0, st, b->seg_table, b->lay, b->win_tab, gathered, stride, R, b->table,
                        ef ? b->etab : nullptr);
     GQL_CHECK_LAUNCH(what);
+    if (chunked(b)) {      // the estimate, the select and the store as one launch, the select per item
+        if (b->rows == 1) hipLaunchKernelGGL(recover_kernel<1>, items, block, 0, st, b->seg_table, b->item_seg, b->lay, b->table, out, rows, b->cr);
+        else if (b->rows == 3) hipLaunchKernelGGL(recover_kernel<3>, items, block, 0, st, b->seg_table, b->item_seg, b->lay, b->table, out, rows, b->cr);
+        else hipLaunchKernelGGL(recover_kernel<5>, items, block, 0, st, b->seg_table, b->item_seg, b->lay, b->table, out, rows, b->cr);
+        GQL_CHECK_LAUNCH(what);
+        if (ef) return sketch_launches(b, out, nullptr, 1, st, what);
+        return GQ_OK;
+    }
     if (b->rows == 1) hipLaunchKernelGGL(estimate_kernel<1>, items, block, 0, st, b->seg_table, b->item_seg, b->lay, b->table, b->est, rows);
     else if (b->rows == 3) hipLaunchKernelGGL(estimate_kernel<3>, items, block, 0, st, b->seg_table, b->item_seg, b->lay, b->table, b->est, rows);
     else hipLaunchKernelGGL(estimate_kernel<5>, items, block, 0, st, b->seg_table, b->item_seg, b->lay, b->table, b->est, rows);

@@ -717,6 +717,7 @@ class SketchCodec(_SparseCodec):
                              % (numel, compressor.rows, compressor.sketch_cr))
         self.c, self.numel, self.shape = compressor, numel, shape
         self.k, self.rows, self.seed, self.nwin, self.items = compressor.k, compressor.rows, compressor.seed, compressor.nwin, compressor.items
+        self.recover, self.cr = compressor.recover, compressor.cr      # ("chunked": every item keeps its own len // cr estimates)
         self.cells = self.rows * self.nwin * native.SKETCH_CHUNK
         self.nbytes = sketch_section_bytes(numel, compressor.rows, compressor.sketch_cr)
         self.E = None
@@ -2415,13 +2416,14 @@ class BatchedSketch(_ItemGroup):
 
     @staticmethod
     def group_key(codec):
-        return (codec.rows, codec.seed)
+        return (codec.rows, codec.seed, codec.recover, codec.cr if codec.recover == "chunked" else 0)
 
     def __init__(self, codecs, offsets, idxs, device, slots, user_bytes, dense=None):
         import numpy as np
         mine = [codecs[i] for i in idxs]
-        self.rows, self.seed = mine[0].rows, mine[0].seed
-        assert all((cd.rows, cd.seed) == (self.rows, self.seed) for cd in mine)
+        self.rows, self.seed, self.recover, self.cr = mine[0].rows, mine[0].seed, mine[0].recover, mine[0].cr
+        assert all(self.group_key(cd) == self.group_key(mine[0]) for cd in mine)
+        chunked = self.recover == "chunked"
         CH, UN = native.SKETCH_CHUNK, native.SKETCH_CHUNK_ITEMS
         nseg, item = self._item_setup(codecs, offsets, idxs, device, slots, user_bytes, dense, lambda cd: cd.items,
                                       {4: [cd.k for cd in mine], 6: [cd.nwin for cd in mine]}, 1)
@@ -2445,23 +2447,25 @@ class BatchedSketch(_ItemGroup):
              "unit_tab": as_dev(np.concatenate(unit_tab), torch.int32),
              "list": as_dev(np.concatenate(lists).view(np.int32), torch.int32),
              # scratch (include/gq_sketch.h): written before it is read, but for the histograms, which every decode leaves zero again
-             "part": torch.empty(U * CH, dtype=torch.float32, device=device), "table": torch.empty(W * CH, dtype=torch.float32, device=device),
-             "est": torch.empty(self.out_floats, dtype=torch.float32, device=device),
-             "hist": torch.zeros(nseg * native.SKETCH_HIST_BINS, dtype=torch.int32, device=device),
-             "state": torch.empty(nseg * 4, dtype=torch.int32, device=device), "counts": torch.empty(item * 2, dtype=torch.int32, device=device)}
-        dec = self._layout.clone()
-        dec[:, 0] = t["est"].data_ptr() + 4 * dec[:, 5]
-        t["dec_table"] = dec.view(-1).to(device)
+             "part": torch.empty(U * CH, dtype=torch.float32, device=device), "table": torch.empty(W * CH, dtype=torch.float32, device=device)}
+        if not chunked:      # (the chunked recovery selects inside its one launch: no estimates in memory, no select scratch)
+            t.update({"est": torch.empty(self.out_floats, dtype=torch.float32, device=device),
+                      "hist": torch.zeros(nseg * native.SKETCH_HIST_BINS, dtype=torch.int32, device=device),
+                      "state": torch.empty(nseg * 4, dtype=torch.int32, device=device),
+                      "counts": torch.empty(item * 2, dtype=torch.int32, device=device)})
+            dec = self._layout.clone()
+            dec[:, 0] = t["est"].data_ptr() + 4 * dec[:, 5]
+            t["dec_table"] = dec.view(-1).to(device)
         tables = [cd.E for cd in mine]
         if any(e is not None for e in tables):
-            if not all(e is not None and e.dtype == torch.float32 and e.is_contiguous() and e.numel() == cd.cells and e.device == t["est"].device
+            if not all(e is not None and e.dtype == torch.float32 and e.is_contiguous() and e.numel() == cd.cells and e.device == t["table"].device
                        for e, cd in zip(tables, mine)):
                 raise ValueError("BatchedSketch: the error tables must be contiguous float32 tensors of rows * nwin * 4096 cells on the "
                                  "group's device, one for every tensor of the group")
             t["etab"] = torch.tensor([e.data_ptr() for e in tables], dtype=torch.int64).to(device)
         self._tables, self._errors = t, tables
         self._batch = native.SketchBatch(self._dev[:self._table_words], self.item_seg, nseg, item, rows=self.rows, seed=self.seed,
-                                         nwindows=W, nunits=U, tables=t)
+                                         nwindows=W, nunits=U, tables=t, recover=self.recover, cr=self.cr if chunked else 0)
 
     def encode(self, tensors, wire_user, slot, salt, errs=None, ef_scale=None, **kw):
         if errs is not None:

@@ -997,7 +997,8 @@ class CountSketchCompressor(object):
     the one wire here that ADDS across users.  sketch_rows r = 1, 3 or 5 rows of nwin = max(1, ceil(items / (sketch_cr * r))) windows
     of 4,096 cells, items = ceil(size / 4096); a hierarchical hash of (sketch_seed, row, item, position) -- include/gq_sketch.h defines
     the hash, the order of every sum and the recovery to the bit.  The decode recovers top-k of the MEAN, k = size // cr, from the
-    cell-wise mean of the users' sketches.  A tensor with 2 * r * nwin > items travels uncompressed (`compresses`).  compress returns
+    cell-wise mean of the users' sketches; with sketch_recover = "chunked" every item of 4,096 elements keeps its own len // cr largest
+    estimates instead (2 <= cr <= 4096), in one launch.  A tensor with 2 * r * nwin > items travels uncompressed (`compresses`).  compress returns
     the decode of this one tensor's own sketch and decompress is the identity, as for the sparsifiers' device paths.  HIP kernels only
     (libgq_sketch.so): a float32 tensor on the device."""
 
@@ -1017,7 +1018,15 @@ class CountSketchCompressor(object):
         seed = 0 if seed is None else seed
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
             raise ValueError("sketch_seed must be an integer in [0, 2^64), got %r" % (seed,))
+        recover = getattr(args, "sketch_recover", None)
+        recover = "global" if recover is None else recover
+        if recover not in ("global", "chunked"):
+            raise ValueError("sketch_recover must be 'global' or 'chunked', got %r" % (recover,))
+        if recover == "chunked" and not 2 <= cr <= 4096:
+            raise ValueError("cr must be in 2 ... 4096 with sketch_recover = 'chunked' (an item of 4,096 elements keeps its own "
+                             "len // cr estimates), got %r" % (cr,))
         self.size, self.shape, self.cr, self.rows, self.sketch_cr, self.seed = size, tuple(shape), cr, rows, C, seed
+        self.recover = recover
         self.ef = bool(getattr(args, "sketch_ef", False))
         self.k = size // cr
         self.items, self.nwin = self.layout(size, rows, C)

@@ -236,6 +236,10 @@ def build_parser():
     p.add_argument('--sketch-ef', dest='sketch_ef', action='store_true',
                    help="--quantizer sketch: FetchSGD's error accumulation -- what the decode does not keep stays in a table per "
                         "parameter on the decoding side and is added to the next mean (not --ef, which keeps a residual per user)")
+    p.add_argument('--sketch-recover', dest='sketch_recover', default='global', choices=['global', 'chunked'],
+                   help='--quantizer sketch: which estimates of the mean the decode keeps -- global: the numel // cr largest of a tensor '
+                        '(eleven launches); chunked: every item of 4,096 elements its own len // cr largest, selected inside ONE '
+                        'launch that never writes the estimates to memory (needs 2 <= --cr <= 4096)')
     p.add_argument('--thr-stages', dest='thr_stages', type=int, default=3, choices=list(range(9)),
                    help='--quantizer threshold: passes of the threshold fit (a count-adaptive multi-stage exponential fit of the tail of '
                         '|g|, aiming at numel // cr kept elements); 0: no fit, the fixed threshold --thr-value')

@@ -1302,13 +1302,15 @@ class CTKBatch(_ItemBatch):
 
 
 # ---- count sketch, a wire that adds across users: libgq_sketch.so (include/gq_sketch.h) -----------------------------------------
-SKETCH_ABI_VERSION = 1
+SKETCH_ABI_VERSION = 2
 SKETCH_EXPORTS = ["gq_sketch_abi_version", "gq_sketch_last_error", "gq_sketch_build_lists", "gq_sketch_compress_batched",
                   "gq_sketch_decode_sum_batched"]
 SKETCH_CHUNK = 4096         # GQ_SKETCH_CHUNK: elements per item, cells per window
 SKETCH_CHUNK_ITEMS = 8      # GQ_SKETCH_CHUNK_ITEMS: list entries per chunk
 SKETCH_HEADER_BYTES = 16    # GQ_SKETCH_HEADER_BYTES: n, r, nwin, 0 in front of a section's cells
 SKETCH_HIST_BINS = 2048     # GQ_SKETCH_HIST_BINS: histogram words per tensor
+SKETCH_RECOVER = {"global": 0, "chunked": 1}      # GQ_SKETCH_RECOVER_*: which elements the decode keeps
+SKETCH_CHUNKED_CR = (2, 4096)                     # GQ_SKETCH_MIN_CR, GQ_SKETCH_MAX_CR: cr of the chunked recovery
 
 SKETCH_LIBRARY = Library("libgq_sketch.so", "GQ_SKETCH_LIB_PATH", "gq_sketch_", SKETCH_ABI_VERSION, SKETCH_EXPORTS)
 SKETCH_LIB_PATH, sketch_lib = SKETCH_LIBRARY.path, SKETCH_LIBRARY.load
@@ -1331,26 +1333,32 @@ class _SketchBatchStruct(ctypes.Structure):      # gq_sketch_batch (include/gq_s
                 ("unit_tab", ctypes.c_void_p), ("list", ctypes.c_void_p), ("part", ctypes.c_void_p), ("table", ctypes.c_void_p),
                 ("est", ctypes.c_void_p), ("dec_table", ctypes.c_void_p), ("hist", ctypes.c_void_p), ("state", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p), ("etab", ctypes.c_void_p), ("dense_table", ctypes.c_void_p), ("ndense", ctypes.c_int32),
-                ("rows", ctypes.c_int32), ("nwindows", ctypes.c_int64), ("nunits", ctypes.c_int64), ("seed", ctypes.c_uint64)]
+                ("rows", ctypes.c_int32), ("nwindows", ctypes.c_int64), ("nunits", ctypes.c_int64), ("seed", ctypes.c_uint64),
+                ("recover", ctypes.c_int32), ("cr", ctypes.c_int32)]
 
 
-assert ctypes.sizeof(_SketchBatchStruct) == 168      # (csrc/sketch.hip asserts the same of gq_sketch_batch)
+assert ctypes.sizeof(_SketchBatchStruct) == 176      # (csrc/sketch.hip asserts the same of gq_sketch_batch)
 
 
 class SketchBatch(_ItemBatch):
     """The launches of libgq_sketch.so: gq_sketch_compress_batched (the sketch launch over the units, the fold launch over the windows)
     and gq_sketch_decode_sum_batched (sum, estimate, top-k's select on the estimates, store, and with `etab` the error accumulation).
-    `tables`: {field: tensor} of everything the descriptor names beside the segment and item tables (include/gq_sketch.h)."""
+    `tables`: {field: tensor} of everything the descriptor names beside the segment and item tables (include/gq_sketch.h).
+    recover "chunked": the decode is the sum launch and ONE recover launch, every item keeping its own len // cr largest estimates;
+    est, dec_table, hist, state and counts are not read and may be left out of `tables`."""
 
     LIBRARY, STRUCT = SKETCH_LIBRARY, _SketchBatchStruct
     _DTYPES = {"lay": torch.int64, "win_tab": torch.int32, "unit_tab": torch.int32, "list": torch.int32, "part": torch.float32,
                "table": torch.float32, "est": torch.float32, "dec_table": torch.int64, "hist": torch.int32, "state": torch.int32,
                "counts": torch.int32, "etab": torch.int64}
 
-    def __init__(self, seg_table, item_seg, nseg, nitems, rows=3, seed=0, nwindows=0, nunits=0, tables=None):
+    def __init__(self, seg_table, item_seg, nseg, nitems, rows=3, seed=0, nwindows=0, nunits=0, tables=None, recover="global", cr=0):
+        if recover not in SKETCH_RECOVER:
+            raise ValueError("SketchBatch: recover must be one of %s, got %r" % (", ".join(SKETCH_RECOVER), recover))
         tables = tables or {}
         _ItemBatch.__init__(self, seg_table, item_seg, nseg, nitems, tuple((f, tables.get(f), dt) for f, dt in self._DTYPES.items()),
-                            rows=int(rows), seed=int(seed) & (2 ** 64 - 1), nwindows=int(nwindows), nunits=int(nunits))
+                            rows=int(rows), seed=int(seed) & (2 ** 64 - 1), nwindows=int(nwindows), nunits=int(nunits),
+                            recover=SKETCH_RECOVER[recover], cr=int(cr))
 
     def part(self, seg_table, item_seg, nseg, nitems):
         raise GQNativeError("the sketch compressor's decode-mean runs over the whole group: it takes no split or pipelined exchange "

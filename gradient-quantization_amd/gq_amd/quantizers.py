@@ -220,6 +220,8 @@ class PSQuantizer(object):
                 raise ValueError("two_phase is not available with the sketch compressor: the mean it decodes is sparse already, and a "
                                  "second sketch of it would be decoded against other tensors' collisions")
             self.sketch_ef = bool(getattr(args, "sketch_ef", False))
+            # (sketch_recover: every CountSketchCompressor reads it from `args` and refuses a cr the chunked recovery cannot take)
+            self.sketch_recover = getattr(args, "sketch_recover", None) or "global"
             if exchange.configured_mode() not in ("allgather", "direct"):
                 raise ValueError("the sketch compressor's decode-mean runs over the whole gathered wire: GQ_EXCHANGE must be allgather "
                                  "or direct, got %r" % (exchange.configured_mode(),))

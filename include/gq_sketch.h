@@ -53,6 +53,13 @@
  *              as 0x7fffffff; the k largest keys, of the keys equal to the k-th largest the lowest indices.
  *              out_i = est_i where kept, +0 elsewhere.
  *              Then, with error accumulation:  E[cell] = T[cell] - sketch(out)[cell], sketch() the compress with SUM ORDER's sums.
+ *
+ * CHUNKED RECOVERY (recover == GQ_SKETCH_RECOVER_CHUNKED; GQ_SKETCH_MIN_CR <= cr <= GQ_SKETCH_MAX_CR).  T, est and E as above; the
+ *              KEPT SET alone differs: it is PER ITEM.  Item a of len elements keeps its own kt = len / cr (integer division) largest
+ *              keys, key as above (bits(est) & 0x7fffffff, a NaN as 0x7fffffff, so above +inf); of the keys equal to the item's
+ *              kt-th largest, the lowest element indices.  kt == 0 (a last item shorter than cr): the item keeps nothing.
+ *              out_i = est_i where kept (the estimate's own bits, a -0 included), +0 elsewhere.  The k of the segment table is not
+ *              read.  A tensor keeps sum over its items of len / cr <= n / cr elements.
  */
 #ifndef GQ_SKETCH_H
 #define GQ_SKETCH_H
@@ -63,12 +70,17 @@
 extern "C" {
 #endif
 
-#define GQ_SKETCH_ABI_VERSION 1
+#define GQ_SKETCH_ABI_VERSION 2      /* 2: gq_sketch_batch ends with { recover, cr } */
 #define GQ_SKETCH_CHUNK 4096         /* elements per item, cells per window */
 #define GQ_SKETCH_CHUNK_ITEMS 8      /* list entries per chunk */
 #define GQ_SKETCH_HEADER_BYTES 16    /* n, r, nwin, 0 in front of a section's cells */
 #define GQ_SKETCH_HIST_BINS 2048     /* histogram words per tensor (the select of include/gq_topk.h) */
 #define GQ_SKETCH_MAX_ROWS 5
+#define GQ_SKETCH_RECOVER_GLOBAL 0   /* the tensor's k largest estimates */
+#define GQ_SKETCH_RECOVER_CHUNKED 1  /* every item's own len / cr largest estimates */
+#define GQ_SKETCH_MIN_CR 2           /* cr of the chunked recovery */
+#define GQ_SKETCH_MAX_CR 4096
+#define GQ_SKETCH_BATCH_BYTES_V1 168 /* the descriptor without { recover, cr }: GQ_SKETCH_RECOVER_GLOBAL */
 
 /*
  * The tensors of one group.  W = the group's windows, numbered tensor by tensor, row-major inside a tensor; U = its units (a unit
@@ -87,6 +99,9 @@ extern "C" {
  *   etab      int64[nseg]: E of every tensor (float *, r * nwin * 4096 each), or NULL: no error accumulation
  *   dense_table int64[ndense][3]: gq_topk_batch.dense_table
  * A compress needs seg_table, lay, win_tab, unit_tab, list, part (and everything else where it is asked for `out`).
+ *   recover, cr  the last two fields.  struct_bytes tells the two layouts apart: GQ_SKETCH_BATCH_BYTES_V1 (a caller built against
+ *             version 1) is read as GQ_SKETCH_RECOVER_GLOBAL.  Under GQ_SKETCH_RECOVER_CHUNKED est, dec_table, hist, state and counts
+ *             are not read and may be NULL; cr is read in that mode alone.
  */
 typedef struct gq_sketch_batch {
     uint32_t struct_bytes;     /* sizeof(gq_sketch_batch) */
@@ -112,6 +127,8 @@ typedef struct gq_sketch_batch {
     int64_t nwindows;
     int64_t nunits;
     uint64_t seed;
+    int32_t recover;           /* GQ_SKETCH_RECOVER_* */
+    int32_t cr;                /* GQ_SKETCH_RECOVER_CHUNKED: an item keeps len / cr elements */
 } gq_sketch_batch;
 
 int gq_sketch_abi_version(void);
@@ -127,7 +144,7 @@ int gq_sketch_build_lists(uint64_t seed, int rows, int64_t items, int64_t nwin, 
  * Two launches: the sketch launch (a workgroup per unit: the chunk's items staged through LDS, 16 cells per thread in registers)
  * and the fold launch (a workgroup per window: the chunks in order, the header, the dense copies).  ef_scale must be NaN (this
  * compressor keeps no per-user residual).  out != NULL: also the decode-mean of this one payload WITHOUT error accumulation at
- * out + out offset (eleven launches more).
+ * out + out offset (eleven launches more; two under GQ_SKETCH_RECOVER_CHUNKED).
  */
 int gq_sketch_compress_batched(const gq_sketch_batch *b, uint8_t *wire, float ef_scale, float *out, void *stream);
 
@@ -135,6 +152,8 @@ int gq_sketch_compress_batched(const gq_sketch_batch *b, uint8_t *wire, float ef
  * DECODE-MEAN of R payloads (payload r at gathered + r * user_stride_bytes, 4-byte aligned) into out + out offset: the sum launch,
  * the estimate launch, the select's six, count, scan, store -- and with error accumulation (etab != NULL and plain == 0) the sketch
  * and fold launches once more, E = T - sketch(out).  plain (R == 1 only): one payload's decode, E neither read nor written.
+ * Under GQ_SKETCH_RECOVER_CHUNKED the sum launch and ONE recover launch (a workgroup per item: the rows' windows through LDS, the
+ * median, a radix select of the item's kt-th largest key in a 256-bin LDS histogram, the dense store) stand for the first eleven.
  */
 int gq_sketch_decode_sum_batched(const gq_sketch_batch *b, const uint8_t *gathered, int64_t user_stride_bytes, int R, float *out,
                                  int plain, void *stream);
